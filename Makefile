@@ -5,7 +5,7 @@ WORLD ?= 3
 NPROC ?= 8
 MASTER_PORT ?= 29500
 
-.PHONY: build install setup graph first second server single gpu launch launch-gpu bench \
+.PHONY: build install setup graph first second server single gpu launch launch-gpu bench bench-full \
 	bench-scale bench-scale-central test test-gpu profile dist clean asan
 
 # compile every gfx950 HIP kernel + bindings into distributed_ml_pytorch_amd/_native*.so
@@ -45,13 +45,17 @@ launch:
 launch-gpu:
 	$(PY) run-pytorch.py --nproc $(NPROC) --gpus -- --cuda --model resnet18 --ps sharded
 
+# headline steps only; bench-full adds the reference batch and time-to-target runs
 bench:
 	$(PY) bench.py
+
+bench-full:
+	$(PY) bench.py --full
 
 bench-scale:
 	for n in 1 2 4 8; do \
 	  $(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $$n --master-addr 127.0.0.1 \
-	    --master-port $(MASTER_PORT) bench.py --gpus $$n || exit $$?; \
+	    --master-port $(MASTER_PORT) bench.py --gpus $$n --full || exit $$?; \
 	done
 
 # the reference topology at every N: rank 0 = parameter server, ranks 1..N-1 = workers
@@ -59,7 +63,7 @@ bench-scale:
 bench-scale-central:
 	for n in 2 4 8; do \
 	  $(PY) -m torch.distributed.run --nnodes=1 --nproc-per-node $$n --master-addr 127.0.0.1 \
-	    --master-port $(MASTER_PORT) bench.py --gpus $$n --ps central || exit $$?; \
+	    --master-port $(MASTER_PORT) bench.py --gpus $$n --ps central --full || exit $$?; \
 	done
 
 test:

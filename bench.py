@@ -43,6 +43,19 @@ never touches the GPU) and relays rank 0's line; under a launcher
 Timing: W untimed warmup steps, then exactly K steps bracketed by barrier +
 ``torch.cuda.synchronize()`` on both sides; the max elapsed over ranks is used.
 Rank 0 prints ONE JSON line.
+
+A plain run (``--gpus N --steps K --warmup W``) does only what the headline
+figure needs: set-up, warmup, the K timed steps, the line.  Everything else the
+benchmark measures runs only with ``--full``: the K steps at the reference's
+batch (``--ref-batch``), the time-to-target-loss runs (``--ttl-*``, ASGD and
+the sync-DP comparison) and, at N > 1, the reference-topology check
+(``--central-check``).  Without ``--full`` those options are ignored.
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller
+(``loss.npy``, ``hits.npy``) and the fp32 master parameters it left behind
+(``params.npy``) as float32 arrays; a model above ``_DUMP_MAX_PARAMS`` elements
+is sampled at fixed seeded indices (``params_index.npy``).  Weights and batches
+are seeded, so two builds given the same arguments see identical inputs.
 """
 from __future__ import annotations
 
@@ -72,9 +85,16 @@ def parse(argv=None):
     ap.add_argument("--model", default="resnet18")
     ap.add_argument("--batch", type=int, default=512,
                     help="per-GPU batch (sweep: profiles/batch_sweep_r1.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: --ref-batch, the "
+                         "time-to-target runs (--ttl-*) and the central check at N > 1; "
+                         "without it those options are ignored")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs (loss, "
+                         "hits, fp32 master parameters) to DIR/<name>.npy as float32")
     ap.add_argument("--ref-batch", type=int, default=64,
-                    help="also time K steps at the reference's default batch "
-                         "(/root/reference/example/main.py:142); 0 skips")
+                    help="with --full: also time K steps at the reference's default batch "
+                         "(its example/main.py:142); 0 skips")
     ap.add_argument("--mode", default="asgd", choices=["asgd", "sync", "single"])
     ap.add_argument("--ps", default="auto", choices=["auto", "local", "sharded", "sharded_async", "central"])
     ap.add_argument("--delta-scale", default="auto",
@@ -96,7 +116,8 @@ def parse(argv=None):
     ap.add_argument("--profile-steps", type=int, default=0,
                     help="extra steps after timing, for rocprofv3 windows")
     ap.add_argument("--ttl-target", type=float, default=0.5,
-                    help="after the throughput run: train a FRESH model on learnable synthetic "
+                    help="with --full, after the throughput run: "
+                         "train a FRESH model on learnable synthetic "
                          "data until the mean loss of 10 steps <= target and report the "
                          "wall time (the metric's time-to-target-loss half); 0 skips")
     ap.add_argument("--ttl-max-steps", type=int, default=4000)
@@ -120,7 +141,8 @@ def parse(argv=None):
     ap.add_argument("--ttl-heldout-acc", type=float, default=0.7,
                     help="held-out accuracy target: ttl_heldout_steps = first evaluation at or above it")
     ap.add_argument("--central-check", type=int, default=-1,
-                    help="after the JSON line, at N>1: STEPS of the reference topology (rank 0 "
+                    help="with --full, before the JSON line, at N>1: "
+                         "STEPS of the reference topology (rank 0 "
                          "= PS, pushes / pulls over the per-pair payload communicators, RCCL on "
                          "GPUs) with a one-line report on stderr; -1 = 12 when the timed run "
                          "is not already central, 0 = off")
@@ -129,7 +151,11 @@ def parse(argv=None):
                          "benchmark line is already out)")
     ap.add_argument("--ttl-compare-sync", type=int, default=1,
                     help="also measure time-to-target of sync all-reduce DP at the same N")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if not a.full:
+        # a plain run times the headline steps only
+        a.ref_batch, a.ttl_target, a.central_check = 0, 0.0, 0
+    return a
 
 
 # ----------------------------------------------------------------------- spawn
@@ -236,7 +262,7 @@ def _serve(a, cfg, ctx, sessions: int):
 
 
 def _timed_steps(w, pool, steps, warmup, ctx, clock=None):
-    """Returns (elapsed s, last loss); ``clock`` (utils.metrics.ClockSampler)
+    """Returns (elapsed s, last loss, last hits); ``clock`` (utils.metrics.ClockSampler)
     samples sclk / power over exactly the timed window."""
     trace = os.environ.get("DMP_BENCH_LOSSES") == "1"
     seen = []
@@ -253,7 +279,7 @@ def _timed_steps(w, pool, steps, warmup, ctx, clock=None):
     t0 = time.perf_counter()
     for _ in range(steps):
         x, y = pool.next()
-        loss, _ = w.train_step(x, y, keep=trace)   # untraced: only the last loss is read
+        loss, hits = w.train_step(x, y, keep=trace)   # untraced: only the last step's are read
         if trace:
             seen.append(loss)
     _sync()
@@ -264,7 +290,30 @@ def _timed_steps(w, pool, steps, warmup, ctx, clock=None):
     if trace:
         print("[trace] losses " + " ".join(f"{float(v.float()):.3g}" for v in seen)
               + f" |p| {w.param_norm():.4f}", file=sys.stderr, flush=True)
-    return elapsed, loss
+    return elapsed, loss, hits
+
+
+_DUMP_MAX_PARAMS = 12 * 2 ** 20     # 48 MB of float32: the whole dump stays under 64 MB
+
+
+def _dump_outputs(path, w, loss, hits):
+    """What the last timed step handed back (loss, hits) and the fp32 master
+    parameters it left, as ``path/<name>.npy`` in float32.  A model with more than
+    ``_DUMP_MAX_PARAMS`` parameters is sampled at fixed (seeded, sorted) indices,
+    stored beside the sample as ``params_index.npy``."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    flat = w.arena.p32.detach().reshape(-1)
+    if flat.numel() > _DUMP_MAX_PARAMS:
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, flat.numel(), (_DUMP_MAX_PARAMS // 4,), generator=g).sort().values
+        np.save(os.path.join(path, "params_index.npy"), idx.numpy().astype(np.float64))
+        flat = flat[idx.to(flat.device)]
+    np.save(os.path.join(path, "params.npy"), flat.float().cpu().numpy())
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    np.save(os.path.join(path, "hits.npy"), hits.detach().float().reshape(-1).cpu().numpy())
 
 
 def time_to_target(a, cfg, ctx, mode=None):
@@ -487,7 +536,9 @@ def run(a):
         from distributed_ml_pytorch_amd.utils.metrics import ClockSampler
 
         clock = ClockSampler(w.device.index or 0) if w.device.type == "cuda" else None
-        elapsed, loss = _timed_steps(w, pool, a.steps, a.warmup, ctx, clock)
+        elapsed, loss, hits = _timed_steps(w, pool, a.steps, a.warmup, ctx, clock)
+        if a.dump_outputs and info.rank == (1 if ctx.central else 0):
+            _dump_outputs(a.dump_outputs, w, loss, hits)     # the first worker's
         res["gpu_clock"] = getattr(w, "clock_reading", None)
         final_loss = float(loss.float().item())
         graphed = bool(getattr(w, "use_graph", False) and w.graph is not None)
@@ -499,7 +550,7 @@ def run(a):
         if a.ref_batch:
             pool64 = DeviceBatchPool(a.ref_batch, w.input_shape, w.num_classes, w.device,
                                      n_batches=4, dtype=w.compute_dtype, seed=info.rank + 7)
-            ref_elapsed, _ = _timed_steps(w, pool64, a.steps, max(a.warmup, 3), ctx)
+            ref_elapsed, _, _ = _timed_steps(w, pool64, a.steps, max(a.warmup, 3), ctx)
         _sync()
         in_shape = tuple(w.input_shape)
         dev_name = str(w.device)

@@ -6,7 +6,7 @@ export DMP_CONV_TUNE_SEED=: DMP_CONV_TUNE_CACHE=gpurun_out/mi355x_tune_cache.jso
 rm -f $DMP_CONV_TUNE_CACHE
 OUT=gpurun_out/tune_cache.log; : > $OUT
 run() { echo "== $*" >> $OUT; timeout -k 10 400 "$@" >> $OUT 2>&1; }
-run python bench.py --steps 10 --warmup 3 --ttl-target 0 \
+run python bench.py --steps 10 --warmup 3 --full --ttl-target 0 \
  && run python bench.py --steps 5 --warmup 2 --ttl-target 0 --ref-batch 0 --model resnet50 --batch 128 \
  && run python bench.py --steps 5 --warmup 2 --ttl-target 0 --ref-batch 0 --model vit_b16 --batch 64 \
  && run python bench.py --steps 5 --warmup 2 --ttl-target 0 --ref-batch 0 --model alexnet --batch 64 \

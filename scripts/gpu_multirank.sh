@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" && mkdir -p gpurun_out && export TMP
 OUT=gpurun_out/multirank.log; : > $OUT
 run() { echo "== $*" >> $OUT; timeout -k 10 300 "$@" >> $OUT 2>&1; }
 export DMP_DIST_BACKEND=gloo
-STEPS="--steps 20 --warmup 5 --ttl-target 0 --ref-batch 0"
+STEPS="--steps 20 --warmup 5 --full --ttl-target 0 --ref-batch 0"
 run python bench.py --gpus 2 $STEPS --ps central \
  && run python bench.py --gpus 3 $STEPS --ps central \
  && run python bench.py --gpus 2 $STEPS \

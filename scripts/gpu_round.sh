@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 ok_rc() { case "$1" in 0|1) return 0;; *) return 1;; esac; }   # 1 = test failures, not a fault
 
 STAGE=${1:-all}
-BENCH_ARGS=${BENCH_ARGS:-"--steps 30 --warmup 10"}
+BENCH_ARGS=${BENCH_ARGS:-"--steps 30 --warmup 10 --full"}
 
 if [[ "$STAGE" == all || "$STAGE" == tests ]]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1

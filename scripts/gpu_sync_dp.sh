@@ -9,5 +9,5 @@ run python bench.py --steps 30 --warmup 10 --ttl-target 0 --ref-batch 0 --mode s
  && run python bench.py --steps 30 --warmup 10 --ttl-target 0 --ref-batch 0 --mode sync \
  && run python bench.py --steps 20 --warmup 5 --ttl-target 0 --ref-batch 0 --mode single --model resnet50 --batch 128 \
  && run python bench.py --steps 20 --warmup 5 --ttl-target 0 --ref-batch 0 --mode sync --model resnet50 --batch 128 \
- && run python bench.py
+ && run python bench.py --full
 rc=$?; grep -E "^==|^\{" $OUT | cut -c1-600; echo "rc=$rc"; exit $rc

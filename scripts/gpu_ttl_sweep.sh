@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" && mkdir -p gpurun_out && export TMP
 OUT=gpurun_out/ttl_sweep.log; : > $OUT
 for sig in ${SIGNALS:-0.1 0.05 0.03}; do
   echo "== signal $sig" >> $OUT
-  timeout -k 10 240 python bench.py --steps 5 --warmup 2 --ref-batch 0 --ttl-signal $sig \
+  timeout -k 10 240 python bench.py --steps 5 --warmup 2 --full --ref-batch 0 --ttl-signal $sig \
     --ttl-batches ${TTL_BATCHES:-128} --ttl-max-steps 4000 --ttl-compare-sync 1 >> $OUT 2>&1 || exit $?
 done
 grep -E "^==|^\{" $OUT | python3 -c "

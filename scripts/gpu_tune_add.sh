@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" && mkdir -p gpurun_out/tadd && export TMPDIR=/tmp
 cp tuning/mi355x_tune_cache.json gpurun_out/tadd/tc.json
 export DMP_CONV_TUNE_CACHE=gpurun_out/tadd/tc.json
-DMP_CONV_TUNE_ROUNDS=4 DMP_CONV_TUNE_REPS=10 timeout -k 10 300 python bench.py --steps 10 --warmup 3 --ttl-target 0 > gpurun_out/tadd/tune.log 2>&1 || exit $?
+DMP_CONV_TUNE_ROUNDS=4 DMP_CONV_TUNE_REPS=10 timeout -k 10 300 python bench.py --steps 10 --warmup 3 --full --ttl-target 0 > "${DMP_CONV_TUNE_CACHE%/*}/tune.log" 2>&1 || exit $?
 python3 -c "import json; print(len(json.load(open('gpurun_out/tadd/tc.json'))), 'entries')"
 timeout -k 10 300 python bench.py --steps 60 --warmup 10 --ttl-target 0 --ref-batch 0 > gpurun_out/tadd/bench.log 2>&1 || exit $?
 tail -1 gpurun_out/tadd/bench.log | cut -c1-200

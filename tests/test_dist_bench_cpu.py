@@ -38,7 +38,7 @@ def _bench(args, env_extra=None, timeout=300):
 def test_bench_self_spawns_n_ranks():
     """``bench.py --gpus 4`` with no launcher env starts 4 ranks itself."""
     r, lines = _bench(["--gpus", "4", "--steps", "2", "--warmup", "1", "--model", "mlp",
-                       "--batch", "8", "--ttl-target", "0", "--ref-batch", "0"])
+                       "--batch", "8", "--full", "--ttl-target", "0", "--ref-batch", "0"])
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert len(lines) == 1, r.stdout
     out = json.loads(lines[0])
@@ -86,7 +86,7 @@ def test_bench_sharded_async_three_ranks():
     """``--ps sharded_async``: every rank trains; shard servers answer point-to-point."""
     r, lines = _bench(["--gpus", "3", "--ps", "sharded_async", "--steps", "4", "--warmup", "2",
                        "--model", "mlp", "--batch", "8", "--n-push", "2", "--n-pull", "2",
-                       "--ttl-target", "0", "--ref-batch", "0"])
+                       "--full", "--ttl-target", "0", "--ref-batch", "0"])
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     assert len(lines) == 1, r.stdout
     out = json.loads(lines[0])
@@ -99,7 +99,7 @@ def test_bench_central_ps_with_time_to_target():
     r, lines = _bench(["--gpus", "3", "--ps", "central", "--steps", "2", "--warmup", "1",
                        "--model", "mlp", "--batch", "16", "--n-push", "2", "--n-pull", "2",
                        "--ttl-target", "1.5", "--ttl-max-steps", "200", "--ttl-signal", "1.0",
-                       "--ref-batch", "0", "--lr", "0.05"])
+                       "--ref-batch", "0", "--lr", "0.05", "--full"])
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     out = json.loads(lines[0])
     assert out["ttl_reached"] and out["ttl_steps"] <= 200
@@ -116,11 +116,42 @@ def test_bench_ttl_heldout_plateau_stop():
     r, lines = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--model", "mlp",
                        "--batch", "16", "--ttl-target", "5.0", "--ttl-max-steps", "3000",
                        "--ttl-heldout-acc", "1.01", "--ttl-eval-every", "10",
-                       "--ttl-plateau-steps", "40", "--ref-batch", "0", "--ttl-compare-sync", "0"])
+                       "--ttl-plateau-steps", "40", "--ref-batch", "0", "--ttl-compare-sync", "0",
+                       "--full"])
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     out = json.loads(lines[0])
     assert out["ttl_reached"] and not out["ttl_heldout_reached"]
     assert out["ttl_heldout_plateau_stop"] and 0.0 <= out["ttl_heldout_best_acc"] <= 1.0
+
+
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` only the headline steps run (no reference-batch or
+    time-to-target figures, even when their options are given), ``--steps`` sets
+    the timed steps, and ``--dump-outputs`` writes the last step's outputs: the
+    same arrays from two runs with the same arguments (seeded weights / batches)."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r, lines = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--model", "mlp",
+                           "--batch", "16", "--ttl-target", "5.0", "--dump-outputs", str(d)])
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert out["steps"] == 5 and out["warmup"] == 2 and out["unit"] == "samples/s"
+        assert out["ms_per_step"] > 0
+        assert out["value"] == pytest.approx(16 * 1e3 / out["ms_per_step"], rel=1e-3)
+        assert "reference_batch" not in out and "ttl_steps" not in out
+        assert "ttl_sync_dp" not in out and "central_check" not in out
+        got = {f: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sorted(got) == ["hits.npy", "loss.npy", "params.npy"]
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in got.values())
+        assert got["loss.npy"].shape == (1,) and got["params.npy"].size > 1000
+        assert got["loss.npy"][0] == pytest.approx(out["final_loss"], abs=1e-4)
+        dumps.append(got)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_bench_rejects_world_size_mismatch():

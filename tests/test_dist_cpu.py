@@ -271,7 +271,7 @@ def test_bench_two_ranks_sharded_ps_cpu():
            "--master-addr", "127.0.0.1", "--master-port", str(_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--model", "lenet", "--batch", "16", "--n-push", "2", "--n-pull", "2",
-           "--ttl-target", "2.2", "--ttl-max-steps", "60"]
+           "--ttl-target", "2.2", "--ttl-max-steps", "60", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

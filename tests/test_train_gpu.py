@@ -83,8 +83,8 @@ def test_bench_script_runs():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3",
-                        "--warmup", "1", "--batch", "32"], capture_output=True, text=True,
-                       timeout=600)
+                        "--warmup", "1", "--batch", "32", "--full"],
+                       capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
