@@ -3,6 +3,7 @@
 // file, loaded with ctypes.  Never part of the extension.
 #include "../common.h"
 #include "../launchers.h"
+#include "../mfma_prims.h"
 
 extern "C" {
 
@@ -46,12 +47,6 @@ long long abl_wgrad_slab_elems(int cfg, int B, int H, int W, int CI, int CO, int
 // HBM-streamed when large), `iters` rounds of INF pieces per wave.
 namespace {
 
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rs, unsigned voff, uint16_t* lds) {
-  const unsigned m0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)lds;
-  asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs),
-               "{m0}"(m0));
-}
-
 template <int NW, int INF>
 __global__ void __launch_bounds__(64 * NW) dma_ceiling_kernel(const uint16_t* src, unsigned mask,
                                                               int iters, int* sink) {
@@ -65,7 +60,7 @@ __global__ void __launch_bounds__(64 * NW) dma_ceiling_kernel(const uint16_t* sr
   for (int it = 0; it < iters; ++it) {
 #pragma unroll
     for (int j = 0; j < INF; ++j)
-      dma16(rs, (off + j * 1024u) & mask, lds + (wid * INF + j) * 512);
+      dmp::dma16(rs, (off + j * 1024u) & mask, lds + (wid * INF + j) * 512);
     off = (off + step) & mask;
     __builtin_amdgcn_s_waitcnt(0x0070);   // vmcnt(0): the round landed
   }

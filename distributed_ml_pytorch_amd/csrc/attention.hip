@@ -32,23 +32,16 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "mfma_prims.h"
 
 namespace dmp {
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int kDH = 64;          // head dim
 constexpr int kRS = kDH + 8;     // row stride (elements) of row-major [token][64] LDS tiles
 constexpr int kMaxKB = 16;       // <= 256 tokens: 16 blocks of 16
 constexpr float kLn2 = 0.6931471805599453f;
-
-__device__ __forceinline__ f32x4 mfma(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                 __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
 
 __device__ __forceinline__ bf16x8 pack8(const f32x4& lo, const f32x4& hi) {
   bf16x8 r;
@@ -152,8 +145,8 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_kernel(const u16* __restrict
       if (kb < nkb) {
         const u16* kr = Ks + (kb * 16 + l16) * kRS + 8 * g;
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = mfma(ld16(kr), qf0, acc);
-        acc = mfma(ld16(kr + 32), qf1, acc);
+        acc = mfma16(ld16(kr), qf0, acc);
+        acc = mfma16(ld16(kr + 32), qf1, acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float v = (kb * 16 + 4 * g + r) < N ? acc[r] * scale_log2 : -INFINITY;
@@ -186,7 +179,7 @@ __global__ void __launch_bounds__(64 * NW) attn_fwd_kernel(const u16* __restrict
         const bf16x8 pb = pack8(s[2 * kp], s[2 * kp + 1]);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb)
-          o[nb] = mfma(ld_tr_perm(Vs, 32 * kp, nb * 16, lane), pb, o[nb]);
+          o[nb] = mfma16(ld_tr_perm(Vs, 32 * kp, nb * 16, lane), pb, o[nb]);
       }
     }
     if (q < N) {
@@ -245,10 +238,10 @@ __global__ void __launch_bounds__(64 * NW) attn_bwd_dq_kernel(
           const u16* kr = Ks + (kb * 16 + l16) * kRS + 8 * g;
           const u16* vr = Vs + (kb * 16 + l16) * kRS + 8 * g;
           f32x4 st = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-          st = mfma(ld16(kr), qf0, st);
-          st = mfma(ld16(kr + 32), qf1, st);
-          dp = mfma(ld16(vr), df0, dp);
-          dp = mfma(ld16(vr + 32), df1, dp);
+          st = mfma16(ld16(kr), qf0, st);
+          st = mfma16(ld16(kr + 32), qf1, st);
+          dp = mfma16(ld16(vr), df0, dp);
+          dp = mfma16(ld16(vr + 32), df1, dp);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float p = (kb * 16 + 4 * g + r) < N
@@ -259,7 +252,7 @@ __global__ void __launch_bounds__(64 * NW) attn_bwd_dq_kernel(
         const bf16x8 db = pack8(ds[0], ds[1]);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb)
-          dq[nb] = mfma(ld_tr_perm(Ks, 32 * kp, nb * 16, lane), db, dq[nb]);
+          dq[nb] = mfma16(ld_tr_perm(Ks, 32 * kp, nb * 16, lane), db, dq[nb]);
       }
     }
     if (q < N) {
@@ -344,10 +337,10 @@ __global__ void __launch_bounds__(64 * NW) attn_bwd_dkv_kernel(
           const u16* qr = Qs + (qb * 16 + l16) * kRS + 8 * g;
           const u16* dr = Ds + (qb * 16 + l16) * kRS + 8 * g;
           f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-          s = mfma(ld16(qr), kf0, s);
-          s = mfma(ld16(qr + 32), kf1, s);
-          dp = mfma(ld16(dr), vf0, dp);
-          dp = mfma(ld16(dr + 32), vf1, dp);
+          s = mfma16(ld16(qr), kf0, s);
+          s = mfma16(ld16(qr + 32), kf1, s);
+          dp = mfma16(ld16(dr), vf0, dp);
+          dp = mfma16(ld16(dr + 32), vf1, dp);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int qq = qb * 16 + 4 * g + r;
@@ -359,8 +352,8 @@ __global__ void __launch_bounds__(64 * NW) attn_bwd_dkv_kernel(
         const bf16x8 pb = pack8(pp[0], pp[1]), db = pack8(ds[0], ds[1]);
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
-          dv[nb] = mfma(ld_tr_perm(Ds, 32 * qp, nb * 16, lane), pb, dv[nb]);
-          dk[nb] = mfma(ld_tr_perm(Qs, 32 * qp, nb * 16, lane), db, dk[nb]);
+          dv[nb] = mfma16(ld_tr_perm(Ds, 32 * qp, nb * 16, lane), pb, dv[nb]);
+          dk[nb] = mfma16(ld_tr_perm(Qs, 32 * qp, nb * 16, lane), db, dk[nb]);
         }
       }
     }

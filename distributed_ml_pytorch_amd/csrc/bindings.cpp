@@ -299,38 +299,6 @@ std::vector<Tensor> bn_bwd(Tensor x, Tensor dy, optional<Tensor> y, optional<Ten
   return {dx, want_dres ? dres : Tensor()};
 }
 
-// dz: the already ReLU-masked output gradient; part: the slot sums the consuming
-// conv's dgrad epilogue accumulated (re-zeroed here)
-Tensor bn_bwd_from_partials(Tensor x, Tensor dz, optional<Tensor> gamma, Tensor stats,
-                            optional<Tensor> dgamma, optional<Tensor> dbeta, Tensor part) {
-  check_nhwc_bf16(x, "x");
-  check_nhwc_bf16(dz, "dz");
-  const int64_t C = channels_of(x);
-  const int64_t M = x.numel() / C;
-  TORCH_CHECK(C % 8 == 0 && C <= 2048, "bn: bad C");
-  TORCH_CHECK(dz.sizes() == x.sizes(), "dz shape mismatch");
-  TORCH_CHECK(stats.scalar_type() == at::kFloat && stats.numel() == 4 * C, "bad stats");
-  for (auto* t : {&gamma, &dgamma, &dbeta}) {
-    if (t->has_value()) {
-      TORCH_CHECK((*t)->is_cuda() && (*t)->scalar_type() == at::kFloat && (*t)->numel() == C &&
-                      (*t)->is_contiguous(),
-                  "bn gamma/dgamma/dbeta must be contiguous fp32 [C]");
-    }
-  }
-  auto fopt = x.options().dtype(at::kFloat);
-  part = bn_slots(part, C, fopt);
-  auto dx = at::empty_like(x);
-  auto coef = at::empty({3, C}, fopt);
-  dmp::launch_bn_bwd_from_partials(reinterpret_cast<const uint16_t*>(x.data_ptr()),
-                                   reinterpret_cast<const uint16_t*>(dz.data_ptr()),
-                                   ptr_or_null<float>(gamma), stats.data_ptr<float>(),
-                                   ptr_or_null<float>(dgamma), ptr_or_null<float>(dbeta),
-                                   coef.data_ptr<float>(), part.data_ptr<float>(),
-                                   reinterpret_cast<uint16_t*>(dx.data_ptr()), M, (int)C,
-                                   cur_stream());
-  return dx;
-}
-
 // ------------------------------------------------------------------ pooling
 // fused GAP + Linear head: [y [B, N] bf16, f [B, C] bf16 (pooled features, kept
 // for the weight gradient)]
@@ -676,9 +644,7 @@ void zero_(Tensor t) {
 
 Tensor conv_dgrad(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t stride, int64_t pad,
                   int64_t cfg, optional<Tensor> wt_pre, optional<Tensor> addend,
-                  optional<Tensor> bn_x, optional<Tensor> bn_mask, optional<Tensor> bn_stats,
-                  optional<Tensor> bn_part, int64_t bn_relu, bool addend_sub,
-                  optional<Tensor> addend_mask) {
+                  bool addend_sub, optional<Tensor> addend_mask) {
   dy = dy.contiguous(at::MemoryFormat::ChannelsLast);
   check_nhwc_bf16(dy, "dy");
   check_gpu(w, "w");
@@ -732,41 +698,11 @@ Tensor conv_dgrad(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t stride, int
                 "dgrad: addend_mask must be the addend's contiguous uint8 [pixels, C/8] bit mask");
     amask = addend_mask->data_ptr<uint8_t>();
   }
-  // fused backward of the BatchNorm(+ReLU) that produced the conv input (bn_relu >= 0)
-  dmp::BnBwdFuse bnf{};
-  const bool fuse = bn_relu >= 0;
-  if (fuse) {
-    TORCH_CHECK(bn_relu <= 3 && bn_x.has_value() && bn_stats.has_value() && bn_part.has_value(),
-                "dgrad: BN fusion needs bn_x, bn_stats and bn_part");
-    check_nhwc_bf16(*bn_x, "bn_x");
-    TORCH_CHECK(bn_x->sizes() == dx.sizes(), "dgrad: bn_x must have the input's shape");
-    TORCH_CHECK(bn_stats->is_cuda() && bn_stats->scalar_type() == at::kFloat &&
-                    bn_stats->is_contiguous() && bn_stats->numel() == 4LL * g.CI,
-                "dgrad: bn_stats must be contiguous fp32 [4, C]");
-    bn_slots(bn_part, g.CI, dy.options().dtype(at::kFloat));
-    if (bn_relu == 1) {
-      TORCH_CHECK(bn_mask.has_value(), "dgrad: bn_relu 1 needs bn_mask");
-      check_nhwc_bf16(*bn_mask, "bn_mask");
-      TORCH_CHECK(bn_mask->sizes() == dx.sizes(), "dgrad: bn_mask must have the input's shape");
-      bnf.mask = reinterpret_cast<const uint16_t*>(bn_mask->data_ptr());
-    } else if (bn_relu == 3) {
-      TORCH_CHECK(bn_mask.has_value() && bn_mask->is_cuda() &&
-                      bn_mask->scalar_type() == at::kByte && bn_mask->is_contiguous() &&
-                      bn_mask->numel() == dx.numel() / 8,
-                  "dgrad: bn_relu 3 needs the uint8 [pixels, C/8] ReLU bit mask");
-      bnf.mask = reinterpret_cast<const uint16_t*>(bn_mask->data_ptr());
-    }
-    bnf.x = reinterpret_cast<const uint16_t*>(bn_x->data_ptr());
-    bnf.stats = bn_stats->data_ptr<float>();
-    bnf.part = bn_part->data_ptr<float>();
-    bnf.relu = (int)bn_relu;
-  }
   dmp::launch_conv_dgrad(reinterpret_cast<const uint16_t*>(dy.data_ptr()),
                          reinterpret_cast<const uint16_t*>(wt.data_ptr()),
                          reinterpret_cast<uint16_t*>(dx.data_ptr()), B, g.H, g.W, g.CI, g.OH,
                          g.OW, g.CO, g.R, g.S, (int)stride, (int)pad, (int)cfg, cur_stream(),
-                         add_ptr, fuse ? &bnf : nullptr, add_ptr != nullptr && addend_sub,
-                         amask);
+                         add_ptr, add_ptr != nullptr && addend_sub, amask);
   return dx;
 }
 
@@ -1776,18 +1712,11 @@ PYBIND11_MODULE(_native, m) {
   m.def("conv_dgrad", &conv_dgrad, "NHWC bf16 implicit-GEMM conv data gradient", py::arg("dy"),
         py::arg("w"), py::arg("H"), py::arg("W"), py::arg("stride"), py::arg("pad"),
         py::arg("cfg") = -1, py::arg("wt") = py::none(), py::arg("addend") = py::none(),
-        py::arg("bn_x") = py::none(), py::arg("bn_mask") = py::none(),
-        py::arg("bn_stats") = py::none(), py::arg("bn_part") = py::none(),
-        py::arg("bn_relu") = -1, py::arg("addend_sub") = false,
-        py::arg("addend_mask") = py::none());
+        py::arg("addend_sub") = false, py::arg("addend_mask") = py::none());
   m.def("subsample2", &subsample2, "x[:, :, ::2, ::2] of a channels_last bf16 activation",
         py::arg("x"));
   m.def("add_subsampled2", &add_subsampled2, "dx[:, :, ::2, ::2] += xs in place",
         py::arg("dx"), py::arg("xs"));
-  m.def("bn_bwd_from_partials", &bn_bwd_from_partials,
-        "BN backward from conv-dgrad-epilogue partials (dz already ReLU-masked)", py::arg("x"),
-        py::arg("dz"), py::arg("gamma"), py::arg("stats"), py::arg("dgamma"), py::arg("dbeta"),
-        py::arg("part"));
   m.def("pad_rows_batched", &pad_rows_batched, "padded-row copies of im2col conv weights");
   m.def("zero_", &zero_, "native zero fill of a dense GPU tensor (a kernel, not a memset)");
   m.def("conv_weight_transpose_batched", &conv_weight_transpose_batched,

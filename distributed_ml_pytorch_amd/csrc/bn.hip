@@ -1457,19 +1457,6 @@ void launch_maxpool_bn_bwd_fold(const u16* x, const u16* dp, const uint8_t* idx,
 }  // namespace dmp
 
 namespace dmp {
-// BN backward whose reductions were already made per block by the consuming
-// conv's data-gradient epilogue (conv.hip bnb_*, which also applied the ReLU
-// mask: dz arrives masked): finalize + a mask-free apply, no reduce pass.
-void launch_bn_bwd_from_partials(const u16* x, const u16* dz, const float* gamma,
-                                 const float* stats, float* dgamma, float* dbeta, float* coef,
-                                 float* part, u16* dx, long long M, int C, hipStream_t s) {
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(1024), 0, s, part,
-                     kBnSlots, M, C, gamma, stats, dgamma, dbeta, coef);
-  const long long nvec = M * C / 8;
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<0, false>), dim3(stream_grid(nvec, 256)), dim3(256), 0,
-                     s, x, dz, nullptr, nullptr, coef, stats, dx, nullptr, nvec, C);
-}
-
 // BN forward whose statistics were already reduced per block by the producing
 // conv's epilogue (conv.hip STATS): finalize + apply only, no stats pass over x.
 void launch_bn_fwd_partials(const u16* x, const u16* res, u16* y, const float* gamma,

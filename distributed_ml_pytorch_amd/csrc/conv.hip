@@ -45,6 +45,7 @@
 #define DMP_HALO_STORE_AUX 2
 #endif
 #include "launchers.h"
+#include "mfma_prims.h"
 
 // Roofline ablations (scripts/conv_roofline.py builds a separate library with
 // -DDMP_ABLATE=N; the extension itself is always built with 0):
@@ -59,10 +60,6 @@
 
 namespace dmp {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-
 
 struct ConvArgs {
   const u16* x;     // gathered operand NHWC [B][GH][GW][CI]   (fwd: X, dgrad: dY)
@@ -74,13 +71,6 @@ struct ConvArgs {
   const float* bias;   // optional fp32 [CO] added in the fwd epilogue
   const u16* addend;   // dgrad: optional [B][H][W][CI] bf16 added to dX in the epilogue
   int relu;            // fwd: max(0, .) in the epilogue (conv -> ReLU, AlexNet)
-  // dgrad with STATS: backward of the BatchNorm(+ReLU) that produced this conv's
-  // input, fused into the epilogue (see bnb_* below)
-  const u16* bnx;       // the BN's input x [B][H][W][CI]
-  const u16* bnmask;    // bnrelu 1: the stored ReLU output (this conv's own input);
-                        // bnrelu 3: bn.hip's 1-bit ReLU mask [pixels][CI/8] bytes
-  const float* bnstat;  // the BN's [4][CI] mean | invstd | scale | shift
-  int bnrelu;           // 0 no ReLU, 1 / 3 mask from bnmask, 2 mask recomputed from bnx
   // dgrad, stride 2: the addend is the gradient of the stride-2 SUBSAMPLED input
   // [B][ceil(H/2)][ceil(W/2)][CI] (a 1x1 / stride-2 shortcut that read x[::2, ::2]):
   // it lands on parity class (0, 0) only, indexed by the class-local row
@@ -93,53 +83,12 @@ struct ConvArgs {
 };
 
 
-// Data-gradient epilogue fused with the backward of the BatchNorm(+ReLU) whose
-// output the conv consumed (dgrad kernels instantiated with STATS): the kernel
-// stores dz = dX * relu'(.) instead of dX, and the two BN-backward reductions
-// sum(dz) and sum(dz * (x - mean)) leave through the same per-block slot sums
-// as the forward statistics (the second scaled by invstd at the block
-// reduction: sum(dz * xhat)).  That removes bn.hip's reduce pass (dY, x and y
-// re-read) and the ReLU-mask input of its apply pass.  The mask is the stored
-// ReLU output > 0 (bnrelu 1: BN + residual + ReLU, whose output is this conv's
-// own input) or is recomputed from x and the folded scale/shift exactly as
-// bn.hip relu_mask_from_x (bnrelu 2).
-__device__ __forceinline__ float bnb_lo(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float bnb_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
-
-// relu'(.) of the BN output: stored output mk (bnrelu 1) or recomputed from the
-// BN input xb and the folded scale/shift (bnrelu 2, rounded as the stored y)
-__device__ __forceinline__ bool bnb_on(int bnrelu, float xb, float mk, float sc, float sh) {
-  if (bnrelu == 1 || bnrelu == 3) return mk > 0.f;
-  if (bnrelu == 2) return bf2f(f2bf(fmaxf(__fmaf_rn(xb, sc, sh), 0.f))) > 0.f;
-  return true;
-}
-
-__device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                 __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-// LDS DMA (buffer_load_dwordx4 ... lds, 16 B per lane into a lane-linear 1 KiB
-// wave slice at m0) from inline asm: with the builtin the compiler cannot tell
-// the ring slot being filled from the one being read and puts s_waitcnt
-// vmcnt(0) before the next ds_read, serialising the pipeline.  Completion is
-// tracked by hand (wait_vm), counted per wave.  Offsets >= the descriptor's
-// num_records read as zeros: that is how padding taps are fetched.
-constexpr unsigned kOOB = 0x80000000u;
-__device__ __forceinline__ void bdma16(__amdgpu_buffer_rsrc_t rs, unsigned voff,
-                                       u16* lds_wave_base) {
-  const unsigned m0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)lds_wave_base;
-  asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs),
-               "{m0}"(m0));
-}
-
 // addend channels n..n+3 at byte offset `boff` (= 2 * element offset) of the
 // addend, with the deferred ReLU mask applied when a.addmask is set
 __device__ __forceinline__ void masked_addend4(const ConvArgs& a, __amdgpu_buffer_rsrc_t rsAdd,
                                                __amdgpu_buffer_rsrc_t rsAm, unsigned boff, bool ok,
                                                int n, float (&ad)[4]) {
-  typedef unsigned int u32x2_m __attribute__((ext_vector_type(2)));
-  const u32x2_m av = __builtin_amdgcn_raw_buffer_load_b64(rsAdd, ok ? boff : kOOB, 0, 0);
+  const u32x2_t av = __builtin_amdgcn_raw_buffer_load_b64(rsAdd, ok ? boff : kOOB, 0, 0);
   ad[0] = __uint_as_float(av.x << 16);
   ad[1] = __uint_as_float(av.x & 0xffff0000u);
   ad[2] = __uint_as_float(av.y << 16);
@@ -162,25 +111,6 @@ __device__ __forceinline__ void small_divmod(int n, int d, float rcp, int& q, in
   else if (r >= d) { ++q; r -= d; }
 }
 
-// sum of v over the 16 lanes of each DPP row, valid in lane 15 of the row:
-// four v_add_f32_dpp row_shr steps (bound_ctrl zero-fills lanes shifted in
-// from outside the row) instead of four ds_bpermute round trips
-__device__ __forceinline__ float row_sum16(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true));
-  return v;
-}
-
-// wait until at most N of this wave's vector-memory ops are outstanding (and
-// all of its LDS ops have completed)
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0070);
-}
-
 // 16-byte chunk swizzle (an involution) for a row-major [rows][BK] bf16 tile.
 //  BK=64 (128-B rows, 2 rows per 256-B bank row): chunk ^= ((row>>1)&3) << 1
 //  BK=32 ( 64-B rows, 4 rows per bank row):       chunk ^= ((row>>2)&1) << 1
@@ -199,6 +129,92 @@ __device__ __forceinline__ int swz(int row, int c) {
   else return c ^ (((row >> 2) & 1) << 1);
 }
 
+// The fragment epilogue of the implicit-GEMM and halo tiles.  Wave (wm, wn)
+// holds TM x TN 16x16 D^T fragments: a lane owns channels n..n+3 of one tile
+// row (8-byte NHWC stores).  Bias and ReLU (FWD), residual addend (add_in: this
+// block adds a.addend, through its deferred bit mask if any), bf16 rounding,
+// store, and (STATS) the BatchNorm slot sums of the stored (rounded) values.
+// row_of(ml, m, pix) maps tile row ml to row m of the block's grid (indexes a
+// subsampled addend) and output pixel pix, and returns whether the row is valid.
+// Stores go through a buffer descriptor with 32-bit offsets; invalid rows and
+// channels past CO get an out-of-range offset and are dropped by the buffer
+// unit (no per-tile branch).  PLAIN: no bias / ReLU / addend, compiled out.
+// AUX: cache policy of the stores.  lds: free, reused for the slot-sum flush.
+template <int BM, int BN, int WM, int WN, bool FWD, bool STATS, bool PLAIN, int AUX, int TM, int TN,
+          class RowOf>
+__device__ __forceinline__ void frag_epilogue(const ConvArgs& a, f32x4 (&acc)[TM][TN], int n0, int wm,
+                                              int wn, int tid, int lane, u16* lds, bool add_in,
+                                              RowOf row_of) {
+  const long long Mtot = (long long)a.B * a.OH * a.OW;
+  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)a.y, 0, (int)(2LL * Mtot * a.CO), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsAdd = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(add_in ? a.addend : a.y), 0, (int)(2LL * Mtot * a.CO), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsAm = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)(add_in && a.addmask ? (const void*)a.addmask : (const void*)a.y), 0,
+      (int)(Mtot * a.CO / 8), 0x00020000);
+  float bj[TN][4];
+  bool nok[TN];
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int n = n0 + wn * (BN / WN) + j * 16 + 4 * (lane >> 4);
+    nok[j] = n < a.CO;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+      bj[j][r] = (FWD && !PLAIN && a.bias != nullptr && n + r < a.CO) ? a.bias[n + r] : 0.f;
+  }
+  float s_sum[TN][4], s_sq[TN][4];
+  if (STATS) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { s_sum[j][r] = 0.f; s_sq[j][r] = 0.f; }
+  }
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    long long m, pix;
+    const bool mok = row_of(wm * (BM / WM) + i * 16 + (lane & 15), m, pix);
+    const unsigned rowoff = 2u * (unsigned)(pix * a.CO);
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int n = n0 + wn * (BN / WN) + j * 16 + 4 * (lane >> 4);
+      const bool ok = mok && nok[j];
+      float ad[4] = {0.f, 0.f, 0.f, 0.f};
+      if (add_in) {
+        const unsigned aoff = a.addend_sub ? 2u * (unsigned)(m * a.CO) : rowoff;
+        masked_addend4(a, rsAdd, rsAm, aoff + 2u * n, ok, n, ad);
+      }
+      u16 h[4];
+      float v[4], t[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        t[r] = PLAIN ? acc[i][j][r] : acc[i][j][r] + bj[j][r] + ad[r];
+        if (FWD && !PLAIN && a.relu) t[r] = fmaxf(t[r], 0.f);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        h[r] = f2bf(t[r]);
+        v[r] = bf2f(h[r]);   // statistics of the stored (rounded) values
+      }
+      const u32x2_t packed = {(u32)h[0] | ((u32)h[1] << 16), (u32)h[2] | ((u32)h[3] << 16)};
+      __builtin_amdgcn_raw_buffer_store_b64(packed, rsY, ok ? rowoff + 2u * n : kOOB, 0, AUX);
+      if (STATS) {
+        const float keep = ok ? 1.f : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float x = v[r] * keep;
+          s_sum[j][r] += x;
+          s_sq[j][r] += x * x;
+        }
+      }
+    }
+  }
+  if (STATS)
+    slot_sum_flush<WM, BN, 64 * WM * WN>(s_sum, s_sq, reinterpret_cast<float*>(lds), wm,
+                                         wn * (BN / WN), tid, lane, a.part, n0, a.CO,
+                                         (blockIdx.x + blockIdx.z * gridDim.x) % kBnSlots);
+}
+
 // MODE 0: forward conv.  MODE 1: data gradient, one parity class per blockIdx.z.
 // NS-stage LDS-DMA ring: NS-1 k-tiles in flight while one is consumed.  (A
 // register-staged variant -- global_load into VGPRs, ds_write_b128 -- measured
@@ -211,8 +227,8 @@ __device__ __forceinline__ void halo_epilogue_rows(const ConvArgs& a, f32x4 (&ac
 // ROWS: the row-staged epilogue of the halo kernels (16-B row segments out of
 // an LDS block tile) instead of the D^T register stores -- for the store-bound
 // 1x1 convs (K = 64 input channels, 4x the output bytes).  Forward tiles, and
-// stride-1 data-gradient tiles without the fused BN backward (output row m =
-// dX pixel m there too; the launcher checks).
+// stride-1 data-gradient tiles (output row m = dX pixel m there too; the
+// launcher checks).
 template <int BM, int BN, int BK, int WM, int WN, int MODE, bool STATS, int NS, bool ROWS = false>
 __global__ void __launch_bounds__(64 * WM * WN) conv_igemm_kernel(ConvArgs a) {
   constexpr int NW = WM * WN;
@@ -230,7 +246,6 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_igemm_kernel(ConvArgs a) {
   // the minimum is conservative for it)
   constexpr int INS_MIN = A_INS / NW + B_INS / NW;
   static_assert(NS >= 2 && (NS - 2) * INS_MIN < 64, "pipeline depth");
-  static_assert(!ROWS || MODE == 0 || !STATS, "row-staged epilogue: no fused BN backward");
   constexpr int LDS_EL = (ROWS && BM * (BN + 8) > NS * STAGE) ? BM * (BN + 8) : NS * STAGE;
   __shared__ __attribute__((aligned(16))) u16 lds[LDS_EL];
 
@@ -325,7 +340,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_igemm_kernel(ConvArgs a) {
       if (A_INS % NW == 0 || ins < A_INS) {
         const int ih = a_h[j] + dh, iw = a_w[j] + dw;
         const bool ok = a_ok[j] && (unsigned)ih < (unsigned)GH && (unsigned)iw < (unsigned)GW;
-        bdma16(rsA, ok ? a_base[j] + adelta : kOOB, As + ins * (RPI * BK));
+        dma16(rsA, ok ? a_base[j] + adelta : kOOB, As + ins * (RPI * BK));
       }
     }
     const unsigned wdelta = 2u * (unsigned)((r * a.S + s) * CI + cb);
@@ -333,7 +348,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_igemm_kernel(ConvArgs a) {
     for (int j = 0; j < B_PW; ++j) {
       const int ins = wid + j * NW;
       if (B_INS % NW == 0 || ins < B_INS)
-        bdma16(rsB, b_base[j] == kOOB ? kOOB : b_base[j] + wdelta, Bs + ins * (RPI * BK));
+        dma16(rsB, b_base[j] == kOOB ? kOOB : b_base[j] + wdelta, Bs + ins * (RPI * BK));
     }
   };
 
@@ -397,156 +412,29 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_igemm_kernel(ConvArgs a) {
     return;
   }
 
-  // epilogue: D^T layout -> lane owns channels n..n+3 of output row m.
-  // Stores go through a buffer descriptor with 32-bit offsets; rows past M and
-  // channels past CO get an out-of-range offset and are dropped by the buffer
-  // unit (no per-tile branch).  Bias (fwd) is fetched once per column tile.
-  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.y, 0, (int)(2LL * a.B * a.OH * a.OW * a.CO), 0x00020000);
   // dgrad accumulate: dX = dgrad + addend (the residual branch's gradient of the
-  // same input, fused here instead of an autograd add over the whole tensor);
-  // forward: the residual of an inference-time BatchNorm fold, before the ReLU
+  // same input, fused here instead of an autograd add over the whole tensor;
+  // a subsampled one lands on parity class 0 only); forward: the residual of an
+  // inference-time BatchNorm fold, before the ReLU
   const bool add_in = a.addend != nullptr && (MODE == 0 || !a.addend_sub || blockIdx.z == 0);
-  const __amdgpu_buffer_rsrc_t rsAdd = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(add_in ? a.addend : a.y), 0, (int)(2LL * a.B * a.OH * a.OW * a.CO), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsAm = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(add_in && a.addmask ? (const void*)a.addmask : (const void*)a.y), 0,
-      (int)(a.B * a.OH * a.OW * (long long)a.CO / 8), 0x00020000);
-  constexpr bool BNB = MODE == 1 && STATS;   // fused BN(+ReLU) backward
-  const __amdgpu_buffer_rsrc_t rsBx = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(BNB ? a.bnx : a.y), 0, (int)(2LL * a.B * a.OH * a.OW * a.CO), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsBm = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(BNB && (a.bnrelu == 1 || a.bnrelu == 3) ? a.bnmask : a.y), 0,
-      (int)((a.bnrelu == 3 ? 1LL : 16LL) * a.B * a.OH * a.OW * a.CO / 8), 0x00020000);
-  float bj[TN][4];
-  bool nok[TN];
-  // BNB: per-channel mean | scale | shift of the BN (channels n..n+3 of tile j)
-  float bmu[BNB ? TN : 1][4], bsc[BNB ? TN : 1][4], bsh[BNB ? TN : 1][4];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * (BN / WN) + j * 16 + 4 * (lane >> 4);
-    nok[j] = n < a.CO;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      bj[j][r] = (MODE == 0 && a.bias != nullptr && n + r < a.CO) ? a.bias[n + r] : 0.f;
-      if constexpr (BNB) {
-        const int ch = nok[j] ? n + r : 0;
-        bmu[j][r] = a.bnstat[ch];
-        bsc[j][r] = a.bnrelu == 2 ? a.bnstat[2 * a.CO + ch] : 0.f;
-        bsh[j][r] = a.bnrelu == 2 ? a.bnstat[3 * a.CO + ch] : 0.f;
-      }
-    }
-  }
-  float s_sum[TN][4], s_sq[TN][4];
-  if (STATS) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { s_sum[j][r] = 0.f; s_sq[j][r] = 0.f; }
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const long long m = m0 + wm * (BM / WM) + i * 16 + (lane & 15);
+  // tile row ml -> row m of the class grid and output pixel pix
+  auto row_of = [&](int ml, long long& m, long long& pix) {
+    m = m0 + ml;
     const bool mok = m < Mc;
-    long long pix = m;
+    pix = m;
     if (MODE == 1) {
-      const int rloc = mok ? (int)(m - m0) : 0;
+      const int rloc = mok ? ml : 0;
       int q1, j, q2, ii;
       small_divmod(ow0 + rloc, RW, rcpW, q1, j);
       small_divmod(oh0 + q1, RH, rcpH, q2, ii);
       const long long b = b0 + q2;
       pix = (b * a.OH + (long long)ii * st + ph) * a.OW + (long long)j * st + pw;
     }
-    const unsigned rowoff = 2u * (unsigned)(pix * a.CO);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = n0 + wn * (BN / WN) + j * 16 + 4 * (lane >> 4);
-      typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-      const bool ok = mok && nok[j];
-      float ad[4] = {0.f, 0.f, 0.f, 0.f};
-      if (add_in) {
-        const unsigned aoff = a.addend_sub ? 2u * (unsigned)(m * a.CO) : rowoff;
-        masked_addend4(a, rsAdd, rsAm, aoff + 2u * n, ok, n, ad);
-      }
-      float xb[4] = {0.f, 0.f, 0.f, 0.f}, mk[4] = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (BNB) {
-        const u32x2_t xv = __builtin_amdgcn_raw_buffer_load_b64(rsBx, ok ? rowoff + 2u * n : kOOB, 0, 0);
-        xb[0] = bnb_lo(xv.x); xb[1] = bnb_hi(xv.x); xb[2] = bnb_lo(xv.y); xb[3] = bnb_hi(xv.y);
-        if (a.bnrelu == 1) {
-          const u32x2_t mv =
-              __builtin_amdgcn_raw_buffer_load_b64(rsBm, ok ? rowoff + 2u * n : kOOB, 0, 0);
-          mk[0] = bnb_lo(mv.x); mk[1] = bnb_hi(mv.x); mk[2] = bnb_lo(mv.y); mk[3] = bnb_hi(mv.y);
-        } else if (a.bnrelu == 3) {
-          // byte (pixel, n / 8) of the bit mask; bits (n & 4) .. +3 are channels n .. n+3
-          const unsigned bits = __builtin_amdgcn_raw_buffer_load_b8(
-              rsBm, ok ? (rowoff >> 4) + (unsigned)(n >> 3) : kOOB, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mk[r] = (bits >> ((n & 4) + r)) & 1u ? 1.f : 0.f;
-        }
-      }
-      u16 h[4];
-      float v[4], t[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        t[r] = acc[i][j][r] + bj[j][r] + ad[r];
-        if (MODE == 0 && a.relu) t[r] = fmaxf(t[r], 0.f);
-        if constexpr (BNB)
-          t[r] = bnb_on(a.bnrelu, xb[r], mk[r], bsc[j][r], bsh[j][r]) ? t[r] : 0.f;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        h[r] = f2bf(t[r]);
-        v[r] = bf2f(h[r]);   // statistics of the stored (rounded) values
-      }
-      const u32x2_t packed = {(u32)h[0] | ((u32)h[1] << 16), (u32)h[2] | ((u32)h[3] << 16)};
-      __builtin_amdgcn_raw_buffer_store_b64(packed, rsY, ok ? rowoff + 2u * n : kOOB, 0, DMP_CONV_STORE_AUX);
-      if (STATS) {
-        const float keep = ok ? 1.f : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float x = v[r] * keep;
-          s_sum[j][r] += x;
-          if constexpr (BNB) s_sq[j][r] += x * (xb[r] - bmu[j][r]);
-          else s_sq[j][r] += x * x;
-        }
-      }
-    }
-  }
-  if (STATS) {
-    // sum over the 16 rows of each lane group with DPP row shifts (lane 15 of
-    // every 16-lane row ends up with the row total)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s_sum[j][r] = row_sum16(s_sum[j][r]);
-        s_sq[j][r] = row_sum16(s_sq[j][r]);
-      }
-    float* red = reinterpret_cast<float*>(lds);   // [WM][BN] sums, then [WM][BN] squares
-    if ((lane & 15) == 15) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int nl = wn * (BN / WN) + j * 16 + 4 * (lane >> 4) + r;
-          red[wm * BN + nl] = s_sum[j][r];
-          red[WM * BN + wm * BN + nl] = s_sq[j][r];
-        }
-    }
-    __syncthreads();
-    for (int nl = tid; nl < BN; nl += 64 * NW) {
-      const int n = n0 + nl;
-      if (n < a.CO) {
-        float ss = 0.f, qq = 0.f;
-#pragma unroll
-        for (int w = 0; w < WM; ++w) { ss += red[w * BN + nl]; qq += red[WM * BN + w * BN + nl]; }
-        if (BNB) qq *= a.bnstat[a.CO + n];   // sum dz * (x - mean) -> sum dz * xhat
-        const int slot = (blockIdx.x + blockIdx.z * gridDim.x) % kBnSlots;
-        atomicAdd(a.part + (long long)slot * a.CO + n, ss);
-        atomicAdd(a.part + (long long)(kBnSlots + slot) * a.CO + n, qq);
-      }
-    }
-  }
+    return mok;
+  };
+  // (no PLAIN compile-out: a statistics forward here may carry a bias)
+  frag_epilogue<BM, BN, WM, WN, MODE == 0, STATS, false, DMP_CONV_STORE_AUX>(
+      a, acc, n0, wm, wn, tid, lane, lds, add_in, row_of);
 }
 
 // ------------------------------------------------ 3x3 stride-1 halo tiles
@@ -580,166 +468,36 @@ struct HaloGeom {
 
 constexpr int kHaloAPW = 8;   // max halo DMA instructions per wave per stage
 
-// Epilogue of the halo tiles (forward layout: output row m = pixel m): bias
-// (fwd), residual gradient addend (FLIP), BN partial sums (STATS) -- as
-// conv_igemm_kernel.  Wave (wm, wn) holds TM x TN 16x16 D^T fragments; the
-// LDS at lds_h is free (the caller synchronised after its last stage read).
+// Epilogue of the halo tiles (forward layout: output row m = pixel m) through
+// frag_epilogue; the LDS at lds_h is free (the caller synchronised after its
+// last stage read).  The training forward that feeds a BatchNorm (STATS, not
+// FLIP) takes no bias, ReLU or addend (launch_halo routes such a conv
+// elsewhere): compiled out (PLAIN).
 // S2: the stride-2 data gradient's parity class `cls` (conv_dgrad_s2_kernel): row
 // m of the class grid (dY geometry GH x GW) is dX pixel (2i + ph, 2j + pw); a
-// subsampled addend (addend_sub) lands on class 0 only, indexed by m.
+// subsampled addend (addend_sub) lands on class 0 only, indexed by m.  (It
+// scatters every other pixel: default store policy, its half-line writes merge
+// in L2.)
 template <int BM, int BN, int WM, int WN, bool FLIP, bool STATS, int TM, int TN, bool S2 = false>
 __device__ __forceinline__ void halo_epilogue(const ConvArgs& a, f32x4 (&acc)[TM][TN], long long m0,
                                               int n0, int wm, int wn, int tid, int lane,
                                               u16* lds_h, int cls = 0, int mv = BM) {
-  constexpr int NW = WM * WN;
-  typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-  const long long Mtot = (long long)a.B * a.OH * a.OW;
-  const long long Mrows = S2 ? (long long)a.B * a.GH * a.GW : Mtot;
-  const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)a.y, 0, (int)(2LL * Mtot * a.CO), 0x00020000);
-  // the training forward that feeds a BatchNorm (STATS, not FLIP) takes no
-  // bias, ReLU or addend (launch_halo routes such a conv elsewhere): compiled out
   constexpr bool PLAIN = STATS && !FLIP;
+  const long long Mrows = S2 ? (long long)a.B * a.GH * a.GW : (long long)a.B * a.OH * a.OW;
   const bool add_in = !PLAIN && (S2 ? (a.addend != nullptr && (!a.addend_sub || cls == 0))
                                     : (a.addend != nullptr));   // dgrad residual grad / fwd BN-fold residual
-  const __amdgpu_buffer_rsrc_t rsAdd = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(add_in ? a.addend : a.y), 0, (int)(2LL * Mtot * a.CO), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsAm = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(add_in && a.addmask ? (const void*)a.addmask : (const void*)a.y), 0,
-      (int)(Mtot * a.CO / 8), 0x00020000);
-  constexpr bool BNB = FLIP && STATS;   // fused BN(+ReLU) backward
-  const __amdgpu_buffer_rsrc_t rsBx = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(BNB ? a.bnx : a.y), 0, (int)(2LL * Mtot * a.CO), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsBm = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(BNB && (a.bnrelu == 1 || a.bnrelu == 3) ? a.bnmask : a.y), 0,
-      (int)((a.bnrelu == 3 ? 1LL : 16LL) * Mtot * a.CO / 8), 0x00020000);
-  float bj[TN][4];
-  bool nok[TN];
-  // BNB: per-channel mean | scale | shift of the BN (channels n..n+3 of tile j)
-  float bmu[BNB ? TN : 1][4], bsc[BNB ? TN : 1][4], bsh[BNB ? TN : 1][4];
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = n0 + wn * (BN / WN) + j * 16 + 4 * (lane >> 4);
-    nok[j] = n < a.CO;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      bj[j][r] = (!FLIP && !PLAIN && a.bias != nullptr && n + r < a.CO) ? a.bias[n + r] : 0.f;
-      if constexpr (BNB) {
-        const int ch = nok[j] ? n + r : 0;
-        bmu[j][r] = a.bnstat[ch];
-        bsc[j][r] = a.bnrelu == 2 ? a.bnstat[2 * a.CO + ch] : 0.f;
-        bsh[j][r] = a.bnrelu == 2 ? a.bnstat[3 * a.CO + ch] : 0.f;
-      }
-    }
-  }
-  float s_sum[TN][4], s_sq[TN][4];
-  if (STATS) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) { s_sum[j][r] = 0.f; s_sq[j][r] = 0.f; }
-  }
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int ml = wm * (BM / WM) + i * 16 + (lane & 15);
-    const long long m = m0 + ml;
-    const bool mok = ml < mv && m < Mrows;
-    long long pix = m;
+  auto row_of = [&](int ml, long long& m, long long& pix) {
+    m = m0 + ml;
+    pix = m;
     if constexpr (S2) {
       const int mi = (int)m, gi = a.GH * a.GW;
       const int b = mi / gi, rem = mi - b * gi, ii = rem / a.GW, jj = rem - ii * a.GW;
       pix = ((long long)b * a.OH + 2 * ii + (cls >> 1)) * a.OW + 2 * jj + (cls & 1);
     }
-    const unsigned rowoff = 2u * (unsigned)(pix * a.CO);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = n0 + wn * (BN / WN) + j * 16 + 4 * (lane >> 4);
-      const bool ok = mok && nok[j];
-      float ad[4] = {0.f, 0.f, 0.f, 0.f};
-      if (add_in) {
-        const unsigned aoff = a.addend_sub ? 2u * (unsigned)(m * a.CO) : rowoff;
-        masked_addend4(a, rsAdd, rsAm, aoff + 2u * n, ok, n, ad);
-      }
-      float xb[4] = {0.f, 0.f, 0.f, 0.f}, mk[4] = {0.f, 0.f, 0.f, 0.f};
-      if constexpr (BNB) {
-        const u32x2_t xv = __builtin_amdgcn_raw_buffer_load_b64(rsBx, ok ? rowoff + 2u * n : kOOB, 0, 0);
-        xb[0] = bnb_lo(xv.x); xb[1] = bnb_hi(xv.x); xb[2] = bnb_lo(xv.y); xb[3] = bnb_hi(xv.y);
-        if (a.bnrelu == 1) {
-          const u32x2_t mv =
-              __builtin_amdgcn_raw_buffer_load_b64(rsBm, ok ? rowoff + 2u * n : kOOB, 0, 0);
-          mk[0] = bnb_lo(mv.x); mk[1] = bnb_hi(mv.x); mk[2] = bnb_lo(mv.y); mk[3] = bnb_hi(mv.y);
-        } else if (a.bnrelu == 3) {
-          // byte (pixel, n / 8) of the bit mask; bits (n & 4) .. +3 are channels n .. n+3
-          const unsigned bits = __builtin_amdgcn_raw_buffer_load_b8(
-              rsBm, ok ? (rowoff >> 4) + (unsigned)(n >> 3) : kOOB, 0, 0);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) mk[r] = (bits >> ((n & 4) + r)) & 1u ? 1.f : 0.f;
-        }
-      }
-      u16 hv[4];
-      float v[4], t[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        t[r] = PLAIN ? acc[i][j][r] : acc[i][j][r] + bj[j][r] + ad[r];
-        if (!FLIP && !PLAIN && a.relu) t[r] = fmaxf(t[r], 0.f);
-        if constexpr (BNB)
-          t[r] = bnb_on(a.bnrelu, xb[r], mk[r], bsc[j][r], bsh[j][r]) ? t[r] : 0.f;
-      }
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        hv[r] = f2bf(t[r]);
-        v[r] = bf2f(hv[r]);
-      }
-      const u32x2_t packed = {(u32)hv[0] | ((u32)hv[1] << 16), (u32)hv[2] | ((u32)hv[3] << 16)};
-      // (the stride-2 data gradient scatters every other pixel: default policy, its
-      // half-line writes merge in L2)
-      __builtin_amdgcn_raw_buffer_store_b64(packed, rsY, ok ? rowoff + 2u * n : kOOB, 0,
-                                            S2 ? 0 : DMP_HALO_STORE_AUX);
-      if (STATS) {
-        const float keep = ok ? 1.f : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float x = v[r] * keep;
-          s_sum[j][r] += x;
-          if constexpr (BNB) s_sq[j][r] += x * (xb[r] - bmu[j][r]);
-          else s_sq[j][r] += x * x;
-        }
-      }
-    }
-  }
-  if (STATS) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s_sum[j][r] = row_sum16(s_sum[j][r]);
-        s_sq[j][r] = row_sum16(s_sq[j][r]);
-      }
-    float* red = reinterpret_cast<float*>(lds_h);   // [WM][BN] sums, then [WM][BN] squares
-    if ((lane & 15) == 15) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int nl = wn * (BN / WN) + j * 16 + 4 * (lane >> 4) + r;
-          red[wm * BN + nl] = s_sum[j][r];
-          red[WM * BN + wm * BN + nl] = s_sq[j][r];
-        }
-    }
-    __syncthreads();
-    for (int nl = tid; nl < BN; nl += 64 * NW) {
-      const int n = n0 + nl;
-      if (n < a.CO) {
-        float ss = 0.f, qq = 0.f;
-#pragma unroll
-        for (int w = 0; w < WM; ++w) { ss += red[w * BN + nl]; qq += red[WM * BN + w * BN + nl]; }
-        if (BNB) qq *= a.bnstat[a.CO + n];   // sum dz * (x - mean) -> sum dz * xhat
-        const int slot = (blockIdx.x + blockIdx.z * gridDim.x) % kBnSlots;
-        atomicAdd(a.part + (long long)slot * a.CO + n, ss);
-        atomicAdd(a.part + (long long)(kBnSlots + slot) * a.CO + n, qq);
-      }
-    }
-  }
+    return ml < mv && m < Mrows;
+  };
+  frag_epilogue<BM, BN, WM, WN, !FLIP, STATS, PLAIN, S2 ? 0 : DMP_HALO_STORE_AUX>(
+      a, acc, n0, wm, wn, tid, lane, lds_h, add_in, row_of);
 }
 
 #ifndef DMP_HALO_EPI_LDS
@@ -747,7 +505,7 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs& a, f32x4 (&acc)[TM
 #endif
 
 
-// Row-staged variant of halo_epilogue (no S2, no fused BN backward): the D^T
+// Row-staged variant of halo_epilogue (no S2): the D^T
 // fragments (lane: 4 channels of one pixel -> 16 rows x 32-B pieces per store
 // instruction) are staged through the free LDS as a [BM][BN + 8] bf16 block
 // tile, then every wave moves whole 16-B row segments: 8 channels of one pixel
@@ -764,7 +522,6 @@ __device__ __forceinline__ void halo_epilogue_rows(const ConvArgs& a, f32x4 (&ac
                                                    int lane, u16* lds_h, int mv) {
   constexpr int NW = WM * WN, PITCH = BN + 8, CPR = BN / 8, RPI = 64 / CPR;
   static_assert(BN % 8 == 0 && 64 % CPR == 0, "row segments of 8 channels");
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
   const long long Mtot = (long long)a.B * a.OH * a.OW;
   // statistics forward (feeds a BatchNorm): no bias / ReLU / addend, compiled out
   // (launch_cfg sends such a conv with any of them to the plain epilogue)
@@ -970,13 +727,13 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
     for (int j = 0; j < kHaloAPW; ++j) {
       const int ins = wid + j * NW;
       if (ins < hg.A_INS)
-        bdma16(rsA, a_base[j] == kOOB ? kOOB : a_base[j] + cd, As + ins * (RPI * BK));
+        dma16(rsA, a_base[j] == kOOB ? kOOB : a_base[j] + cd, As + ins * (RPI * BK));
     }
 #pragma unroll
     for (int j = 0; j < B_PW; ++j) {
       const int ins = wid + j * NW;
       if (B_INS % NW == 0 || ins < B_INS)
-        bdma16(rsB, b_base[j] == kOOB ? kOOB : b_base[j] + cd, Bs + ins * (RPI * BK));
+        dma16(rsB, b_base[j] == kOOB ? kOOB : b_base[j] + cd, Bs + ins * (RPI * BK));
     }
   };
 
@@ -1091,7 +848,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
   // the data gradient stores through the row-staged epilogue (-5..-9 % on the
   // 128 / 256-channel layers, no change on the forward, whose BN sums cost
   // more in the row layout: profiles/conv_roofline_r4.txt)
-  if constexpr ((DMP_HALO_EPI_LDS || FLIP) && !(FLIP && STATS))
+  if constexpr (DMP_HALO_EPI_LDS || FLIP)
     halo_epilogue_rows<BM, BN, WM, WN, FLIP, STATS, TM, TN>(a, acc, m0, n0, wm, wn, tid, lane, lds_h,
                                                             MV);
   else
@@ -1172,13 +929,13 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_dgrad_s2_kernel(ConvArgs a,
 #pragma unroll
     for (int j = 0; j < kHaloAPW; ++j) {
       const int ins = wid + j * NW;
-      if (ins < hg.A_INS) bdma16(rsA, a_base[j] == kOOB ? kOOB : a_base[j] + cd, As + ins * (RPI * BK));
+      if (ins < hg.A_INS) dma16(rsA, a_base[j] == kOOB ? kOOB : a_base[j] + cd, As + ins * (RPI * BK));
     }
 #pragma unroll
     for (int j = 0; j < B_PW; ++j) {
       const int ins = wid + j * NW;
       if (B_INS % NW == 0 || ins < B_INS)
-        bdma16(rsB, b_base[j] == kOOB ? kOOB : b_base[j] + cd, Bs + ins * (RPI * BK));
+        dma16(rsB, b_base[j] == kOOB ? kOOB : b_base[j] + cd, Bs + ins * (RPI * BK));
     }
   };
 
@@ -1315,21 +1072,6 @@ constexpr int kHpAPW = 12;   // max halo DMA pieces per wave per tile
 // smaller bound frees 8 VGPRs of slot offsets in the register-capped kernel
 constexpr int hp_apw_max(int nw) { return nw == 8 ? 8 : kHpAPW; }
 
-__device__ __forceinline__ void wait_vm_n(int n) {
-  switch (n) {
-#define DMP_WV(k) \
-  case k:         \
-    wait_vm<k>(); \
-    break;
-    DMP_WV(1) DMP_WV(2) DMP_WV(3) DMP_WV(4) DMP_WV(5) DMP_WV(6) DMP_WV(7) DMP_WV(8) DMP_WV(9)
-    DMP_WV(10) DMP_WV(11) DMP_WV(12) DMP_WV(13) DMP_WV(14) DMP_WV(15) DMP_WV(16) DMP_WV(17)
-    DMP_WV(18) DMP_WV(19) DMP_WV(20) DMP_WV(21) DMP_WV(22) DMP_WV(23) DMP_WV(24)
-#undef DMP_WV
-    default:
-      wait_vm<0>();
-  }
-}
-
 template <int BM, int NS, int NW, bool FLIP, bool STATS>
 __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloPGeom hg) {
   constexpr int BK = 64, BN = 64, RPI = 8;
@@ -1369,7 +1111,7 @@ __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloP
     const int row = ins * RPI + lane / 8;
     const int t = row / BN, co = row - t * BN;
     const bool ok = n0 + co < a.CO;
-    bdma16(rsB, ok ? 2u * (unsigned)(((n0 + co) * 9 + t) * C + swz<BK>(row, lane % 8) * 8) : kOOB,
+    dma16(rsB, ok ? 2u * (unsigned)(((n0 + co) * 9 + t) * C + swz<BK>(row, lane % 8) * 8) : kOOB,
            Ws + ins * (RPI * BK));
   }
   // halo DMA slots: staged row -> element offset from the tile's first pixel +
@@ -1403,7 +1145,7 @@ __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloP
         const unsigned inf = x_inf[j];
         const int tb = (int)((inf >> 16) & 0x7fff), dh = (int)((inf >> 8) & 255) - 64;
         const bool ok = live && (inf >> 31) && b0 + tb < a.B && (unsigned)(h0 + dh) < (unsigned)H;
-        bdma16(rsA, ok ? 2u * (unsigned)(m0 * C + x_off[j]) : kOOB, As + (wid + j * NW) * 512);
+        dma16(rsA, ok ? 2u * (unsigned)(m0 * C + x_off[j]) : kOOB, As + (wid + j * NW) * 512);
       }
     }
   };
@@ -1471,7 +1213,6 @@ __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloP
     }
   };
 
-  typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
   // conv bias: forward without BN statistics only (the eval-mode BN fold);
   // the training forward (STATS) feeds a BatchNorm and has none -- the
   // launcher routes a biased STATS conv elsewhere -- which frees 16 VGPRs of
@@ -1493,20 +1234,19 @@ __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloP
   // residual-gradient addend of the data gradient (FLIP): its rows of tile k are
   // loaded (inline asm, counted by hand) BEFORE the next tile's DMA is issued,
   // so the deferred epilogue waits only for them, never for that DMA
-  typedef unsigned int u32x2_a __attribute__((ext_vector_type(2)));
   // (the statistics forward feeds a BatchNorm: no addend / ReLU, compiled out)
   constexpr bool PLAIN = STATS && !FLIP;
   const bool add_in = a.addend != nullptr;   // dgrad residual grad / fwd BN-fold residual
   const __amdgpu_buffer_rsrc_t rsAdd = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(add_in ? a.addend : a.y), 0, (int)(2LL * P * a.CO), 0x00020000);
-  u32x2_a ad[TM][TN];
+  u32x2_t ad[TM][TN];
   // deferred ReLU mask of the addend (ConvArgs::addmask): the 64 bits of the
   // block's 64 channels of pixel m, one dwordx2 per fragment row i
   const bool add_mask = add_in && a.addmask != nullptr;
   const __amdgpu_buffer_rsrc_t rsAm = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(add_mask ? (const void*)a.addmask : (const void*)a.y), 0, (int)((long long)P * a.CO / 8),
       0x00020000);
-  u32x2_a am[TM];
+  u32x2_t am[TM];
   auto aload = [&](int k) {
     const int m0 = tile_of(k) * BM;
 #pragma unroll
@@ -1524,7 +1264,7 @@ __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloP
         asm volatile("buffer_load_dwordx2 %0, %1, %2, 0 offen" : "=v"(am[i]) : "v"(moff), "s"(rsAm)
                      : "memory");
       } else {
-        am[i] = u32x2_a{0xffffffffu, 0xffffffffu};
+        am[i] = u32x2_t{0xffffffffu, 0xffffffffu};
       }
     }
   };
@@ -1573,7 +1313,7 @@ __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloP
   auto addend_wait = [&](bool last) {
     if (add_in) {
       if (last) wait_vm<0>();
-      else wait_vm_n(dma_pw);
+      else wait_vm_n<24>(dma_pw);
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
 #pragma unroll
@@ -1645,7 +1385,7 @@ __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloP
   } else {
     for (int k = 0; k < nt; ++k) {
       if (NS == 2) wait_vm<0>();
-      else wait_vm_n(vm_wait);            // tile k (and, at k = 0, the weights) landed ...
+      else wait_vm_n<24>(vm_wait);            // tile k (and, at k = 0, the weights) landed ...
       if (!FLIP && hg.xform) xform_tile(k);
       __builtin_amdgcn_s_barrier();       // ... for every wave; slot (k-1) % NS is free
       asm volatile("" ::: "memory");
@@ -1669,35 +1409,10 @@ __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloP
     if (DMP_ABLATE != 3) epilogue(nt - 1, true);
   }
   if (STATS) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s_sum[j][r] = row_sum16(s_sum[j][r]);
-        s_sq[j][r] = row_sum16(s_sq[j][r]);
-      }
     wait_vm<0>();                        // the ring's trailing (zero) DMAs have landed
     __syncthreads();
-    float* red = reinterpret_cast<float*>(Hs);   // [NW][BN] sums, then [NW][BN] squares
-    if ((lane & 15) == 15) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int nl = j * 16 + 4 * (lane >> 4) + r;
-          red[wid * BN + nl] = s_sum[j][r];
-          red[NW * BN + wid * BN + nl] = s_sq[j][r];
-        }
-    }
-    __syncthreads();
-    if (tid < BN && n0 + tid < a.CO) {
-      float ss = 0.f, qq = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { ss += red[w * BN + tid]; qq += red[NW * BN + w * BN + tid]; }
-      const int slot = blockIdx.x % kBnSlots;
-      atomicAdd(a.part + (long long)slot * a.CO + n0 + tid, ss);
-      atomicAdd(a.part + (long long)(kBnSlots + slot) * a.CO + n0 + tid, qq);
-    }
+    slot_sum_flush<NW, BN, 64 * NW>(s_sum, s_sq, reinterpret_cast<float*>(Hs), wid, 0, tid, lane,
+                                    a.part, n0, a.CO, blockIdx.x % kBnSlots);
   }
 }
 
@@ -1744,8 +1459,8 @@ __global__ void __launch_bounds__(256) conv_weight_transpose_kernel(
   X(22, 64, 64, 32, 2, 2, 4)     \
   X(23, 128, 128, 32, 2, 2, 4)
 // 24-27: tiles with the row-staged epilogue (conv_igemm_kernel<ROWS>): forward,
-// and stride-1 data gradients without the fused BN backward; otherwise they run
-// the plain epilogue of the same geometry
+// and stride-1 data gradients; otherwise they run the plain epilogue of the same
+// geometry
 #define DMP_CONV_CONFIGS_ROWS(X) \
   X(24, 128, 128, 32, 2, 4, 2)   \
   X(25, 128, 128, 64, 2, 4, 2)   \
@@ -1795,13 +1510,12 @@ template <int BM, int BN, int BK, int WM, int WN, int NS, int MODE, bool STATS, 
 static void launch_cfg(const ConvArgs& a, int classes, hipStream_t s) {
   const dim3 grid((unsigned)((a.M + BM - 1) / BM), (unsigned)((a.CO + BN - 1) / BN),
                   (unsigned)classes);
-  // row-staged epilogue: forward, or a stride-1 data gradient without the fused BN
-  // backward (one parity class, output row = dX pixel); otherwise the plain tile
-  constexpr bool R = ROWS && (MODE == 0 || !STATS);
+  // row-staged epilogue: forward, or a stride-1 data gradient (one parity class,
+  // output row = dX pixel); otherwise the plain tile
   // (the row epilogue of a statistics forward has no bias / ReLU / addend: PLAIN)
   const bool plain_ok = !(MODE == 0 && STATS) || (a.bias == nullptr && !a.relu && a.addend == nullptr);
-  if (R && plain_ok && (MODE == 0 || (a.stride == 1 && !a.addend_sub)))
-    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WM, WN, MODE, STATS, NS, R>), grid,
+  if (ROWS && plain_ok && (MODE == 0 || (a.stride == 1 && !a.addend_sub)))
+    hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WM, WN, MODE, STATS, NS, ROWS>), grid,
                        dim3(64 * WM * WN), 0, s, a);
   else
     hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, BK, WM, WN, MODE, STATS, NS, false>), grid,
@@ -2022,14 +1736,12 @@ static bool launch_halo(const ConvArgs& a, int cfg, hipStream_t s) {
     HaloPGeom pg;
     int bm, ns, nw;
     size_t plds;
-    // the BN-backward epilogue is not fused in the persistent kernel (its
-    // deferred epilogue runs with the next tile's DMA in flight): take the 4-wave
-    // halo tile for those dgrads instead (a residual addend is fused: loaded ahead
-    // of the DMA, see conv_halo64p_kernel)
     // the persistent kernel's statistics forward carries no conv bias (HAS_BIAS)
     // (a statistics forward takes no bias / ReLU / addend in these kernels: PLAIN)
     if (!FLIP && STATS && (a.bias != nullptr || a.relu || a.addend != nullptr)) return false;
-    if (FLIP && (STATS || (a.addend != nullptr && a.addend_sub)))
+    // the persistent kernel's addend is full-resolution only: a subsampled one
+    // takes the 4-wave halo tile instead
+    if (FLIP && a.addend != nullptr && a.addend_sub)
       return launch_halo<FLIP, STATS>(a, kHaloBase + 9, s) ||
              launch_halo<FLIP, STATS>(a, kHaloBase + 5, s);
     if (!halop_geom(cfg, a.B, a.GH, a.GW, a.CI, a.R, a.S, a.stride, a.pad, &pg, &bm, &ns, &nw,
@@ -2050,11 +1762,9 @@ static bool launch_halo(const ConvArgs& a, int cfg, hipStream_t s) {
     pg.xs = 1.f;
     pg.xh = 0.f;
     pg.xlo = -INFINITY;
-    if constexpr (!(FLIP && STATS)) {
-      if (nw == 8) launch_halop_t<256, 2, 8, FLIP, STATS>(a, pg, plds, s);
-      else if (bm == 256) launch_halop_t<256, 2, 4, FLIP, STATS>(a, pg, plds, s);
-      else launch_halop_t<128, 3, 4, FLIP, STATS>(a, pg, plds, s);
-    }
+    if (nw == 8) launch_halop_t<256, 2, 8, FLIP, STATS>(a, pg, plds, s);
+    else if (bm == 256) launch_halop_t<256, 2, 4, FLIP, STATS>(a, pg, plds, s);
+    else launch_halop_t<128, 3, 4, FLIP, STATS>(a, pg, plds, s);
     return true;
   }
   if (!halo_geom(cfg, a.GH, a.GW, a.CI, a.R, a.S, a.stride, a.pad, &g, &lds)) return false;
@@ -2176,24 +1886,17 @@ void launch_conv_fwd(const u16* x, const u16* w, u16* y, float* part, int B, int
 // dX (B,H,W,CI) from dY (B,OH,OW,CO) and Wt [CI][R][S][CO]; stride*stride parity classes.
 void launch_conv_dgrad(const u16* dy, const u16* wt, u16* dx, int B, int H, int W, int CI,
                        int OH, int OW, int CO, int R, int S, int stride, int pad, int cfg,
-                       hipStream_t s, const u16* addend, const BnBwdFuse* bnf,
-                       bool addend_sub, const uint8_t* addend_mask) {
+                       hipStream_t s, const u16* addend, bool addend_sub,
+                       const uint8_t* addend_mask) {
   const long long rows = (long long)B * ((H + stride - 1) / stride) * ((W + stride - 1) / stride);
   ConvArgs a{dy, wt, dx, nullptr, B, OH, OW, CO, H, W, CI, R, S, stride, pad, rows, nullptr,
              addend};
   a.addend_sub = addend_sub ? 1 : 0;
   a.addmask = addend ? addend_mask : nullptr;
-  if (bnf) {
-    a.part = bnf->part;
-    a.bnx = bnf->x;
-    a.bnmask = bnf->mask;
-    a.bnstat = bnf->stats;
-    a.bnrelu = bnf->relu;
-  }
   if (cfg >= kS2Base && cfg < kS2Base + kNumS2Configs) {
     HaloGeom g;
     size_t lds;
-    if (!bnf && s2_geom(cfg, H, W, OH, OW, CO, CI, R, S, stride, pad, &g, &lds)) {
+    if (s2_geom(cfg, H, W, OH, OW, CO, CI, R, S, stride, pad, &g, &lds)) {
       switch (cfg - kS2Base) {
 #define X(i, BM, BN, WM, WN, NS) \
   case i: launch_s2_t<BM, BN, WM, WN, NS>(a, g, lds, s); return;
@@ -2205,12 +1908,11 @@ void launch_conv_dgrad(const u16* dy, const u16* wt, u16* dx, int B, int H, int 
   }
   if (cfg >= kHaloBase) {
     // stride 1, 3x3, pad 1: dX = the same conv over dY with Wt and mirrored taps
-    if (bnf ? launch_halo<true, true>(a, cfg, s) : launch_halo<true, false>(a, cfg, s)) return;
+    if (launch_halo<true, false>(a, cfg, s)) return;
     cfg = -1;
   }
   if (cfg < 0 || cfg >= kNumConvConfigs) cfg = conv_default_config(rows * stride * stride, CI);
-  if (bnf) dispatch<1, true>(a, cfg, stride * stride, s);
-  else dispatch<1, false>(a, cfg, stride * stride, s);
+  dispatch<1, false>(a, cfg, stride * stride, s);
 }
 
 // x_sub[b][i][j][c] = x[b][2i][2j][c] (NHWC bf16, C % 8 == 0): the input of a

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "mfma_prims.h"
 
 namespace dmp {
 
@@ -427,19 +428,11 @@ void launch_conv_small_wgrad(const u16* dy, const u16* x, int xbytes, int sb, in
 //   lanes (xor shuffles) and the 4 waves (LDS) into slot blockIdx % kBnSlots.
 // wgrad: D[co][k] = dY^T[co][px] X[px][k] over 32-pixel k-steps.  dY[32 px][64]
 //   is staged row-major into a [32][128] LDS image (chunk-swizzled like the GEMM's
-//   transposed operands, gemm.hip toff) and read with ds_read_b64_tr_b16, which
+//   transposed operands, mfma_prims.h toff) and read with ds_read_b64_tr_b16, which
 //   hands a lane 8 consecutive pixels of one channel; X fragments (8 consecutive
 //   pixels of one tap: one image row when W % 8 == 0) are gathered from L2.  Each
 //   wave owns a 32-pixel slice of a 128-pixel step, 8 MFMAs; the 4 waves' 64 x 32
 //   tiles are summed in LDS and flushed with one fp32 atomic per weight per block.
-typedef __bf16 bf16x8_t_ __attribute__((ext_vector_type(8)));
-typedef short s16x4_t_ __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ f32x4 s3_mfma(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t_, a),
-                                                 __builtin_bit_cast(bf16x8_t_, b), c, 0, 0, 0);
-}
-
 struct Stem3Args {
   const u16* x;
   const u16* w;     // [64][3][3][CI] bf16
@@ -514,7 +507,7 @@ __global__ void __launch_bounds__(256) stem3_fwd_kernel(Stem3Args a) {
     if (gi + 1 < a.groups) gather(gi + 1, xnext);
     f32x4 acc[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = s3_mfma(wf[j], xf, f32x4{0.f, 0.f, 0.f, 0.f});
+    for (int j = 0; j < 4; ++j) acc[j] = mfma16(wf[j], xf, f32x4{0.f, 0.f, 0.f, 0.f});
     // D: lane holds channels 16j + 4kg + r of pixel `col`... of THIS group's pixel px
     // (D row = co, D col = pixel: lane = (row block kg, col))
     // the D fragments (8 B per lane: 16 pixels x 32 B per store instruction) go
@@ -570,13 +563,7 @@ __global__ void __launch_bounds__(256) stem3_fwd_kernel(Stem3Args a) {
   }
 }
 
-// [32][128] bf16 transposed-read image: 32-B granule u of row r holds logical
-// granule u ^ tf(r) (gemm.hip toff<128>)
-__device__ __forceinline__ int s3_tf(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-__device__ __forceinline__ int s3_toff(int row, int col) {
-  return row * 128 + (((col >> 4) ^ s3_tf(row)) << 4) + (col & 15);
-}
-
+// (dY stages as a [32][128] bf16 transposed-read image: toff<128>, mfma_prims.h)
 __global__ void __launch_bounds__(256) stem3_wgrad_kernel(Stem3Args a) {
   __shared__ __attribute__((aligned(16))) u16 img[4][32 * 128];
   __shared__ float tile[64][33];
@@ -647,7 +634,7 @@ __global__ void __launch_bounds__(256) stem3_wgrad_kernel(Stem3Args a) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int e = u * 64 + lane;
-      *reinterpret_cast<bf16x8*>(im + s3_toff(e >> 3, (e & 7) * 8)) = dcur[u];   // 8 cols stay in one granule
+      *reinterpret_cast<bf16x8*>(im + toff<128>(e >> 3, (e & 7) * 8)) = dcur[u];   // 8 cols stay in one granule
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's LDS image writes landed
     __builtin_amdgcn_wave_barrier();
@@ -657,13 +644,13 @@ __global__ void __launch_bounds__(256) stem3_wgrad_kernel(Stem3Args a) {
     for (int j = 0; j < 4; ++j) {
       const int g = lane >> 4, li = lane & 15, qq = li >> 2, pp = li & 3;
       const int row = 8 * g + qq;
-      const s16x4_t_ lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) s16x4_t_*)(im + s3_toff(row, 16 * j + 4 * pp)));
-      const s16x4_t_ hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-          (__attribute__((address_space(3))) s16x4_t_*)(im + s3_toff(row + 4, 16 * j + 4 * pp)));
+      const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) s16x4_t*)(im + toff<128>(row, 16 * j + 4 * pp)));
+      const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+          (__attribute__((address_space(3))) s16x4_t*)(im + toff<128>(row + 4, 16 * j + 4 * pp)));
       const bf16x8 af = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-      acc[j][0] = s3_mfma(af, xf[0], acc[j][0]);
-      acc[j][1] = s3_mfma(af, xf[1], acc[j][1]);
+      acc[j][0] = mfma16(af, xf[0], acc[j][0]);
+      acc[j][1] = mfma16(af, xf[1], acc[j][1]);
     }
     __builtin_amdgcn_wave_barrier();
   }

@@ -23,15 +23,13 @@
 //   NS   - pipeline depth: NS-1 stages of DMA in flight, retired with a
 //          counted s_waitcnt vmcnt(N) before one raw s_barrier per stage.
 #include "common.h"
+#include "mfma_prims.h"
 
 #ifndef DMP_ABLATE
 #define DMP_ABLATE 0   // roofline ablations: see conv.hip
 #endif
 
 namespace dmp {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
 
 struct WgradArgs {
@@ -45,34 +43,6 @@ struct WgradArgs {
   float* slab;      // halo wgrad, slab mode: per-split partials [splits][CO][R][S][CI]
   int xcd;          // gather wgrad: XCD-aware deal of the blocks (cfg bit 512)
 };
-
-__device__ __forceinline__ f32x4 mfma16w(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                 __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-// LDS DMA (buffer_load_dwordx4 ... lds) issued from inline asm on purpose: the
-// compiler models the builtin as an LDS store it cannot disambiguate from the
-// ring buffer being read, and inserts s_waitcnt vmcnt(0) in front of the very
-// next ds_read -- serialising every stage's DMA with the MFMA work.
-// Completion is tracked by hand (wait_vm below).  32-bit byte offsets into a
-// buffer descriptor; offsets past its bound read zeros (padding taps, rows
-// past the end of P).
-constexpr unsigned kOOBw = 0x80000000u;
-__device__ __forceinline__ void bdma16w(__amdgpu_buffer_rsrc_t rs, unsigned voff,
-                                        u16* lds_wave_base) {
-  const unsigned m0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)lds_wave_base;
-  asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs),
-               "{m0}"(m0));
-}
-
-// wait until at most N vector-memory ops (our DMAs) of this wave are outstanding,
-// and for all of this wave's LDS ops (row-table writes) to complete
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0070);
-}
 
 // 32-B granule swizzle (an involution) for [p][ROWE] bf16 images read by
 // ds_read_b64_tr_b16.  A transposed read of one half-wave touches rows
@@ -194,7 +164,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradArgs a) {
     for (int j = 0; j < A_PW; ++j) {
       const int p = pb + a_row[j];
       const bool ok = stg < nsteps && p < (int)p_end;
-      bdma16w(rsA, ok ? 2u * (unsigned)(p * a.CO + a_col[j]) : kOOBw, As + (wid + j * NW) * 512);
+      dma16(rsA, ok ? 2u * (unsigned)(p * a.CO + a_col[j]) : kOOB, As + (wid + j * NW) * 512);
     }
     const int4* tb = rowtab + buf * BP;
 #pragma unroll
@@ -202,7 +172,7 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradArgs a) {
       const int4 e = tb[b_row[j]];
       const int ih = e.y + b_r[j], iw = e.z + b_s[j];
       const bool ok = e.w && (unsigned)ih < (unsigned)GH && (unsigned)iw < (unsigned)GW;
-      bdma16w(rsB, ok ? 2u * (unsigned)((e.x + ih * GW + iw) * CI + b_ci[j]) : kOOBw,
+      dma16(rsB, ok ? 2u * (unsigned)((e.x + ih * GW + iw) * CI + b_ci[j]) : kOOB,
               Bs + (wid + j * NW) * 512);
     }
   };
@@ -255,10 +225,10 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradArgs a) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = mfma16w(af[i], bf[j], acc[i][j]);
+        for (int j = 0; j < TN; ++j) acc[i][j] = mfma16(af[i], bf[j], acc[i][j]);
       if (do_bias) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) accb[i] = mfma16w(af[i], ones, accb[i]);
+        for (int i = 0; i < TM; ++i) accb[i] = mfma16(af[i], ones, accb[i]);
       }
     }
   };
@@ -332,24 +302,6 @@ struct WgradHaloGeom {
 
 constexpr int kWhXPW = 12;   // max X-row DMA instructions per wave per stage
 
-// vmcnt wait with a launch-time (wave-uniform) count
-__device__ __forceinline__ void wait_vm_rt(int n) {
-  switch (n) {
-#define DMP_WV(k) \
-  case k:         \
-    wait_vm<k>(); \
-    break;
-    DMP_WV(1) DMP_WV(2) DMP_WV(3) DMP_WV(4) DMP_WV(5) DMP_WV(6) DMP_WV(7) DMP_WV(8) DMP_WV(9)
-    DMP_WV(10) DMP_WV(11) DMP_WV(12) DMP_WV(13) DMP_WV(14) DMP_WV(15) DMP_WV(16) DMP_WV(17)
-    DMP_WV(18) DMP_WV(19) DMP_WV(20) DMP_WV(21) DMP_WV(22) DMP_WV(23) DMP_WV(24) DMP_WV(25)
-    DMP_WV(26) DMP_WV(27) DMP_WV(28) DMP_WV(29) DMP_WV(30) DMP_WV(31) DMP_WV(32) DMP_WV(33)
-    DMP_WV(34) DMP_WV(35) DMP_WV(36) DMP_WV(37) DMP_WV(38) DMP_WV(39) DMP_WV(40)
-#undef DMP_WV
-    default:
-      wait_vm<0>();
-  }
-}
-
 // PG = 2: 8 waves in two pixel groups.  Group g (waves 4g..4g+3) owns the
 // same 64 x 16-column slices as the 4-wave block but only pk steps
 // [g * NPK / 2, (g+1) * NPK / 2) of every tile; at the end group 1 parks its
@@ -401,10 +353,10 @@ __global__ void __launch_bounds__(256 * PG) conv_wgrad_halo_kernel(WgradArgs a, 
   // dY: row of the tile + swizzled source column.  X: staged row -> (image in
   // tile tb, source row dh relative to the tile's first row h0, column w); a
   // row that is outside the image for every tile (column halo, rows past the
-  // staged image, and with whole-image tiles the row halo) holds kOOBw, and
+  // staged image, and with whole-image tiles the row halo) holds kOOB, and
   // the halo row above the tile wraps below 0 (correct modulo 2^32 once the
   // tile's base offset is added).  Interior tiles then issue every piece with
-  // ONE v_add (kOOBw + base stays >= 2^31, past the descriptor's bound); only
+  // ONE v_add (kOOB + base stays >= 2^31, past the descriptor's bound); only
   // tiles touching an image edge or the end of P test rows per lane.  (Per-tile
   // integer divisions and the per-piece decode/compare chain were ~2/3 of the
   // kernel's VALU: 4.1 VALU per MFMA, issue-bound, profiles/conv_kernels_r2.txt.)
@@ -416,14 +368,14 @@ __global__ void __launch_bounds__(256 * PG) conv_wgrad_halo_kernel(WgradArgs a, 
     d_row[j] = row;
     d_rel[j] = row < MV ? 2u * (unsigned)(row * CO + co0 + (((pch >> 1) ^ wg_f<CW>(row)) * 16) +
                                           (pch & 1) * 8)
-                        : kOOBw;   // padded tile: zeros
+                        : kOOB;   // padded tile: zeros
   }
   const bool whole_img = TH == OHd;   // tiles of whole images: h0 == 0 for every tile
   unsigned x_rel[kWhXPW];
   int x_dh[kWhXPW], x_tb[kWhXPW];
 #pragma unroll
   for (int j = 0; j < kWhXPW; ++j) {
-    x_rel[j] = kOOBw;
+    x_rel[j] = kOOB;
     x_dh[j] = 0;
     x_tb[j] = 0;
     if (j < XPW) {
@@ -475,22 +427,22 @@ __global__ void __launch_bounds__(256 * PG) conv_wgrad_halo_kernel(WgradArgs a, 
                           (whole_img || (hx0 + lo_dh >= 0 && hx0 + hi_dh < H));
     if (interior) {
 #pragma unroll
-      for (int j = 0; j < D_PW; ++j) bdma16w(rsD, d_rel[j] + dbase, Ds + (wid + j * NW) * 512);
+      for (int j = 0; j < D_PW; ++j) dma16(rsD, d_rel[j] + dbase, Ds + (wid + j * NW) * 512);
 #pragma unroll
       for (int j = 0; j < kWhXPW; ++j)
-        if (j < XPW) bdma16w(rsX, x_rel[j] + xbase, Xs + (wid + j * NW) * 512);
+        if (j < XPW) dma16(rsX, x_rel[j] + xbase, Xs + (wid + j * NW) * 512);
     } else {
 #pragma unroll
       for (int j = 0; j < D_PW; ++j) {
         const bool ok = live && m0 + d_row[j] < P;
-        bdma16w(rsD, ok ? d_rel[j] + dbase : kOOBw, Ds + (wid + j * NW) * 512);
+        dma16(rsD, ok ? d_rel[j] + dbase : kOOB, Ds + (wid + j * NW) * 512);
       }
 #pragma unroll
       for (int j = 0; j < kWhXPW; ++j) {
         if (j < XPW) {
-          const bool ok = live && x_rel[j] != kOOBw && b0 + x_tb[j] < a.B &&
+          const bool ok = live && x_rel[j] != kOOB && b0 + x_tb[j] < a.B &&
                           (whole_img || (unsigned)(hx0 + x_dh[j]) < (unsigned)H);
-          bdma16w(rsX, ok ? x_rel[j] + xbase : kOOBw, Xs + (wid + j * NW) * 512);
+          dma16(rsX, ok ? x_rel[j] + xbase : kOOB, Xs + (wid + j * NW) * 512);
         }
       }
     }
@@ -573,7 +525,7 @@ __global__ void __launch_bounds__(256 * PG) conv_wgrad_halo_kernel(WgradArgs a, 
 #pragma unroll
       for (int t = 0; t < 3 * TR; ++t)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[t][i] = mfma16w(af[pk & 1][i], bx[pk & 1][t], acc[t][i]);
+        for (int i = 0; i < 4; ++i) acc[t][i] = mfma16(af[pk & 1][i], bx[pk & 1][t], acc[t][i]);
       if (pk + 1 < NPK) {
         // one read of step pk+1 after each MFMA of step pk, the rest at the end
 #pragma unroll
@@ -594,7 +546,7 @@ __global__ void __launch_bounds__(256 * PG) conv_wgrad_halo_kernel(WgradArgs a, 
   for (int s = 0; s < NS - 1; ++s) stage(s, t_begin + s);
   for (int it = 0; it < nt; ++it) {
     if (NS == 2) wait_vm<0>();
-    else wait_vm_rt(vm_wait);           // tile `it` landed (this wave's DMAs) ...
+    else wait_vm_n<40>(vm_wait);           // tile `it` landed (this wave's DMAs) ...
     __builtin_amdgcn_s_barrier();       // ... for every wave; slot (it-1) % NS is free
     asm volatile("" ::: "memory");
     if (DMP_ABLATE != 2) stage((it + NS - 1) % NS, t_begin + it + NS - 1);

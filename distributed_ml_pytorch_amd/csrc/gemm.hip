@@ -30,6 +30,7 @@
 // land on the same XCD (shared L2) under round-robin dispatch -- a speed
 // choice only, any placement is correct.
 #include "common.h"
+#include "mfma_prims.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -37,13 +38,6 @@
 
 namespace dmp {
 namespace {
-
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kOOBg = 0x80000000u;
 
 // EPI_DRELU (data gradient): out = aux > 0 ? acc : 0 with aux = the layer's own
 // forward INPUT -- the output of a ReLU (or of a dropout after one), so the
@@ -114,27 +108,6 @@ __device__ unsigned long long g_gemm_stamps[1 << 16][4];
 #define DMP_STAMP(i) do {} while (0)
 #endif
 
-__device__ __forceinline__ f32x4 mfma_bf16(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                 __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-// LDS DMA from inline asm (the builtin makes hipcc wait vmcnt(0) before the
-// next ds_read of ANY ring slot, serialising the pipeline); completion counted
-// by hand with wait_vm.
-__device__ __forceinline__ void gdma16(__amdgpu_buffer_rsrc_t rs, unsigned voff,
-                                       u16* lds_wave_base) {
-  const unsigned m0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)lds_wave_base;
-  asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs),
-               "{m0}"(m0));
-}
-
-template <int N>
-__device__ __forceinline__ void gwait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0070);
-}
-
 // [rows][BK] image, 16-B chunk c of row r holds logical chunk rswz(r, c) (an
 // involution): each ds_read_b128 lane group (16 rows, one chunk) hits 16
 // distinct slots.  BK = 64 (128-B rows, 2 per bank row): c ^= (r>>1)&7;
@@ -146,21 +119,11 @@ __device__ __forceinline__ int rswz(int row, int c) {
   else return c ^ ((-(row >> 2)) & 3);
 }
 
-// [64][R] image (R >= 128 bf16 = whole bank rows): 32-B granule u of row r
-// holds logical granule u ^ tf(r).  One half-wave tr read touches rows
-// {8g + q : g = 0,1, q = 0..3} of one granule column; tf gives those 8 rows
-// 8 distinct granules of the 256-B bank row -> conflict-free.
-__device__ __forceinline__ int tf(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-template <int R>
-__device__ __forceinline__ int toff(int row, int col) {
-  return row * R + (((col >> 4) ^ tf(row)) << 4) + (col & 15);
-}
-
 // One operand's per-lane DMA slots: PW 1-KiB wave-instructions per k-tile
 // (waves wid < INS % NW issue one more when NW does not divide INS).  The
 // per-lane byte offsets are computed once per block (recomputing them per
 // stage cost ~12 VALU per DMA and measured 15-25 % slower on the wgrad tiles).
-// 32-bit offsets; out-of-range pieces read zeros (kOOBg).
+// 32-bit offsets; out-of-range pieces read zeros (kOOB).
 template <int R, bool T, int NW, int BK>
 struct Stager {
   static constexpr int EL = R * BK;
@@ -169,7 +132,7 @@ struct Stager {
   static constexpr int PW_MIN = INS / NW;
   static_assert(EL % 512 == 0, "whole 1-KiB DMA pieces");
   static_assert(!T || R % 128 == 0, "transposed image rows must be whole 256-B bank rows");
-  unsigned off[PW];   // byte offset of the piece at k = kbase (kOOBg: row/col out of range)
+  unsigned off[PW];   // byte offset of the piece at k = kbase (kOOB: row/col out of range)
   int kk[PW];         // k of the piece relative to the k-tile start
 
   // r0: tile origin along the operand's rows
@@ -181,12 +144,12 @@ struct Stager {
         const int row = e / BK;
         const int kc = rswz<BK>(row, (e % BK) / 8) * 8;
         kk[j] = kc;
-        off[j] = r0 + row < rows ? 2u * (unsigned)((r0 + row) * ld + kbase + kc) : kOOBg;
+        off[j] = r0 + row < rows ? 2u * (unsigned)((r0 + row) * ld + kbase + kc) : kOOB;
       } else {
         const int row = e / R, pch = (e % R) / 8;
         const int col = (((pch >> 1) ^ tf(row)) << 4) + (pch & 1) * 8;
         kk[j] = row;
-        off[j] = r0 + col < rows ? 2u * (unsigned)((kbase + row) * ld + r0 + col) : kOOBg;
+        off[j] = r0 + col < rows ? 2u * (unsigned)((kbase + row) * ld + r0 + col) : kOOB;
       }
     }
   }
@@ -197,8 +160,8 @@ struct Stager {
 #pragma unroll
     for (int j = 0; j < PW; ++j) {
       if (j < PW_MIN || wid + j * NW < INS) {
-        const bool ok = off[j] != kOOBg && k0 + kk[j] < kend;
-        gdma16(rs, ok ? off[j] + delta : kOOBg, img + (wid + j * NW) * 512);
+        const bool ok = off[j] != kOOB && k0 + kk[j] < kend;
+        dma16(rs, ok ? off[j] + delta : kOOB, img + (wid + j * NW) * 512);
       }
     }
   }
@@ -342,11 +305,11 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          acc[i][j] = TRANS_OUT ? mfma_bf16(bf[j], af[i], acc[i][j])
-                                : mfma_bf16(af[i], bf[j], acc[i][j]);
+          acc[i][j] = TRANS_OUT ? mfma16(bf[j], af[i], acc[i][j])
+                                : mfma16(af[i], bf[j], acc[i][j]);
       if (EPI == EPI_ACC32 && do_bias) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) accb[i] = mfma_bf16(af[i], ones, accb[i]);
+        for (int i = 0; i < TM; ++i) accb[i] = mfma16(af[i], ones, accb[i]);
       }
     }
   };
@@ -453,7 +416,7 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
       for (int q = 0; q < NR; ++q) {
         const int row = q * RPI + lrow, m = m0 + ra + row;
         o[q] = (lane_on && row < WROWS && m < g.M && n < g.N) ? 2u * (unsigned)(m * g.ldc + n)
-                                                              : kOOBg;
+                                                              : kOOB;
       }
       // the aux row segments (GELU' pre-activation / addend) are fetched first,
       // so their latency overlaps the LDS staging below
@@ -472,7 +435,7 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
             amask ? (void*)g.auxmask : g.c, 0, cbytes / 16, 0x00020000);
 #pragma unroll
         for (int q = 0; q < NR; ++q)
-          mb[q] = amask ? __builtin_amdgcn_raw_buffer_load_b8(rsM, o[q] != kOOBg ? o[q] >> 4 : kOOBg,
+          mb[q] = amask ? __builtin_amdgcn_raw_buffer_load_b8(rsM, o[q] != kOOB ? o[q] >> 4 : kOOB,
                                                              0, 0)
                         : 0xffu;
       }
@@ -502,7 +465,7 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
 #pragma unroll
             for (int e = 0; e < 8; ++e)
               xv.v[e] = n + e < g.N ? (u16)__builtin_amdgcn_raw_buffer_load_b16(
-                                          rsX, o[q] == kOOBg ? kOOBg : o[q] + 2u * e, 0, 0)
+                                          rsX, o[q] == kOOB ? kOOB : o[q] + 2u * e, 0, 0)
                                     : (u16)0;
           }
         }
@@ -525,7 +488,7 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
             out.v[e] = f2bf(a * d);
           }
         }
-        if (stats && o[q] != kOOBg) {
+        if (stats && o[q] != kOOB) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const float yv = bf2f(out.v[e]);
@@ -539,7 +502,7 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
           if constexpr (EPI == EPI_GELU)
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, out2), rsC2, o[q],
                                                    0, DMP_GEMM_STORE_AUX);
-        } else if (o[q] != kOOBg) {
+        } else if (o[q] != kOOB) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             if (n + e < g.N) {
@@ -584,7 +547,7 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
     const bool late = wm == 1;
 #pragma unroll
     for (int s = 0; s < 3; ++s) stage(s, s);        // k-tiles past KT load zeros
-    gwait_vm<2 * PWK>();                            // k-tile 0 landed (this wave)
+    wait_vm<2 * PWK>();                            // k-tile 0 landed (this wave)
     __builtin_amdgcn_s_barrier();
     DMP_STAMP(1);
     if (late) __builtin_amdgcn_s_barrier();
@@ -598,7 +561,7 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
 #pragma unroll
       for (int j = 0; j < TN; ++j) bf[j] = frag<BN, BT, BK>(Bs, rb + j * 16, 0, lane);
       stage((kt + 3) & 3, kt + 3);
-      gwait_vm<2 * PWK>();                          // k-tile kt+1 landed; fragments read
+      wait_vm<2 * PWK>();                          // k-tile kt+1 landed; fragments read
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
@@ -607,11 +570,11 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          acc[i][j] = TRANS_OUT ? mfma_bf16(bf[j], af[i], acc[i][j])
-                                : mfma_bf16(af[i], bf[j], acc[i][j]);
+          acc[i][j] = TRANS_OUT ? mfma16(bf[j], af[i], acc[i][j])
+                                : mfma16(af[i], bf[j], acc[i][j]);
       if (EPI == EPI_ACC32 && do_bias) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) accb[i] = mfma_bf16(af[i], ones, accb[i]);
+        for (int i = 0; i < TM; ++i) accb[i] = mfma16(af[i], ones, accb[i]);
       }
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
@@ -619,15 +582,15 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
       __builtin_amdgcn_sched_barrier(0);
     }
     if (!late) __builtin_amdgcn_s_barrier();
-    gwait_vm<0>();
+    wait_vm<0>();
   } else {
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s)
     if (s < KT) stage(s, s);
   for (int kt = 0; kt < KT; ++kt) {
     // k-tile kt landed for this wave (younger ones may still fly) ...
-    if (kt + NS - 2 < KT) gwait_vm<(NS - 2) * INS_MIN>();
-    else gwait_vm<0>();
+    if (kt + NS - 2 < KT) wait_vm<(NS - 2) * INS_MIN>();
+    else wait_vm<0>();
     // ... and for every wave; everyone is done reading slot (kt-1) % NS
     __builtin_amdgcn_s_barrier();
     if (kt == 0) DMP_STAMP(1);
@@ -639,7 +602,7 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
   DMP_STAMP(2);
   if constexpr (KG == 2) {
     // group 1 parks its partial sums in the drained ring, group 0 adds them
-    gwait_vm<0>();
+    wait_vm<0>();
     __syncthreads();
     float* park = reinterpret_cast<float*>(lds);   // [NWG][TM*TN (+TM)][64 lanes] f32x4
     constexpr int PT = TM * TN + TM;

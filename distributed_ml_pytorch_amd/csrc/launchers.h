@@ -51,9 +51,6 @@ void launch_bn_fwd(const uint16_t* x, const uint16_t* res, uint16_t* y, const fl
                    const float* beta, float* running_mean, float* running_var, float* stats,
                    float* part, long long M, int C, float momentum, float eps, bool training,
                    bool relu, hipStream_t s, uint8_t* mask = nullptr);
-void launch_bn_bwd_from_partials(const uint16_t* x, const uint16_t* dz, const float* gamma,
-                                 const float* stats, float* dgamma, float* dbeta, float* coef,
-                                 float* part, uint16_t* dx, long long M, int C, hipStream_t s);
 // finalize folded into the apply passes (zero_buf: the other direction's slots)
 void launch_bn_fwd_fold(const uint16_t* x, const uint16_t* res, uint16_t* y, const float* gamma,
                         const float* beta, float* running_mean, float* running_var, float* stats,
@@ -164,22 +161,9 @@ void launch_conv_fwd(const uint16_t* x, const uint16_t* w, uint16_t* y, float* p
                      int W, int CI, int OH, int OW, int CO, int R, int S, int stride, int pad,
                      int cfg, hipStream_t s, const float* bias = nullptr, bool relu = false,
                      const uint16_t* addend = nullptr);
-// Backward of the BatchNorm(+ReLU) that produced a conv's input, fused into the
-// conv's data-gradient epilogue (conv.hip bnb_*): the dgrad stores dz and adds
-// sum(dz), sum(dz * xhat) per channel into the BN's backward slot buffer.
-struct BnBwdFuse {
-  const uint16_t* x;     // BN input [B][H][W][C]
-  const uint16_t* mask;  // relu 1: stored BN(+residual)+ReLU output (the conv input);
-                         // relu 3: the BN's 1-bit ReLU mask (bytes)
-  const float* stats;    // [4][C] mean | invstd | scale | shift
-  float* part;           // [2][kBnSlots][C] (+tail) slot sums, zeroed
-  int relu;              // 0 none, 1 / 3 mask from `mask`, 2 mask from x and scale/shift
-};
-
 void launch_conv_dgrad(const uint16_t* dy, const uint16_t* wt, uint16_t* dx, int B, int H, int W,
                        int CI, int OH, int OW, int CO, int R, int S, int stride, int pad, int cfg,
-                       hipStream_t s, const uint16_t* addend = nullptr,
-                       const BnBwdFuse* bnf = nullptr, bool addend_sub = false,
+                       hipStream_t s, const uint16_t* addend = nullptr, bool addend_sub = false,
                        const uint8_t* addend_mask = nullptr);
 // x_sub = x[:, ::2, ::2, :] (NHWC bf16, C % 8 == 0), [B][ceil(H/2)][ceil(W/2)][C]
 void launch_subsample2(const uint16_t* x, uint16_t* xs, int B, int H, int W, int C,

@@ -24,61 +24,13 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "mfma_prims.h"
 
 namespace dmp {
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-
-constexpr unsigned kOOBs = 0x80000000u;
 constexpr int kSCO = 64, kSK = 256;   // output channels, packed reduction length
 constexpr int kSAPW = 8;              // max halo DMA pieces per wave per tile
-
-__device__ __forceinline__ f32x4 smfma(const bf16x8& a, const bf16x8& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a),
-                                                 __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
-}
-
-// LDS DMA from inline asm, completion counted by hand (see conv.hip)
-__device__ __forceinline__ void sdma16(__amdgpu_buffer_rsrc_t rs, unsigned voff,
-                                       u16* lds_wave_base) {
-  const unsigned m0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)lds_wave_base;
-  asm volatile("s_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs),
-               "{m0}"(m0));
-}
-
-template <int N>
-__device__ __forceinline__ void swait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0070);
-}
-
-// vmcnt wait with a launch-time (wave-uniform) count
-__device__ __forceinline__ void swait_vm_n(int n) {
-  switch (n) {
-#define DMP_SWV(k) \
-  case k:          \
-    swait_vm<k>(); \
-    break;
-    DMP_SWV(1) DMP_SWV(2) DMP_SWV(3) DMP_SWV(4) DMP_SWV(5) DMP_SWV(6) DMP_SWV(7) DMP_SWV(8)
-    DMP_SWV(9) DMP_SWV(10) DMP_SWV(11) DMP_SWV(12) DMP_SWV(13) DMP_SWV(14) DMP_SWV(15) DMP_SWV(16)
-    DMP_SWV(17) DMP_SWV(18) DMP_SWV(19) DMP_SWV(20) DMP_SWV(21) DMP_SWV(22) DMP_SWV(23) DMP_SWV(24)
-#undef DMP_SWV
-    default:
-      swait_vm<0>();
-  }
-}
-
-__device__ __forceinline__ float srow_sum16(float v) {
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x112, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x114, 0xf, 0xf, true));
-  v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true));
-  return v;
-}
 
 // 32-B granule swizzle of the [pixel][64] dY rows read transposed (as the
 // weight-gradient kernels of conv_wgrad.hip)
@@ -181,7 +133,7 @@ __global__ void __launch_bounds__(256) stem_fwd_kernel(const u16* __restrict__ x
     const int ins = wid + j * NW;
     const int e = ins * 512 + lane * 8;
     const int co = e / kSK, cp = (e % kSK) >> 3;
-    sdma16(rsW, 2u * (unsigned)(co * kSK + ((cp ^ (co & 15)) << 3)), Ws + ins * 512);
+    dma16(rsW, 2u * (unsigned)(co * kSK + ((cp ^ (co & 15)) << 3)), Ws + ins * 512);
   }
   // halo slots: staged pixel q (32 per piece, 2 lanes per pixel) -> offset from the
   // tile's first output-row pixel + {valid, source row - oh0}
@@ -213,7 +165,7 @@ __global__ void __launch_bounds__(256) stem_fwd_kernel(const u16* __restrict__ x
         const unsigned inf = x_inf[j];
         const int dh = (int)((inf >> 8) & 255) - 64;
         const bool ok = live && (inf >> 31) && (unsigned)(oh0 + dh) < (unsigned)OH;
-        sdma16(rsX, ok ? 2u * (unsigned)(m0 * 16 + x_off[j]) : kOOBs, As + (wid + j * NW) * 512);
+        dma16(rsX, ok ? 2u * (unsigned)(m0 * 16 + x_off[j]) : kOOB, As + (wid + j * NW) * 512);
       }
     }
   };
@@ -242,7 +194,7 @@ __global__ void __launch_bounds__(256) stem_fwd_kernel(const u16* __restrict__ x
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = smfma(bw[st & 1][j], af[st & 1][i], acc[i][j]);
+        for (int j = 0; j < TN; ++j) acc[i][j] = mfma16(bw[st & 1][j], af[st & 1][i], acc[i][j]);
     }
   };
 
@@ -309,8 +261,8 @@ __global__ void __launch_bounds__(256) stem_fwd_kernel(const u16* __restrict__ x
   for (int k = 0; k < nt; ++k) {
     // tile k (and, at k = 0, the weights) landed: later loads are only the
     // (NS-2) younger stages' pieces (epilogue stores may retire in any order)
-    if constexpr (NS == 2) swait_vm<0>();
-    else swait_vm_n((NS - 2) * APW);
+    if constexpr (NS == 2) wait_vm<0>();
+    else wait_vm_n<24>((NS - 2) * APW);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     stage((k + NS - 1) % NS, k + NS - 1);
@@ -323,35 +275,10 @@ __global__ void __launch_bounds__(256) stem_fwd_kernel(const u16* __restrict__ x
   }
   epilogue(nt - 1);
   if (STATS) {
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        s_sum[j][r] = srow_sum16(s_sum[j][r]);
-        s_sq[j][r] = srow_sum16(s_sq[j][r]);
-      }
-    swait_vm<0>();
+    wait_vm<0>();      // the ring's trailing DMAs have landed: Hs is free
     __syncthreads();
-    float* red = reinterpret_cast<float*>(Hs);
-    if (l16 == 15) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int nl = j * 16 + 4 * kg + r;
-          red[wid * kSCO + nl] = s_sum[j][r];
-          red[NW * kSCO + wid * kSCO + nl] = s_sq[j][r];
-        }
-    }
-    __syncthreads();
-    if (tid < kSCO) {
-      float ss = 0.f, qq = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { ss += red[w * kSCO + tid]; qq += red[NW * kSCO + w * kSCO + tid]; }
-      const int slot = blockIdx.x % kBnSlots;
-      atomicAdd(part + (long long)slot * kSCO + tid, ss);
-      atomicAdd(part + (long long)(kBnSlots + slot) * kSCO + tid, qq);
-    }
+    slot_sum_flush<NW, kSCO, 64 * NW>(s_sum, s_sq, reinterpret_cast<float*>(Hs), wid, 0, tid, lane,
+                                      part, 0, kSCO, blockIdx.x % kBnSlots);
   }
 }
 
@@ -413,14 +340,14 @@ __global__ void __launch_bounds__(256) stem_wgrad_kernel(const u16* __restrict__
     const int m0 = (b * OH + oh0) * OW;
 #pragma unroll
     for (int j = 0; j < D_PW; ++j)
-      sdma16(rsD, live ? 2u * (unsigned)(m0 * kSCO + d_off[j]) : kOOBs, Ds + (wid + j * NW) * 512);
+      dma16(rsD, live ? 2u * (unsigned)(m0 * kSCO + d_off[j]) : kOOB, Ds + (wid + j * NW) * 512);
 #pragma unroll
     for (int j = 0; j < kSAPW; ++j) {
       if (j < APW) {
         const unsigned inf = x_inf[j];
         const int dh = (int)((inf >> 8) & 255) - 64;
         const bool ok = live && (inf >> 31) && (unsigned)(oh0 + dh) < (unsigned)OH;
-        sdma16(rsX, ok ? 2u * (unsigned)(m0 * 16 + x_off[j]) : kOOBs, Xs + (wid + j * NW) * 512);
+        dma16(rsX, ok ? 2u * (unsigned)(m0 * 16 + x_off[j]) : kOOB, Xs + (wid + j * NW) * 512);
       }
     }
   };
@@ -472,21 +399,21 @@ __global__ void __launch_bounds__(256) stem_wgrad_kernel(const u16* __restrict__
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) acc[i][s] = smfma(af[i], bx[s], acc[i][s]);
+        for (int i = 0; i < 4; ++i) acc[i][s] = mfma16(af[i], bx[s], acc[i][s]);
     }
   };
 
 #pragma unroll
   for (int s = 0; s < NS - 1; ++s) stage(s, s);
   for (int k = 0; k < nt; ++k) {
-    if constexpr (NS == 2) swait_vm<0>();
-    else swait_vm_n((NS - 2) * (D_PW + APW));
+    if constexpr (NS == 2) wait_vm<0>();
+    else wait_vm_n<24>((NS - 2) * (D_PW + APW));
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     stage((k + NS - 1) % NS, k + NS - 1);
     compute(k % NS);
   }
-  swait_vm<0>();
+  wait_vm<0>();
   // D layout: lane holds rows co = 4*(lane>>4)+rr of column ci = lane & 15
 #pragma unroll
   for (int i = 0; i < 4; ++i)

@@ -329,10 +329,6 @@ class _NativeConv(Function):
                                            relu)
         # ReLU fused in the epilogue; its backward masks dY by the saved output
         ctx.save_for_backward(x, w16, y if relu else None)
-        # input produced by a training BatchNorm(+ReLU): its backward reduce can
-        # run in this conv's dgrad epilogue (ops/functional.py BNLink)
-        link = getattr(x, "_dmp_bnlink", None)
-        ctx.bnlink = link if link is not None and link.consumer_ok(x) else None
         ctx.master = master
         ctx.geom = (x.shape[2], x.shape[3], stride, pad)
         # alias: x handed back as a third output (a view whose gradient arrives
@@ -403,28 +399,13 @@ class _NativeConv(Function):
             shadow = getattr(master, "_dmp_w16", None)
             if arena is not None and shadow is not None and shadow.data_ptr() == w16.data_ptr():
                 wt = arena.transposed_conv_shadow(master)
-            bn = ctx.bnlink
-            if bn is not None:
-                dx = native().conv_dgrad(dy, w16, H, W, stride, pad, cfg, wt, dxa, bn_x=bn.x,
-                                         bn_mask=(x if bn.relu == 1 else
-                                                  bn.mask if bn.relu == 3 else None),
-                                         bn_stats=bn.stats, bn_part=bn.part, bn_relu=bn.relu,
-                                         addend_sub=sub, addend_mask=amask)
-                bn.fused = (dx, dx._version)
-            else:
-                dx = native().conv_dgrad(dy, w16, H, W, stride, pad, cfg, wt, dxa,
-                                         addend_sub=sub, addend_mask=amask)
+            dx = native().conv_dgrad(dy, w16, H, W, stride, pad, cfg, wt, dxa,
+                                     addend_sub=sub, addend_mask=amask)
         elif dxa is not None:
             dx = dxa
         if sub_after is not None:
             dx = dx.contiguous(memory_format=torch.channels_last)
             native().add_subsampled2(dx, sub_after)
-            link = ctx.bnlink
-            if link is not None and link.fused is not None:
-                # the native in-place add does not bump autograd's version counter:
-                # invalidate the BN partials the fused dgrad epilogue recorded (they
-                # miss the added gradient) so the BN backward redoes its reduce
-                link.fused = (link.fused[0], -1)
         gw = None
         bias = ctx.bias
         # a conv bias gradient (AlexNet) summed by the gather wgrad kernel from the

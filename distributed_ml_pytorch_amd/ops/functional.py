@@ -233,16 +233,8 @@ def softmax_cross_entropy(logits, labels, label_smoothing: float = 0.0, ignore_i
 
 
 # ------------------------------------------------------------------ batchnorm
-# which BatchNorms hand their backward reduce to the consuming conv's dgrad
-# epilogue: "0" (default), "residual" (BN + residual + ReLU only) or "all".
-# Measured a loss or a wash (profiles/bn_bwd_fusion_r2.txt): the conv kernels
-# are bound by their per-CU global->LDS fill, and the epilogue's extra reads of
-# x (and the mask) go through that same path, costing more inside the conv
-# (+30-50 % on the 64-channel dgrads) than the standalone streaming reduce
-# they replace -- once the residual BNs keep a 1-bit ReLU mask instead of
-# re-reading y, the separate pass is the cheaper place for those bytes.
-_BN_BWD_FUSE = os.environ.get("DMP_BN_BWD_FUSE", "0")
-BN_BWD_FUSE_STATS = {"fused": 0, "fallback": 0}
+# (running the backward reduce inside the consuming conv's dgrad epilogue was
+# tried and measured a loss: profiles/bn_bwd_fusion_r2.txt)
 _BN_BITMASK = os.environ.get("DMP_BN_BITMASK", "1") != "0"   # backward passes by path (diagnostics)
 # BatchNorm finalize folded into the apply passes (csrc/bn.hip fold kernels): no
 # separate finalize launch per BN and direction.  Slot hygiene: the forward apply
@@ -281,33 +273,6 @@ def _fresh_slots(buf, C, device):
     return clean_slots(buf)
 
 
-class BNLink:
-    """Hand-off between a training BatchNorm(+ReLU) and the native conv that
-    consumes its output (attached to the output as ``_dmp_bnlink``).
-
-    The conv's data-gradient epilogue can run the BN backward's reduce pass
-    itself (csrc/conv.hip ``bnb_*``): it stores dz = dX * relu'(.) and adds
-    sum(dz), sum(dz * xhat) into the BN's backward slot buffer ``part``, then
-    records ``fused = (dX, version)``.  The BN backward uses those partials only
-    if the gradient it receives IS that tensor, unmodified (same storage and
-    version: no other consumer's gradient was accumulated into it); otherwise it
-    re-zeroes the slots and runs the full reduce (the ReLU mask is idempotent,
-    so a pre-masked contribution stays correct)."""
-
-    __slots__ = ("x", "stats", "relu", "part", "y_ptr", "fused", "mask")
-
-    def __init__(self, x, stats, relu: int, part, y, mask=None):
-        self.x, self.stats, self.part = x, stats, part
-        # ReLU-mask source for the epilogue: 3 = the forward's bit mask
-        self.relu = 3 if (relu == 1 and mask is not None) else relu
-        self.mask = mask
-        self.y_ptr = y.data_ptr()
-        self.fused = None
-
-    def consumer_ok(self, inp) -> bool:
-        return inp.data_ptr() == self.y_ptr and inp.shape == self.x.shape
-
-
 class _BNAct(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, training, momentum, eps,
@@ -322,7 +287,7 @@ class _BNAct(Function):
         # BN + residual + ReLU: the backward's ReLU mask depends on the residual;
         # keep it as 1 bit per element (written by the apply) instead of y
         want_mask = bool(relu and residual is not None and _BN_BITMASK)
-        ctx.fold = bool(_BN_FOLD and training and x.is_cuda and _BN_BWD_FUSE in ("0", False))
+        ctx.fold = bool(_BN_FOLD and training and x.is_cuda)
         ctx.fpart = None
         if ctx.fold:
             C = x.shape[1]
@@ -353,13 +318,6 @@ class _BNAct(Function):
                                              bool(relu), slots[0] if slots is not None else None,
                                              want_mask)
         ctx.bslots = slots[1] if slots is not None else None
-        ctx.link = None
-        if (_BN_BWD_FUSE not in ("0", False) and training and x.dim() == 4 and x.is_cuda
-                and ctx.bslots is not None
-                and (residual is not None and relu or _BN_BWD_FUSE in ("all", True))):
-            mode = 0 if not relu else (1 if residual is not None else 2)
-            ctx.link = BNLink(x, stats, mode, ctx.bslots, y, mask)
-            y._dmp_bnlink = ctx.link
         ctx.relu = relu
         ctx.has_res = residual is not None
         # dres handed over unmasked with the bit mask (see deferred residual mask)
@@ -389,16 +347,6 @@ class _BNAct(Function):
             torch.zeros_like(gamma) if need_g else None)
         db = db_arena if db_arena is not None else (
             torch.zeros_like(beta) if need_b else None)
-        link = ctx.link
-        fused = False
-        if link is not None and link.fused is not None:
-            fdx, fver = link.fused
-            link.fused = None
-            fused = (dy.data_ptr() == fdx.data_ptr() and dy._version == fver
-                     and dy.shape == fdx.shape and dy.stride() == fdx.stride())
-            BN_BWD_FUSE_STATS["fused" if fused else "fallback"] += 1
-            if not fused:
-                link.part.zero_()        # partial sums of an incomplete gradient
         if ctx.fold:
             if x.dim() == 4:
                 dy = dy.contiguous(memory_format=CL)
@@ -419,10 +367,6 @@ class _BNAct(Function):
             mark_slots(bs, True)
             mark_slots(ctx.fpart, False)
             ctx.fpart = None
-        elif fused:
-            # the consuming conv's dgrad already masked dz and reduced it
-            dx = native().bn_bwd_from_partials(x, dy, gamma, stats, dg, db, link.part)
-            dres = dy if ctx.has_res else None
         else:
             if x.dim() == 4:
                 dy = dy.contiguous(memory_format=CL)
@@ -579,7 +523,7 @@ class _BNReLUPool(Function):
 def bn_relu_maxpool_ok(x, bn, k: int, s: int, p: int) -> bool:
     """The fused training path applies: a bf16 GPU NHWC activation feeding a
     ReLU BatchNorm in batch-statistics mode, then a 3x3/s2/p1 max pool."""
-    return bool(_BN_POOL_FUSE and _BN_FOLD and _BN_BWD_FUSE in ("0", False) and x.is_cuda
+    return bool(_BN_POOL_FUSE and _BN_FOLD and x.is_cuda
                 and x.dtype == torch.bfloat16 and x.dim() == 4 and bn.training
                 and getattr(bn, "relu", False) and 2 * x.numel() < 2 ** 31
                 and native().bn_maxpool_supported(x.shape[1], k, s, p))

@@ -73,6 +73,13 @@ def test_every_tile_config(shape):
     xr = x.float().requires_grad_(True)
     wr = w.float().requires_grad_(True)
     F.conv2d(xr, wr, None, st, pd).backward(dy.float())
+    add = torch.randn_like(x)
+    if st == 2:
+        # odd H and W: parity class (0, 0) is larger than the others
+        sub = torch.randn(B, CI, (H + 1) // 2, (W + 1) // 2, device="cuda").to(torch.bfloat16)
+        sub = sub.contiguous(memory_format=CL)
+        ref_sub = xr.grad.clone()
+        ref_sub[:, :, ::2, ::2] += sub.float()
     for cfg in [c[0] for c in nat.conv_configs()]:
         y, part, G = nat.conv_fwd(x, w, st, pd, True, cfg)
         assert _rel(y, yr) < 1e-2, cfg
@@ -80,6 +87,13 @@ def test_every_tile_config(shape):
         torch.testing.assert_close(ps[0], y.float().sum(dim=(0, 2, 3)), rtol=1e-3, atol=1e-2)
         dx = nat.conv_dgrad(dy, w, H, W, st, pd, cfg)
         assert _rel(dx, xr.grad) < 1e-2, cfg
+        # residual-gradient addend in the dgrad epilogue: full resolution, and
+        # (stride 2) the subsampled one that lands on parity class (0, 0) only
+        dxa = nat.conv_dgrad(dy, w, H, W, st, pd, cfg, None, add)
+        assert _rel(dxa, xr.grad + add.float()) < 1e-2, cfg
+        if st == 2:
+            dxs = nat.conv_dgrad(dy, w, H, W, st, pd, cfg, addend=sub, addend_sub=True)
+            assert _rel(dxs, ref_sub) < 1e-2, cfg
     from distributed_ml_pytorch_amd.ops.conv import _wgrad_candidates
 
     for cfg in _wgrad_candidates(CI * k * k, CO):
@@ -672,10 +686,9 @@ def test_stem_conv_layer_route():
     assert _rel(master.grad, wr.grad) < 1e-2
 
 
-def _grads_with_bn_fusion(monkeypatch, fuse, model, x, g, bitmask=True):
+def _grads_with_bn_fusion(monkeypatch, model, x, g, bitmask=True):
     from distributed_ml_pytorch_amd.ops import functional as Fn
 
-    monkeypatch.setattr(Fn, "_BN_BWD_FUSE", fuse if fuse else "0")
     monkeypatch.setattr(Fn, "_BN_BITMASK", bitmask)
     for p in model.parameters():
         p.grad = None
@@ -687,15 +700,13 @@ def _grads_with_bn_fusion(monkeypatch, fuse, model, x, g, bitmask=True):
 
 
 @pytest.mark.parametrize("kind", ["basic_s1", "basic_s2", "bottleneck"])
-def test_bn_backward_fused_into_dgrad(kind, monkeypatch):
-    """BN(+ReLU) backward reductions run in the consuming conv's dgrad epilogue
-    (csrc/conv.hip bnb_*; ops/functional.py BNLink): gradients match the
-    separate reduce pass.  Two chained blocks exercise both ReLU-mask sources:
-    bn1 -> conv2 (mask recomputed from x) and block 1's bn2 + residual ->
-    block 2's conv1 with the shortcut gradient as the dgrad addend (mask from
-    the stored output)."""
+def test_bn_bitmask_matches_saved_output_mask(kind, monkeypatch):
+    """The residual BatchNorms' backward with the forward's 1-bit ReLU mask
+    matches the one that reads the mask from the stored output y.  Two chained
+    blocks exercise both ReLU-mask sources: bn1 -> conv2 (mask recomputed from
+    x) and block 1's bn2 + residual -> block 2's conv1 with the shortcut
+    gradient as the dgrad addend (bit mask, or the stored output)."""
     from distributed_ml_pytorch_amd.models.resnet import BasicBlock, Bottleneck
-    from distributed_ml_pytorch_amd.ops import functional as Fn
 
     torch.manual_seed(0)
     if kind == "bottleneck":
@@ -707,56 +718,16 @@ def test_bn_backward_fused_into_dgrad(kind, monkeypatch):
         x = torch.randn(4, 64, 16, 16, device="cuda")
     x = x.to(torch.bfloat16).contiguous(memory_format=CL)
     g = torch.randn(model(x).shape, device="cuda")
-    # reference: standalone reduce, ReLU mask of the residual BNs read from y
-    y0, ref = _grads_with_bn_fusion(monkeypatch, False, model, x, g, bitmask=False)
-    # standalone reduce with the forward's 1-bit mask
-    _, bits = _grads_with_bn_fusion(monkeypatch, False, model, x, g)
+    # reference: ReLU mask of the residual BNs read from y
+    y0, ref = _grads_with_bn_fusion(monkeypatch, model, x, g, bitmask=False)
+    # the forward's 1-bit mask
+    y1, bits = _grads_with_bn_fusion(monkeypatch, model, x, g)
+    assert _rel(y1, y0) < 1e-3        # forward untouched (atomic-order noise only)
     for a, b in zip(ref, bits):
         assert _rel(b, a) < 5e-3
-    before = dict(Fn.BN_BWD_FUSE_STATS)
-    y1, got = _grads_with_bn_fusion(monkeypatch, "all", model, x, g)
-    assert Fn.BN_BWD_FUSE_STATS["fused"] > before["fused"]
-    assert _rel(y1, y0) < 1e-3        # forward untouched (atomic-order noise only)
-    for a, b in zip(ref, got):
-        assert _rel(b, a) < 5e-3
-    # the default policy (residual BNs only)
-    _, res = _grads_with_bn_fusion(monkeypatch, "residual", model, x, g)
-    for a, b in zip(ref, res):
-        assert _rel(b, a) < 5e-3
     # a second identical step: persistent slot buffers were left zeroed
-    _, again = _grads_with_bn_fusion(monkeypatch, "all", model, x, g)
-    for a, b in zip(got, again):
-        assert _rel(b, a) < 5e-3
-
-
-def test_bn_backward_fusion_falls_back_on_shared_output(monkeypatch):
-    """A BN output read by two convs: each conv's dgrad records a fused
-    reduction, autograd sums the two input gradients, and the BN backward must
-    notice (different tensor) and redo the reduce over the summed gradient."""
-    from distributed_ml_pytorch_amd.ops import functional as Fn
-    from distributed_ml_pytorch_amd.ops.layers import BatchNorm2d, Conv2d
-
-    class Fork(torch.nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.conv0 = Conv2d(64, 64, 3, 1, 1, bias=False)
-            self.bn = BatchNorm2d(64, relu=True)
-            self.a = Conv2d(64, 64, 3, 1, 1, bias=False)
-            self.b = Conv2d(64, 64, 1, 1, 0, bias=False)
-
-        def forward(self, x):
-            h = self.bn(self.conv0(x))
-            return self.a(h) + self.b(h)
-
-    torch.manual_seed(0)
-    model = Fork().cuda()
-    x = torch.randn(4, 64, 16, 16, device="cuda").to(torch.bfloat16).contiguous(memory_format=CL)
-    g = torch.randn(4, 64, 16, 16, device="cuda")
-    _, ref = _grads_with_bn_fusion(monkeypatch, False, model, x, g)
-    before = dict(Fn.BN_BWD_FUSE_STATS)
-    _, got = _grads_with_bn_fusion(monkeypatch, "all", model, x, g)
-    assert Fn.BN_BWD_FUSE_STATS["fallback"] > before["fallback"]
-    for a, b in zip(ref, got):
+    _, again = _grads_with_bn_fusion(monkeypatch, model, x, g)
+    for a, b in zip(bits, again):
         assert _rel(b, a) < 5e-3
 
 
