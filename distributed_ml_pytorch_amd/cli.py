@@ -76,6 +76,13 @@ def build_parser() -> argparse.ArgumentParser:
                    help="sharded PS: combine simultaneous pushes by 'sum' (Downpour), 'mean' or x")
     p.add_argument("--ps-worker-timeout", type=float, default=0.0,
                    help="central PS drops a worker silent for this many seconds (0 = never)")
+    p.add_argument("--stale-bound", type=int, default=0, metavar="S",
+                   help="version-based staleness bound S of --stale-policy")
+    p.add_argument("--stale-policy", default="off", choices=["off", "damp", "block"],
+                   help="central / sharded_async PS: 'block' defers a worker's pulls while its "
+                        "push clock is more than S ahead of the slowest active worker "
+                        "(stale-synchronous parallel); 'damp' applies a push that is tau > S "
+                        "versions stale at weight 1 / (1 + tau - S); 'off' only reports")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log-dir", default="log")
     p.add_argument("--no-eval", action="store_true", default=False)
@@ -96,7 +103,8 @@ def config_from_args(a) -> TrainConfig:
         cuda=a.cuda, log_interval=a.log_interval, evaluate=not a.no_eval, seed=a.seed,
         log_dir=a.log_dir, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every,
         resume=a.resume, ps_resume=a.ps_resume, delta_scale=a.delta_scale,
-        ps_worker_timeout=a.ps_worker_timeout, bucket_mb=a.bucket_mb,
+        ps_worker_timeout=a.ps_worker_timeout, stale_bound=a.stale_bound,
+        stale_policy=a.stale_policy, bucket_mb=a.bucket_mb,
         label_smoothing=a.label_smoothing, divergence_check=not a.no_divergence_check,
         deterministic=a.deterministic)
 

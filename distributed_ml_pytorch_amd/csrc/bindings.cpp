@@ -71,29 +71,38 @@ void asgd_fused_step(Tensor g, Tensor p, optional<Tensor> acc, optional<Tensor> 
                               cur_stream());
 }
 
-void ps_apply(Tensor shard, Tensor delta, optional<Tensor> mirror, double scale, bool atomic) {
+// `factor`: the {factor, tau} slot ps_stale_factor wrote on the current stream
+// (staleness damping: scale * factor is applied); None = the plain apply
+void ps_apply(Tensor shard, Tensor delta, optional<Tensor> mirror, double scale, bool atomic,
+              optional<Tensor> factor) {
   const int64_t n = shard.numel();
   TORCH_CHECK(n % 4 == 0, "shard length must be a multiple of 4");
   check_flat(shard, at::kFloat, n, "shard");
   if (mirror) check_flat(*mirror, at::kBFloat16, n, "mirror");
+  if (factor)
+    TORCH_CHECK(factor->is_cuda() && factor->scalar_type() == at::kFloat &&
+                    factor->numel() >= 1 && factor->is_contiguous() &&
+                    factor->device() == shard.device(),
+                "ps_apply: factor must be a contiguous fp32 tensor on the shard's device");
+  const float* fac = ptr_or_null<const float>(factor);
   if (atomic) {
     // concurrent applies on several streams: no mirror (it would race)
     TORCH_CHECK(!mirror, "ps_apply: atomic applies take no bf16 mirror");
     const bool bf = delta.scalar_type() == at::kBFloat16;
     check_flat(delta, bf ? at::kBFloat16 : at::kFloat, n, "delta");
     dmp::launch_ps_apply_atomic(shard.data_ptr<float>(), delta.data_ptr(), bf, n, (float)scale,
-                                cur_stream());
+                                cur_stream(), fac);
     return;
   }
   if (delta.scalar_type() == at::kFloat) {
     check_flat(delta, at::kFloat, n, "delta");
     dmp::launch_ps_apply_f32(shard.data_ptr<float>(), delta.data_ptr<float>(),
-                             ptr_or_null<uint16_t>(mirror), n, (float)scale, cur_stream());
+                             ptr_or_null<uint16_t>(mirror), n, (float)scale, cur_stream(), fac);
   } else {
     check_flat(delta, at::kBFloat16, n, "delta");
     dmp::launch_ps_apply_bf16(shard.data_ptr<float>(),
                               reinterpret_cast<uint16_t*>(delta.data_ptr()),
-                              ptr_or_null<uint16_t>(mirror), n, (float)scale, cur_stream());
+                              ptr_or_null<uint16_t>(mirror), n, (float)scale, cur_stream(), fac);
   }
 }
 
@@ -113,6 +122,31 @@ void ps_stamp(Tensor cnt, Tensor dst) {
                   dst.device() == cnt.device(),
               "ps_stamp: dst must be a 1-element fp32 tensor on the counter's device");
   dmp::launch_ps_stamp(cnt.data_ptr<int>(), dst.data_ptr<float>(), cur_stream());
+}
+
+// Staleness factor of the next apply on the current stream (parallel/staleness.py,
+// policy "damp"): tau = max(0, min(counter, cap) - base), f = 1 / (1 + max(0, tau - bound))
+// -> slot = {f, tau}; the apply index, max tau, damped count and a ring of
+// (tau, f) go to the int32 `log` (ps_stale_log_numel() elements).  `cap`: the
+// host's enqueue count when the push arrived (None = no clamp)
+void ps_stale_factor(Tensor cnt, int64_t base, int64_t bound, Tensor slot, Tensor log,
+                     optional<int64_t> cap) {
+  TORCH_CHECK(cnt.is_cuda() && cnt.scalar_type() == at::kInt && cnt.numel() == 1,
+              "ps_stale_factor: counter must be a 1-element int32 GPU tensor");
+  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kFloat && slot.numel() == 2 &&
+                  slot.is_contiguous() && slot.device() == cnt.device(),
+              "ps_stale_factor: slot must be a 2-element fp32 tensor on the counter's device");
+  TORCH_CHECK(log.is_cuda() && log.scalar_type() == at::kInt && log.is_contiguous() &&
+                  log.numel() == dmp::stale_log_numel() && log.device() == cnt.device(),
+              "ps_stale_factor: log must be an int32 tensor of ps_stale_log_numel() elements "
+              "on the counter's device");
+  TORCH_CHECK(bound >= 0 && bound < (int64_t(1) << 30) && base > -(int64_t(1) << 30) &&
+                  base < (int64_t(1) << 30),
+              "ps_stale_factor: bound must be in [0, 2^30) and |base| below 2^30");
+  const int64_t top = (int64_t(1) << 30);
+  const int c = (int)std::min<int64_t>(std::max<int64_t>(cap.value_or(top), -top), top);
+  dmp::launch_ps_stale_factor(cnt.data_ptr<int>(), (int)base, (int)bound, c,
+                              slot.data_ptr<float>(), log.data_ptr<int>(), cur_stream());
 }
 
 void pull_land(Tensor p, Tensor src, optional<Tensor> acc, optional<Tensor> w16) {
@@ -1758,10 +1792,16 @@ PYBIND11_MODULE(_native, m) {
         },
         "fwd / dgrad remainder split-K: fp32 workspace floats per split tile (0 = no split)");
   m.def("ps_apply", &ps_apply, "parameter-server delta apply", py::arg("shard"), py::arg("delta"),
-        py::arg("mirror") = py::none(), py::arg("scale") = 1.0, py::arg("atomic") = false);
+        py::arg("mirror") = py::none(), py::arg("scale") = 1.0, py::arg("atomic") = false,
+        py::arg("factor") = py::none());
   m.def("ps_count", &ps_count, "bump / set a PS applied-count", py::arg("cnt"),
         py::arg("add") = 1, py::arg("set") = false);
   m.def("ps_stamp", &ps_stamp, "copy a PS applied-count into a reply's version element");
+  m.def("ps_stale_factor", &ps_stale_factor, "publish the staleness factor of the next apply",
+        py::arg("cnt"), py::arg("base"), py::arg("bound"), py::arg("slot"), py::arg("log"),
+        py::arg("cap") = py::none());
+  m.def("ps_stale_log_numel", []() { return dmp::stale_log_numel(); },
+        "int32 elements of a ps_stale_factor log");
   m.def("pull_land", &pull_land, "land a parameter pull into the worker arena");
   m.def("push_handoff", &push_handoff, "snapshot+zero the push accumulator");
   m.def("cast_f32_bf16", &cast_f32_bf16, "flat fp32 -> bf16");

@@ -11,14 +11,19 @@ namespace dmp {
 void launch_asgd_fused_step(const float* g, float* p, float* acc, float* mom, uint16_t* w16,
                             long long n, float lr, float wd, float momentum, float dampening,
                             bool nesterov, hipStream_t s);
+// `factor`: one device fp32 published by launch_ps_stale_factor on the same
+// stream (staleness damping); null = the plain apply
 void launch_ps_apply_atomic(float* shard, const void* delta, bool bf16, long long n, float scale,
-                            hipStream_t s);
+                            hipStream_t s, const float* factor = nullptr);
 void launch_ps_apply_f32(float* shard, const float* delta, uint16_t* mirror, long long n,
-                         float scale, hipStream_t s);
+                         float scale, hipStream_t s, const float* factor = nullptr);
 void launch_ps_apply_bf16(float* shard, const uint16_t* delta, uint16_t* mirror, long long n,
-                          float scale, hipStream_t s);
+                          float scale, hipStream_t s, const float* factor = nullptr);
 void launch_ps_count(int* cnt, int add, bool set, hipStream_t s);
 void launch_ps_stamp(int* cnt, float* dst, hipStream_t s);
+int stale_log_numel();
+void launch_ps_stale_factor(int* cnt, int base, int bound, int cap, float* slot, int* log,
+                            hipStream_t s);
 void launch_pull_land_f32(float* p, const float* src, const float* acc, uint16_t* w16,
                           long long n, hipStream_t s);
 void launch_pull_land_bf16(float* p, const uint16_t* src, const float* acc, uint16_t* w16,

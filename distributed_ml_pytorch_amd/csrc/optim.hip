@@ -64,11 +64,22 @@ __global__ void __launch_bounds__(256) asgd_fused_step_kernel(
   }
 }
 
+// Staleness damping (parallel/staleness.py, policy "damp"): an apply may take a
+// pointer to ONE fp32 factor that ps_stale_factor_kernel (below) published on
+// the same stream before this kernel started.  Every thread loads it once (an
+// agent-scope load: served by L2, the same word for the whole grid) and uses
+// scale * factor; a null pointer is the undamped apply.
+__device__ __forceinline__ float ps_scale(float scale, const float* factor) {
+  return factor ? scale * __hip_atomic_load(factor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                : scale;
+}
+
 // shard += scale * delta (fp32 delta)      -- PS GradientUpdate apply
 // optional: mirror the new shard into bf16 for low-precision pulls.
 __global__ void __launch_bounds__(256) ps_apply_f32_kernel(
     float4* __restrict__ shard, const float4* __restrict__ delta, bf16x4* __restrict__ mirror,
-    long long n4, float scale) {
+    long long n4, float scale, const float* factor = nullptr) {
+  scale = ps_scale(scale, factor);
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 s = shard[i];
@@ -86,7 +97,8 @@ __global__ void __launch_bounds__(256) ps_apply_f32_kernel(
 // shard += scale * delta (bf16 wire-format delta)
 __global__ void __launch_bounds__(256) ps_apply_bf16_kernel(
     float4* __restrict__ shard, const bf16x4* __restrict__ delta, bf16x4* __restrict__ mirror,
-    long long n4, float scale) {
+    long long n4, float scale, const float* factor = nullptr) {
+  scale = ps_scale(scale, factor);
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 s = shard[i];
@@ -111,7 +123,9 @@ __global__ void __launch_bounds__(256) ps_apply_bf16_kernel(
 template <typename D>
 __global__ void __launch_bounds__(256) ps_apply_atomic_kernel(float* __restrict__ shard,
                                                               const D* __restrict__ delta,
-                                                              long long n, float scale) {
+                                                              long long n, float scale,
+                                                              const float* factor = nullptr) {
+  scale = ps_scale(scale, factor);
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
     float d;
@@ -142,6 +156,52 @@ __global__ void __launch_bounds__(64) ps_stamp_kernel(int* __restrict__ cnt,
   if (threadIdx.x == 0) {
     const int v = __hip_atomic_fetch_add(cnt, 0, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
     dst[0] = (float)v;
+  }
+}
+
+// Staleness factor of ONE apply (policy "damp").  Runs on the applying stream
+// immediately before the apply kernel: reads the applied count (agent-scope
+// acquire, as ps_stamp does), forms tau = max(0, count - base) where `base` is
+// the version the pushed delta was computed from (its header), and publishes
+//   f(tau) = 1 for tau <= bound,  1 / (1 + tau - bound) above
+// as {factor, tau} in the stream's own 2-float slot: the next apply on the same
+// stream is ordered behind this one, so one slot per stream is enough.  One
+// factor per apply, complete before the apply starts, on purpose: blocks of the
+// apply never read the counter themselves (it can move mid-kernel, which would
+// scale different elements differently) and no block waits for another.
+// tau is the staleness when THIS kernel ran: a lower bound on the staleness
+// when the apply lands (other streams' applies may land in between), the same
+// lower-bound semantics as the reply stamps.  `cap` is the host's enqueue count
+// when the push's header was handled: the count is clamped to it, so tau never
+// exceeds the staleness the host logged for the same push.  A faster link's
+// LATER pushes may have landed by now (completion-ordered applies); the server
+// ordered them behind this push and they do not count against it.
+// log (int32, kStaleLogHead + 2 * kStaleLogRing): [0] applies seen, [1] max tau,
+// [2] damped applies (tau > bound), then a wrapping ring of (tau, factor bits)
+// indexed by the apply's number.  All agent-scope atomics: factor kernels of
+// different link streams run concurrently on any XCD; the host reads the log
+// after a sync (stats, tests).
+constexpr int kStaleLogHead = 4;
+constexpr int kStaleLogRing = 1024;
+
+__global__ void __launch_bounds__(64) ps_stale_factor_kernel(int* __restrict__ cnt, int base,
+                                                             int bound, int cap,
+                                                             float* __restrict__ slot,
+                                                             int* __restrict__ log) {
+  if (threadIdx.x == 0) {
+    int v = __hip_atomic_fetch_add(cnt, 0, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+    v = v < cap ? v : cap;
+    const int tau = v > base ? v - base : 0;
+    const float f = tau <= bound ? 1.f : 1.f / (float)(1 + tau - bound);
+    __hip_atomic_store(slot, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(slot + 1, (float)tau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int idx = __hip_atomic_fetch_add(log, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_max(log + 1, tau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tau > bound)
+      __hip_atomic_fetch_add(log + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int* e = log + kStaleLogHead + 2 * (int)((unsigned)idx % (unsigned)kStaleLogRing);
+    __hip_atomic_store(e, tau, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(e + 1, __float_as_int(f), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -272,29 +332,29 @@ void launch_asgd_fused_step(const float* g, float* p, float* acc, float* mom, u1
 }
 
 void launch_ps_apply_f32(float* shard, const float* delta, u16* mirror, long long n, float scale,
-                         hipStream_t s) {
+                         hipStream_t s, const float* factor) {
   const long long n4 = n / 4;
   hipLaunchKernelGGL(ps_apply_f32_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                     (float4*)shard, (const float4*)delta, (bf16x4*)mirror, n4, scale);
+                     (float4*)shard, (const float4*)delta, (bf16x4*)mirror, n4, scale, factor);
 }
 
 void launch_ps_apply_bf16(float* shard, const u16* delta, u16* mirror, long long n, float scale,
-                          hipStream_t s) {
+                          hipStream_t s, const float* factor) {
   const long long n4 = n / 4;
   hipLaunchKernelGGL(ps_apply_bf16_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                     (float4*)shard, (const bf16x4*)delta, (bf16x4*)mirror, n4, scale);
+                     (float4*)shard, (const bf16x4*)delta, (bf16x4*)mirror, n4, scale, factor);
 }
 
 void launch_ps_apply_atomic(float* shard, const void* delta, bool bf16, long long n, float scale,
-                            hipStream_t s) {
+                            hipStream_t s, const float* factor) {
   if (n <= 0) return;   // an empty shard: nothing to add (a 0-block grid is invalid)
   const int grid = (int)std::min<long long>((n + 255) / 256, 256LL * 16);
   if (bf16)
     hipLaunchKernelGGL(ps_apply_atomic_kernel<u16>, dim3(grid), dim3(256), 0, s, shard,
-                       (const u16*)delta, n, scale);
+                       (const u16*)delta, n, scale, factor);
   else
     hipLaunchKernelGGL(ps_apply_atomic_kernel<float>, dim3(grid), dim3(256), 0, s, shard,
-                       (const float*)delta, n, scale);
+                       (const float*)delta, n, scale, factor);
 }
 
 void launch_ps_count(int* cnt, int add, bool set, hipStream_t s) {
@@ -303,6 +363,14 @@ void launch_ps_count(int* cnt, int add, bool set, hipStream_t s) {
 
 void launch_ps_stamp(int* cnt, float* dst, hipStream_t s) {
   hipLaunchKernelGGL(ps_stamp_kernel, dim3(1), dim3(64), 0, s, cnt, dst);
+}
+
+int stale_log_numel() { return kStaleLogHead + 2 * kStaleLogRing; }
+
+void launch_ps_stale_factor(int* cnt, int base, int bound, int cap, float* slot, int* log,
+                            hipStream_t s) {
+  hipLaunchKernelGGL(ps_stale_factor_kernel, dim3(1), dim3(64), 0, s, cnt, base, bound, cap,
+                     slot, log);
 }
 
 void launch_pull_land_f32(float* p, const float* src, const float* acc, u16* w16, long long n,

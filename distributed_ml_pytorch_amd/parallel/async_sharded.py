@@ -44,6 +44,7 @@ from __future__ import annotations
 
 import logging
 import threading
+import time
 from collections import Counter, deque
 
 import torch
@@ -52,6 +53,7 @@ import torch.distributed as dist
 from . import messaging as M
 from .clients import PSClient, _EventWork, _Pending
 from .links import AppliedCount, PairGroupTransport, PairLinks, wait_on, warm_stream
+from .staleness import DeviceStaleLog, StalenessGate, check_policy
 
 _LOG = logging.getLogger(__name__)
 
@@ -94,10 +96,17 @@ class ShardServer:
     """One rank's shard of the master, served to every rank from a thread.
 
     ``push_groups[(sender, rank)]`` / ``reply_groups[(rank, dst)]``: the payload
-    groups this server receives pushes on / sends replies on."""
+    groups this server receives pushes on / sends replies on.
+
+    ``stale_policy`` / ``stale_bound``: the staleness bound of :mod:`.staleness`.
+    Every rank is a worker of this shard; the co-located rank's :meth:`apply`
+    counts as its push and its :meth:`snapshot` obeys the same gate as a peer's
+    ``ParameterRequest`` (``block_timeout``: it raises instead of hanging)."""
 
     def __init__(self, rank: int, world: int, init_shard: torch.Tensor, req_group,
-                 push_groups: dict, reply_groups: dict, scale: float = 1.0, transport=None):
+                 push_groups: dict, reply_groups: dict, scale: float = 1.0, transport=None,
+                 stale_bound: int = 0, stale_policy: str = "off",
+                 block_timeout: float = 600.0):
         self.rank, self.world = rank, world
         self.device = init_shard.device
         self.cuda = self.device.type == "cuda"
@@ -127,9 +136,17 @@ class ShardServer:
         self.reply_g = reply_groups
         self.scale = scale
         self.lock = threading.Lock()
+        self.gate = StalenessGate(range(world), stale_bound, stale_policy)
+        self.gate_cv = threading.Condition(self.lock)   # the local worker's deferred pulls
+        self.block_timeout = block_timeout
         self.version = 0           # applies ENQUEUED (host): staleness of incoming pushes
         # applies wholly landed (device count on GPU): what a reply is stamped with
         self.applied = AppliedCount(self.device, self.nat if self.cuda else None)
+        # policy "damp" on the GPU: factors from the device count, per applying stream
+        self.stale_dev = None
+        if self.cuda and stale_policy == "damp":
+            self.stale_dev = DeviceStaleLog(self.device, self.nat, self.applied, stale_bound,
+                                            keys=range(world))
         self.counts: Counter = Counter()
         self.staleness: list[int] = []
         self.error: BaseException | None = None
@@ -147,6 +164,14 @@ class ShardServer:
                     self.nat.ps_apply(self.master, torch.zeros(self.n, dtype=dt,
                                                                device=self.device),
                                       None, self.scale, True)
+                    if self.stale_dev is not None:
+                        self.nat.ps_apply(self.master, torch.zeros(self.n, dtype=dt,
+                                                                   device=self.device),
+                                          None, self.scale, True,
+                                          torch.ones(2, device=self.device))
+                if self.stale_dev is not None:
+                    # a log of its own: the warm-up launch is no apply
+                    DeviceStaleLog(self.device, self.nat, self.applied, 0).factor(0, 0)
                 self.nat.ps_count(self.applied.dev, 0)
                 self.nat.ps_stamp(self.applied.dev, torch.empty(1, device=self.device))
             self.stream.synchronize()
@@ -160,17 +185,39 @@ class ShardServer:
         return torch.cuda.stream(self.stream) if self.cuda else _Null()
 
     # --------------------------------------------------------------- apply
-    def _apply_locked(self, delta: torch.Tensor, base_version: int | None):
+    def _apply_locked(self, delta: torch.Tensor, base_version: int | None, sender: int):
+        tau = self.version - base_version if base_version is not None else None
         if self.cuda:
             # fp32 atomics: the local apply (self.stream) and every peer's apply
             # (its own link stream, _recv_push) may run at the same time
-            self.nat.ps_apply(self.master, delta, None, self.scale, True)
+            if self.stale_dev is not None and tau is not None:
+                # damp: the factor from the device count, on this applying stream
+                fac = self.stale_dev.factor(sender, base_version, cap=self.version)
+                self.nat.ps_apply(self.master, delta, None, self.scale, True, fac)
+                self.gate.log.append((sender, tau, None))
+            else:
+                self.nat.ps_apply(self.master, delta, None, self.scale, True)
         else:
-            self.master.add_(delta.to(torch.float32), alpha=self.scale)
+            f = self.gate.note_push(sender, tau) if tau is not None else 1.0
+            self.master.add_(delta.to(torch.float32), alpha=self.scale * f)
         self.applied.bump()        # GPU: on the applying stream, counted once landed
-        if base_version is not None:
-            self.staleness.append(self.version - base_version)
+        if tau is not None:
+            self.staleness.append(tau)
         self.version += 1
+        self._answer(self.gate.on_push(sender))
+
+    def _answer(self, released):
+        """Serve the requests the gate released (lock held); wake the local worker."""
+        for w, _ in released:
+            if w != self.rank:
+                self._reply_locked(w)
+        self.gate_cv.notify_all()
+
+    def leave(self, worker: int):
+        """``worker`` (a peer's Shutdown, or the co-located worker finishing) pushes
+        no more: it no longer holds the others back."""
+        with self.lock:
+            self._answer(self.gate.leave(worker))
 
     def apply(self, delta: torch.Tensor, base_version: int | None = None):
         """Apply a delta from the calling thread (the co-located worker's own
@@ -182,27 +229,50 @@ class ShardServer:
             if self.cuda:
                 self.stream.wait_stream(torch.cuda.current_stream(self.device))
                 with self._ctx():
-                    self._apply_locked(delta, base_version)
+                    self._apply_locked(delta, base_version, self.rank)
                     done = torch.cuda.Event()
                     done.record()
                 delta.record_stream(self.stream)
                 return done
-            self._apply_locked(delta, base_version)
+            self._apply_locked(delta, base_version, self.rank)
             return None
 
-    def snapshot(self, out: torch.Tensor | None = None):
+    def _gate_local(self):
+        """Policy ``block`` for the co-located worker's pull (lock held): wait, with
+        the lock released, until its clock is within the bound of the slowest."""
+        if self.gate.eligible(self.rank):
+            return
+        self.gate.deferred[self.rank] += 1
+        t0 = time.monotonic()
+        ok = self.gate_cv.wait_for(lambda: self.gate.eligible(self.rank) or
+                                   self.error is not None, timeout=self.block_timeout)
+        self.gate.deferred_s += time.monotonic() - t0
+        if not ok or self.error is not None:
+            raise RuntimeError(
+                f"shard {self.rank}: local pull deferred by the staleness bound for "
+                f"{time.monotonic() - t0:.0f}s (clocks {self.gate.clock}, active "
+                f"{sorted(self.gate.active)}, error {self.error!r})")
+
+    def snapshot(self, out: torch.Tensor | None = None, gated: bool = True):
         """``(copy of the shard, version, event)``: on GPU the copy is taken on the
         PS stream after every LOCAL apply enqueued so far (peers' applies land on
         their link streams whenever their payloads arrive); ``event`` marks it done.
         ``version`` counts the applies the copy wholly contains: a host int on CPU,
         on GPU a 1-element device tensor stamped on the PS stream before the copy
-        (:class:`.links.AppliedCount`)."""
+        (:class:`.links.AppliedCount`).  ``gated``: a worker's pull, subject to the
+        staleness gate (checkpoints pass ``False``)."""
+        caller = torch.cuda.current_stream(self.device) if self.cuda else None
         with self.lock:
+            if gated:
+                self._gate_local()
             if not self.cuda:
                 snap = self.master.clone() if out is None else out.copy_(self.master)
                 return snap, self.applied.host, None
             with self._ctx():
                 v = torch.empty(1, dtype=torch.float32, device=self.device)
+                # allocated on the PS stream, read on the caller's: without this the
+                # block could be reused, and stamped over, before the caller has read it
+                v.record_stream(caller)
                 self.applied.stamp(v)
                 snap = self.master.clone() if out is None else out.copy_(self.master)
                 ev = torch.cuda.Event()
@@ -223,34 +293,41 @@ class ShardServer:
             # other peer's apply (the receive's ``ready`` is on that stream)
             s = self.rx.stream(sender)
             with self.lock, torch.cuda.stream(s):
-                self._apply_locked(slot.buf, version)
+                self._apply_locked(slot.buf, version, sender)
                 self.rx.release(slot, s)
             return
         with self.lock, self._ctx():
             wait_on(self.stream, ready)
-            self._apply_locked(slot.buf, version)
+            self._apply_locked(slot.buf, version, sender)
             self.rx.release(slot, self.stream)
 
     def _reply(self, dst: int):
-        n = self.n
         with self.lock:
-            def fill(buf):
-                self.applied.stamp(buf[n:])    # before the copy: wholly-landed applies
-                buf[:n].copy_(self.master)
+            # policy "block": deferred while dst is too far ahead (answered by a
+            # later push / leave, or when the server thread ends)
+            if self.gate.on_request(dst):
+                self._reply_locked(dst)
 
-            # snapshot on dst's own reply-link stream, after dst's own applies
-            # (its push-link stream: read-your-writes) and the local worker's
-            # (self.stream), never behind another peer's payload in flight; the
-            # ring slot is reused only after its previous send completed
-            if self.cuda:
-                s = self.tx.stream(dst)
-                for src in (self.rx.stream(dst), self.stream):
-                    ev = torch.cuda.Event()
-                    ev.record(src)
-                    s.wait_event(ev)
-                self.tx.send(dst, n + 1, torch.float32, fill, s)
-            else:
-                self.tx.send(dst, n + 1, torch.float32, fill, self.stream)
+    def _reply_locked(self, dst: int):
+        n = self.n
+
+        def fill(buf):
+            self.applied.stamp(buf[n:])    # before the copy: wholly-landed applies
+            buf[:n].copy_(self.master)
+
+        # snapshot on dst's own reply-link stream, after dst's own applies
+        # (its push-link stream: read-your-writes) and the local worker's
+        # (self.stream), never behind another peer's payload in flight; the
+        # ring slot is reused only after its previous send completed
+        if self.cuda:
+            s = self.tx.stream(dst)
+            for src in (self.rx.stream(dst), self.stream):
+                ev = torch.cuda.Event()
+                ev.record(src)
+                s.wait_event(ev)
+            self.tx.send(dst, n + 1, torch.float32, fill, s)
+        else:
+            self.tx.send(dst, n + 1, torch.float32, fill, self.stream)
 
     def _run(self):
         remaining = set(range(self.world)) - {self.rank}
@@ -264,8 +341,15 @@ class ShardServer:
                     self._reply(sender)
                 elif code == M.MessageCode.Shutdown:
                     remaining.discard(sender)
+                    self.leave(sender)
         except BaseException as e:   # surfaced by join()
             self.error = e
+        with self.lock:
+            # every peer has shut down (or the loop failed): nobody is left waiting
+            for w, _ in self.gate.drain():
+                if w != self.rank and self.error is None:
+                    self._reply_locked(w)
+            self.gate_cv.notify_all()
 
     def join(self):
         self.thread.join()
@@ -276,9 +360,27 @@ class ShardServer:
         if self.error is not None:
             raise RuntimeError(f"shard server {self.rank} failed: {self.error!r}")
 
+    def stale_log(self):
+        """Policy ``damp`` on the GPU: the device log (host sync), else ``None``."""
+        if self.stale_dev is None:
+            return None
+        for links in (self.rx, self.tx):
+            links.synchronize()
+        self.stream.synchronize()
+        return self.stale_dev.read()
+
     def stats(self) -> dict:
         st = self.staleness
-        return {"shard_version": self.version, "shard_applied": self.applied.value(),
+        with self.lock:
+            stale = self.gate.stats()
+        if self.stale_dev is not None:
+            dev = self.stale_log()
+            stale["damped"] = dev["damped"]
+            stale["staleness_max_landed"] = dev["tau_max"]
+        else:
+            # CPU: synchronous applies; GPU without "damp": not measured
+            stale["staleness_max_landed"] = None if self.cuda else (max(st) if st else 0)
+        return {**stale, "shard_version": self.version, "shard_applied": self.applied.value(),
                 "shard_counts": dict(self.counts),
                 "shard_links": dict(self.rx.counts, sends=self.tx.counts["send"],
                                     send_reused=self.tx.counts["reused"]),
@@ -308,12 +410,17 @@ class _ShardedPull:
 class AsyncShardedPSClient(PSClient):
     """Worker side of the non-lock-step sharded PS (one :class:`ShardServer` per rank)."""
 
-    def __init__(self, group=None, delta_scale: str | float = "sum", **kw):
+    def __init__(self, group=None, delta_scale: str | float = "sum", stale_bound: int = 0,
+                 stale_policy: str = "off", **kw):
         """``delta_scale``: ``"sum"`` adds every worker's delta as a Downpour PS
-        does; ``"mean"`` scales each delta by 1/world; a float is used as is."""
+        does; ``"mean"`` scales each delta by 1/world; a float is used as is.
+        ``stale_policy`` / ``stale_bound``: every shard server's staleness bound
+        (:mod:`.staleness`)."""
         super().__init__(**kw)
+        check_policy(stale_policy, stale_bound)
         self.group = group
         self.delta_scale = delta_scale
+        self.stale_bound, self.stale_policy = stale_bound, stale_policy
         self.shard_versions: list[int] = []
 
     def init(self):
@@ -348,7 +455,8 @@ class AsyncShardedPSClient(PSClient):
         self.server = ShardServer(
             self.rank, self.world, self.arena.p32.detach()[lo: lo + self.shard_n], self.req,
             {k: g for k, g in push.items() if k[1] == self.rank},
-            {k: g for k, g in reply.items() if k[0] == self.rank}, scale).start()
+            {k: g for k, g in reply.items() if k[0] == self.rank}, scale,
+            stale_bound=self.stale_bound, stale_policy=self.stale_policy).start()
         self._pull_free: deque = deque()      # reusable reply staging sets (+ free event)
         self._push_work: list = [[], []]      # per hand-off slot: payload sends
         self.side = torch.cuda.Stream(self.device) if self.cuda else None
@@ -467,6 +575,7 @@ class AsyncShardedPSClient(PSClient):
             if o != self.rank:
                 M.send_message(M.MessageCode.Shutdown, None, o, group=self.req)
         M.SENDS.drain()
+        self.server.leave(self.rank)           # this worker pushes no more
         self.server.join()                     # returns once every rank has shut down
         if self.cuda:
             torch.cuda.current_stream().wait_stream(self.server.stream)
@@ -486,7 +595,7 @@ class AsyncShardedPSClient(PSClient):
         return self.server.master
 
     def state_dict(self) -> dict:
-        snap, v, ev = self.server.snapshot()
+        snap, v, ev = self.server.snapshot(gated=False)
         if ev is not None:
             ev.synchronize()
         return {"kind": "sharded_async", "rank": self.rank, "world": self.world,

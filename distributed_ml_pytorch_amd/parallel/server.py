@@ -44,6 +44,7 @@ import torch.distributed as dist
 from . import messaging as M
 from .arena import FlatArena
 from .links import AppliedCount, PairGroupTransport, PairLinks, wait_on
+from .staleness import DeviceStaleLog, StalenessGate
 
 _LOG = logging.getLogger(__name__)
 
@@ -73,18 +74,26 @@ class ParameterServer:
                  pair_groups=None, payload: str = "auto", device=None, init_policy: str = "first",
                  checkpoint_path: str | None = None, checkpoint_every: int = 0,
                  worker_timeout: float | None = None, delta_scale: str | float = "sum",
-                 transport=None, trace_links: bool = False):
+                 transport=None, trace_links: bool = False, stale_bound: int = 0,
+                 stale_policy: str = "off"):
         """``delta_scale``: factor on every pushed delta -- ``"sum"`` (1.0, the
         reference Downpour PS: /root/reference/asgd/optim/Asynchronous.py:48-55
         ships raw accumulated updates that the PS adds), ``"mean"`` (1 / #workers:
         the W workers' concurrent deltas average instead of adding up, which keeps
-        many-worker runs stable; profiles/ttl_n8_delta_scale_r2.txt), or a float."""
+        many-worker runs stable; profiles/ttl_n8_delta_scale_r2.txt), or a float.
+
+        ``stale_policy`` / ``stale_bound``: the version-based staleness bound
+        (:mod:`.staleness`): ``"block"`` defers a worker's pulls while its push
+        clock is more than ``stale_bound`` ahead of the slowest active worker,
+        ``"damp"`` scales a push more than ``stale_bound`` versions stale by
+        ``1 / (1 + tau - stale_bound)``; ``"off"`` (default) only keeps the clocks."""
         if not dist.is_initialized():
             raise RuntimeError("ParameterServer needs torch.distributed to be initialised")
         self.rank = dist.get_rank()
         world = dist.get_world_size()
         self.workers = list(workers) if workers is not None else [
             r for r in range(world) if r != self.rank]
+        self.gate = StalenessGate(self.workers, stale_bound, stale_policy)
         if delta_scale == "sum":
             self.delta_scale = 1.0
         elif delta_scale == "mean":
@@ -157,6 +166,12 @@ class ParameterServer:
         # applies wholly landed: the version a reply is stamped with (links.AppliedCount);
         # self.version stays the host's ENQUEUE count (staleness of incoming pushes)
         self.applied = AppliedCount(self.device, self._native)
+        # policy "damp" on the GPU: the factor of every apply comes from the device
+        # count, on the applying stream (one slot per link stream + the apply stream)
+        self.stale_dev = None
+        if self._native is not None and stale_policy == "damp":
+            self.stale_dev = DeviceStaleLog(self.device, self._native, self.applied,
+                                            stale_bound, keys=[*self.workers, None])
         if self.links is not None:
             self._warm_kernels(padded)
 
@@ -171,6 +186,14 @@ class ParameterServer:
                 z = torch.zeros(padded, dtype=dt, device=self.device)
                 self._native.ps_apply(self.shard, z, None, self.delta_scale)
                 self._native.ps_apply(self.shard, z, None, self.delta_scale, True)
+                if self.stale_dev is not None:
+                    one = torch.ones(2, device=self.device)
+                    self._native.ps_apply(self.shard, z, None, self.delta_scale, False, one)
+                    self._native.ps_apply(self.shard, z, None, self.delta_scale, True, one)
+            if self.stale_dev is not None:
+                # a log of its own: the warm-up launch is no apply
+                warm = DeviceStaleLog(self.device, self._native, self.applied, 0)
+                warm.factor(None, 0)
             snap = torch.empty(self.numel + 1, dtype=torch.float32, device=self.device)
             self._native.ps_count(self.applied.dev, 0)
             self._native.ps_stamp(self.applied.dev, snap[self.numel:])
@@ -221,17 +244,32 @@ class ParameterServer:
             self.links.send(dst, n + 1, torch.float32, fill, s)
         else:
             snap = torch.empty(n + 1, dtype=torch.float32)
+            if self.stream is not None:
+                # a device shard behind gloo payloads: the applies run on the apply
+                # stream; once it has drained the host count is what has landed
+                self.stream.synchronize()
+                snap[n] = float(self.applied.host)
+            else:
+                self.applied.stamp(snap[n:])     # gloo: applies are synchronous
             snap[:n].copy_(self.shard[:n])
-            self.applied.stamp(snap[n:])     # gloo: applies are synchronous
             w = dist.isend(snap, dst, group=self.ctrl, tag=M.TAG_REPLY)
             self._tracker.add(w, snap)
         self.bytes_out += (n + 1) * 4
 
-    def _apply(self, delta: torch.Tensor, ready=None, slot=None, sender: int | None = None):
+    def _apply(self, delta: torch.Tensor, ready=None, slot=None, sender: int | None = None,
+               base: int | None = None):
         """``shard += scale * delta``.  Device links: on the SENDER's link stream,
         right behind its receive (``ready`` is on that stream), with fp32 atomics
         so concurrent applies of different workers all land, releasing the receive
-        ``slot`` when done.  Otherwise on the apply stream after ``ready``."""
+        ``slot`` when done.  Otherwise on the apply stream after ``ready``.
+
+        ``base``: the version in the push header.  Policy ``damp`` scales the delta
+        by the staleness factor of ``count - base``: the device count, read on the
+        applying stream right before the apply (GPU), or the host count (CPU)."""
+        damp = base is not None and self.gate.policy == "damp"
+        tau = self.version - base if base is not None else 0
+        if damp and self.stale_dev is not None:
+            return self._apply_damped(delta, ready, slot, sender, base, tau)
         if self._native is not None and self.links is not None and sender is not None:
             s = self.links.stream(sender)
             with torch.cuda.stream(s):
@@ -250,9 +288,30 @@ class ParameterServer:
                 if slot is not None:
                     self.links.release(slot, self.stream)
         else:
+            f = self.gate.note_push(sender, tau) if base is not None else 1.0
             self.shard[: self.numel].add_(delta[: self.numel].to(torch.float32),
-                                          alpha=self.delta_scale)
+                                          alpha=self.delta_scale * f)
             self.applied.bump()
+        self.version += 1
+
+    def _apply_damped(self, delta, ready, slot, sender, base: int, tau_host: int):
+        """Policy ``damp`` on the GPU: ``ps_stale_factor`` then the factor-aware
+        apply, both on the applying stream (the sender's link stream, atomics; or
+        the apply stream).  No host sync: the factor never reaches the host here."""
+        links = self.links is not None and sender is not None
+        s = self.links.stream(sender) if links else self.stream
+        with torch.cuda.stream(s):
+            wait_on(s, ready)
+            if links:
+                wait_on(s, self._init_ev)
+            fac = self.stale_dev.factor(sender if links else None, base, cap=self.version)
+            self._native.ps_apply(self.shard, delta, None, self.delta_scale, links, fac)
+            self.applied.bump()
+            if slot is not None:
+                self.links.release(slot, s)
+        if links:
+            self._touched_on.add(sender)
+        self.gate.log.append((sender, tau_host, None))   # the factor is on the device
         self.version += 1
 
     def _set(self, params: torch.Tensor, ready=None, slot=None, version: int | None = None):
@@ -281,7 +340,8 @@ class ParameterServer:
         if code == M.MessageCode.GradientUpdate:
             delta, ready, slot = self._recv_payload(sender, nelem, dtype)
             self.staleness.append(self.version - version)
-            self._apply(delta, ready, slot, sender)
+            self._apply(delta, ready, slot, sender, base=version)
+            self._answer(self.gate.on_push(sender))
             if self.checkpoint_every and self.version % self.checkpoint_every == 0:
                 self.save_checkpoint()
         elif code == M.MessageCode.ParameterUpdate:
@@ -292,22 +352,38 @@ class ParameterServer:
             elif slot is not None:
                 slot.free = ready        # never read: free once it has arrived
         elif code == M.MessageCode.ParameterRequest:
-            self._reply(sender)
+            # policy "block": deferred while the sender is too far ahead (queued in
+            # the gate, answered by a later push / shutdown / drop, or by finish())
+            if self.gate.on_request(sender):
+                self._reply(sender)
         elif code == M.MessageCode.Checkpoint:
             self.save_checkpoint()
         elif code == M.MessageCode.Heartbeat:
             pass
+
+    def _answer(self, released):
+        for w, _ in released:
+            self._reply(w)
+
+    def leave(self, worker: int):
+        """``worker`` shut down or was dropped: it no longer holds others back."""
+        self._answer(self.gate.leave(worker))
 
     def _check_liveness(self, alive: set):
         if not self.worker_timeout:
             return
         now = time.monotonic()
         for w in list(alive):
+            if self.gate.waiting(w):
+                # silent because its pull is deferred: it waits on the PS
+                self.last_seen[w] = now
+                continue
             if now - self.last_seen[w] > self.worker_timeout:
                 _LOG.warning("PS: worker %d silent for %.1fs, dropping", w,
                              now - self.last_seen[w])
                 alive.discard(w)
                 self.dropped.append(w)
+                self.leave(w)
 
     def _header_pump(self, q):
         """Receive thread: any-source headers into ``q`` until every worker has
@@ -365,6 +441,7 @@ class ParameterServer:
             code, sender, step, version, nelem, dtype = hdr
             if code == M.MessageCode.Shutdown:
                 alive.discard(sender)
+                self.leave(sender)
                 continue
             self.handle(code, sender, step, version, nelem, dtype)
             self._check_liveness(alive)
@@ -372,6 +449,7 @@ class ParameterServer:
         return self.stats()
 
     def finish(self):
+        self._answer(self.gate.drain())     # nobody is left waiting for a reply
         self._tracker.drain()
         self._sync_device()
         if self.checkpoint_path:
@@ -389,9 +467,27 @@ class ParameterServer:
         self._sync_device()
         return self.shard[: self.numel]
 
+    def stale_log(self):
+        """Policy ``damp`` on the GPU: the device log (host sync), else ``None``."""
+        if self.stale_dev is None:
+            return None
+        self._sync_device()
+        return self.stale_dev.read()
+
     def stats(self) -> dict:
         st = self.staleness
+        stale = self.gate.stats()
+        if self.stale_dev is not None:
+            # damp on the GPU: what the device measured when each factor was formed
+            dev = self.stale_log()
+            stale["damped"] = dev["damped"]
+            stale["staleness_max_landed"] = dev["tau_max"]
+        elif self._native is None:
+            stale["staleness_max_landed"] = max(st) if st else 0   # synchronous applies
+        else:
+            stale["staleness_max_landed"] = None    # GPU without "damp": not measured
         return {
+            **stale,
             "version": self.version,
             "applied": self.applied.value(),
             "counts": dict(self.counts),

@@ -38,6 +38,7 @@ from ..parallel.async_sharded import AsyncShardedPSClient
 from ..parallel.clients import (GlooPSClient, LocalPSClient, RcclPSClient, ShardedPSClient)
 from ..parallel.ddp import BucketedAllReduce, FusedSGD
 from ..parallel.server import ParameterServer, make_ps_groups
+from ..parallel.staleness import check_policy
 from ..utils import checkpoint as ckpt
 from ..utils.data import get_datasets, make_loaders
 from ..utils.metrics import IterationLog, StepTimer, Throughput, classification_report
@@ -87,6 +88,8 @@ class TrainConfig:
     ps_resume: str | None = None      # explicit PS checkpoint (overrides <base> for the PS)
     delta_scale: str = "sum"          # PS push combine: "sum" (Downpour PS semantics) | "mean" | float
     ps_worker_timeout: float = 0.0    # central PS: drop a worker silent this long (0 = never)
+    stale_bound: int = 0              # S of the version-based staleness bound (parallel/staleness.py)
+    stale_policy: str = "off"         # off | damp | block (central and sharded_async PS only)
     bucket_mb: float = 0.0            # sync-DP all-reduce bucket; <= 0: measured (ddp.py)
     label_smoothing: float = 0.0
     divergence_check: bool = True     # halt on non-finite parameters at each log interval
@@ -108,6 +111,7 @@ class Worker:
         :class:`~..parallel.clients.SharedPSClient` of the virtual-worker runner)."""
         self.cfg = cfg
         self.info = info
+        check_stale_config(cfg, info)
         if cfg.deterministic:
             cfg = self.cfg = enable_determinism(cfg)
         torch.manual_seed(cfg.seed + info.rank)
@@ -178,7 +182,9 @@ class Worker:
         if cfg.ps == "sharded":
             return ShardedPSClient(delta_scale=cfg.delta_scale, **kw)
         if cfg.ps == "sharded_async":
-            return AsyncShardedPSClient(delta_scale=cfg.delta_scale, **kw)
+            return AsyncShardedPSClient(delta_scale=cfg.delta_scale,
+                                        stale_bound=cfg.stale_bound,
+                                        stale_policy=cfg.stale_policy, **kw)
         if cfg.ps == "central":
             ctrl, pairs = ps_groups if ps_groups is not None else (None, {})
             if pairs and self.device.type == "cuda" and _payload(cfg, info) == "rccl":
@@ -380,6 +386,24 @@ class Worker:
             self.opt.finish()
 
 
+def check_stale_config(cfg: TrainConfig, info: DistInfo):
+    """The staleness bound is enforced by a PS that serves workers one by one
+    (central, sharded_async).  Asking for it anywhere else is an error at
+    start-up, never silently ignored."""
+    check_policy(cfg.stale_policy, cfg.stale_bound)
+    if cfg.stale_policy == "off":
+        return
+    enforced = cfg.mode == "asgd" and info.is_distributed and \
+        cfg.ps in ("central", "sharded_async")
+    if not enforced:
+        what = f"--mode {cfg.mode}" if cfg.mode != "asgd" else (
+            f"--ps {cfg.ps}" if info.is_distributed else "a single-process run (local PS)")
+        raise ValueError(
+            f"--stale-policy {cfg.stale_policy} cannot be enforced with {what}: only the "
+            "central PS and --ps sharded_async serve pulls and applies per worker "
+            "(the local PS has one worker, the collective sharded PS is lock-step)")
+
+
 def _payload(cfg: TrainConfig, info: DistInfo) -> str:
     if cfg.payload != "auto":
         return cfg.payload
@@ -397,7 +421,8 @@ def run_server(cfg: TrainConfig, info: DistInfo, ps_groups):
                              checkpoint_path=cfg.checkpoint,
                              checkpoint_every=cfg.checkpoint_every,
                              worker_timeout=cfg.ps_worker_timeout or None,
-                             delta_scale=cfg.delta_scale)
+                             delta_scale=cfg.delta_scale, stale_bound=cfg.stale_bound,
+                             stale_policy=cfg.stale_policy)
     ps_path = _ps_resume_path(cfg)
     if ps_path:
         server.load_checkpoint(ps_path)
@@ -411,6 +436,7 @@ def run_server(cfg: TrainConfig, info: DistInfo, ps_groups):
 
 def run_training(cfg: TrainConfig, info: DistInfo):
     """Entry point for every rank. Returns a result dict (worker) or PS stats."""
+    check_stale_config(cfg, info)
     ps_groups = None
     central = cfg.mode == "asgd" and cfg.ps == "central" and info.is_distributed
     if central:
