@@ -55,7 +55,20 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--momentum", type=float, default=0.0)
     p.add_argument("--weight-decay", type=float, default=0.0)
-    p.add_argument("--lr-schedule", default="constant", choices=["constant", "inv_epoch"])
+    p.add_argument("--lr-schedule", default="constant",
+                   choices=["constant", "inv_epoch", "warmup_cosine"],
+                   help="inv_epoch: lr / (epoch + 1) per epoch (host); warmup_cosine: linear "
+                        "warm-up then cosine decay to --lr-min, per step on the device")
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"])
+    p.add_argument("--beta1", type=float, default=0.9)
+    p.add_argument("--beta2", type=float, default=0.999)
+    p.add_argument("--adam-eps", type=float, default=1e-8)
+    p.add_argument("--clip-grad-norm", type=float, default=0.0, metavar="MAX",
+                   help="clip the global gradient norm to MAX (0 = off)")
+    p.add_argument("--warmup-steps", type=int, default=0)
+    p.add_argument("--lr-min", type=float, default=0.0)
+    p.add_argument("--schedule-steps", type=int, default=None,
+                   help="length of warmup_cosine (default: --max-steps, or epochs x batches)")
     p.add_argument("--max-steps", type=int, default=None)
     p.add_argument("--bucket-mb", type=float, default=0.0,
                    help="sync-DP all-reduce bucket (MB); 0 = measured on the group at start-up")
@@ -106,7 +119,9 @@ def config_from_args(a) -> TrainConfig:
         ps_worker_timeout=a.ps_worker_timeout, stale_bound=a.stale_bound,
         stale_policy=a.stale_policy, bucket_mb=a.bucket_mb,
         label_smoothing=a.label_smoothing, divergence_check=not a.no_divergence_check,
-        deterministic=a.deterministic)
+        deterministic=a.deterministic, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
+        adam_eps=a.adam_eps, clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,
+        lr_min=a.lr_min, schedule_steps=a.schedule_steps)
 
 
 def main(argv=None):

@@ -71,6 +71,82 @@ void asgd_fused_step(Tensor g, Tensor p, optional<Tensor> acc, optional<Tensor> 
                               cur_stream());
 }
 
+// Hyper block of one optimizer (optim.hip): optim_hyper_words() fp32 words on
+// the arena's device
+void check_hyper(const Tensor& hyper, const Tensor& like) {
+  TORCH_CHECK(hyper.is_cuda() && hyper.scalar_type() == at::kFloat && hyper.is_contiguous() &&
+                  hyper.numel() == dmp::optim_hyper_words() && hyper.device() == like.device(),
+              "hyper block must be a contiguous fp32 tensor of optim_hyper_words() elements on "
+              "the parameters' device");
+}
+
+// One optimizer step of the hyper block on the current stream.  `g` + `partials`
+// (a persistent 1024-element fp32 buffer) given: clipping on, the gradient norm
+// is taken first; both None: no norm launch.
+void optim_hyper(Tensor hyper, optional<Tensor> g, optional<Tensor> partials) {
+  check_hyper(hyper, hyper);
+  TORCH_CHECK(g.has_value() == partials.has_value(),
+              "optim_hyper: pass the gradient and the partials buffer together");
+  int64_t n = 0;
+  if (g) {
+    n = g->numel();
+    TORCH_CHECK(n % 4 == 0, "flat arena length must be a multiple of 4");
+    check_flat(*g, at::kFloat, n, "g");
+    check_flat(*partials, at::kFloat, 1024, "partials");
+    TORCH_CHECK(g->device() == hyper.device() && partials->device() == hyper.device(),
+                "optim_hyper: g, partials and the hyper block must share a device");
+  }
+  dmp::launch_optim_hyper(hyper.data_ptr<float>(), ptr_or_null<const float>(g),
+                          ptr_or_null<float>(partials), n, cur_stream());
+}
+
+void asgd_fused_step_dev(Tensor g, Tensor p, optional<Tensor> acc, optional<Tensor> mom,
+                         optional<Tensor> w16, Tensor hyper, double wd, double momentum,
+                         double dampening, bool nesterov) {
+  const int64_t n = p.numel();
+  TORCH_CHECK(n % 4 == 0, "flat arena length must be a multiple of 4");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat(g, at::kFloat, n, "g");
+  if (acc) check_flat(*acc, at::kFloat, n, "acc");
+  if (mom) check_flat(*mom, at::kFloat, n, "mom");
+  if (w16) check_flat(*w16, at::kBFloat16, n, "w16");
+  check_hyper(hyper, p);
+  TORCH_CHECK(g.device() == p.device(), "g and p must share a device");
+  dmp::launch_asgd_fused_step_dev(g.data_ptr<float>(), p.data_ptr<float>(),
+                                  ptr_or_null<float>(acc), ptr_or_null<float>(mom),
+                                  ptr_or_null<uint16_t>(w16), n, hyper.data_ptr<float>(),
+                                  (float)wd, (float)momentum, (float)dampening, nesterov,
+                                  cur_stream());
+}
+
+// `decay`: uint8 mask, one entry per 64-element arena block (None: decay all)
+void adamw_fused_step(Tensor g, Tensor p, optional<Tensor> acc, Tensor m, Tensor v,
+                      optional<Tensor> w16, optional<Tensor> decay, Tensor hyper, double wd,
+                      double eps) {
+  const int64_t n = p.numel();
+  TORCH_CHECK(n % 4 == 0, "flat arena length must be a multiple of 4");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat(g, at::kFloat, n, "g");
+  check_flat(m, at::kFloat, n, "m");
+  check_flat(v, at::kFloat, n, "v");
+  if (acc) check_flat(*acc, at::kFloat, n, "acc");
+  if (w16) check_flat(*w16, at::kBFloat16, n, "w16");
+  check_hyper(hyper, p);
+  TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device(),
+              "g, p, m and v must share a device");
+  if (decay) {
+    TORCH_CHECK(n % 64 == 0, "a decay mask needs an arena length that is a multiple of 64");
+    TORCH_CHECK(decay->is_cuda() && decay->scalar_type() == at::kByte && decay->is_contiguous() &&
+                    decay->numel() == n / 64 && decay->device() == p.device(),
+                "decay mask must be a contiguous uint8 tensor of n / 64 elements on the "
+                "parameters' device");
+  }
+  dmp::launch_adamw_fused_step(g.data_ptr<float>(), p.data_ptr<float>(), ptr_or_null<float>(acc),
+                               m.data_ptr<float>(), v.data_ptr<float>(),
+                               ptr_or_null<uint16_t>(w16), ptr_or_null<const uint8_t>(decay), n,
+                               hyper.data_ptr<float>(), (float)wd, (float)eps, cur_stream());
+}
+
 // `factor`: the {factor, tau} slot ps_stale_factor wrote on the current stream
 // (staleness damping: scale * factor is applied); None = the plain apply
 void ps_apply(Tensor shard, Tensor delta, optional<Tensor> mirror, double scale, bool atomic,
@@ -1783,6 +1859,12 @@ PYBIND11_MODULE(_native, m) {
         py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("stride"), py::arg("pad"));
   m.doc() = "gfx950 (MI355X) HIP kernels for distributed_ml_pytorch_amd";
   m.def("asgd_fused_step", &asgd_fused_step, "fused flat ASGD/SGD update");
+  m.def("optim_hyper_words", []() { return dmp::optim_hyper_words(); },
+        "fp32 words of an optimizer's device-resident hyper block");
+  m.def("optim_hyper", &optim_hyper, "advance a hyper block one step (norm, clip, schedule)");
+  m.def("asgd_fused_step_dev", &asgd_fused_step_dev,
+        "fused flat ASGD/SGD update, lr and gradient scale from the hyper block");
+  m.def("adamw_fused_step", &adamw_fused_step, "fused flat AdamW update");
   m.def("gemm_sk_pieces",
         [](int64_t cfg, int64_t M, int64_t N, int64_t K, int64_t splits) {
           long long wf = 0;

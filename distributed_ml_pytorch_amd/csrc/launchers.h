@@ -11,6 +11,18 @@ namespace dmp {
 void launch_asgd_fused_step(const float* g, float* p, float* acc, float* mom, uint16_t* w16,
                             long long n, float lr, float wd, float momentum, float dampening,
                             bool nesterov, hipStream_t s);
+// Device-resident optimizer state (optim.hip "hyper block", optim_hyper_words()
+// fp32/int32 words): launch_optim_hyper advances it by one step (`partial`
+// non-null: grad-norm pass over g first, for clipping); the two step launchers
+// read lr / gradient scale / bias corrections from it.
+int optim_hyper_words();
+void launch_optim_hyper(float* hyper, const float* g, float* partial, long long n, hipStream_t s);
+void launch_asgd_fused_step_dev(const float* g, float* p, float* acc, float* mom, uint16_t* w16,
+                                long long n, const float* hyper, float wd, float momentum,
+                                float dampening, bool nesterov, hipStream_t s);
+void launch_adamw_fused_step(const float* g, float* p, float* acc, float* m, float* v,
+                             uint16_t* w16, const uint8_t* decay, long long n, const float* hyper,
+                             float wd, float eps, hipStream_t s);
 // `factor`: one device fp32 published by launch_ps_stale_factor on the same
 // stream (staleness damping); null = the plain apply
 void launch_ps_apply_atomic(float* shard, const void* delta, bool bf16, long long n, float scale,

@@ -18,19 +18,24 @@
 
 namespace dmp {
 
-// g      : fp32 gradient (flat)         [n]
-// p      : fp32 worker parameters       [n]   (in/out)
-// acc    : fp32 push accumulator        [n]   (in/out, may be null)
-// mom    : fp32 momentum buffer         [n]   (in/out, may be null)
-// w16    : bf16 compute shadow of p     [n]   (out, may be null)
-__global__ void __launch_bounds__(256) asgd_fused_step_kernel(
+// One grid-stride pass of the SGD update, shared by the two kernels below.
+// `gscale` (device-hyper variant only, SCALE = true) multiplies the gradient
+// before weight decay and momentum see it; __fmul_rn keeps that product out of
+// FMA contraction, so gscale == 1 leaves every later rounding where the
+// by-value kernel has it (bitwise-equal results).
+template <bool SCALE>
+__device__ __forceinline__ void asgd_fused_step_body(
     const float4* __restrict__ g, float4* __restrict__ p, float4* __restrict__ acc,
-    float4* __restrict__ mom, bf16x4* __restrict__ w16, long long n4, float lr,
-    float weight_decay, float momentum, float dampening, int nesterov) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4* __restrict__ mom, bf16x4* __restrict__ w16, long long n4, float lr, float gscale,
+    float weight_decay, float momentum, float dampening, int nesterov, long long first,
+    long long stride) {
+  for (long long i = first; i < n4; i += stride) {
     float4 gv = g[i];
     float4 pv = p[i];
+    if (SCALE) {
+      gv.x = __fmul_rn(gscale, gv.x); gv.y = __fmul_rn(gscale, gv.y);
+      gv.z = __fmul_rn(gscale, gv.z); gv.w = __fmul_rn(gscale, gv.w);
+    }
     if (weight_decay != 0.f) {
       gv.x += weight_decay * pv.x; gv.y += weight_decay * pv.y;
       gv.z += weight_decay * pv.z; gv.w += weight_decay * pv.w;
@@ -59,6 +64,175 @@ __global__ void __launch_bounds__(256) asgd_fused_step_kernel(
     if (w16) {
       bf16x4 o;
       o.v[0] = f2bf(pv.x); o.v[1] = f2bf(pv.y); o.v[2] = f2bf(pv.z); o.v[3] = f2bf(pv.w);
+      w16[i] = o;
+    }
+  }
+}
+
+// g      : fp32 gradient (flat)         [n]
+// p      : fp32 worker parameters       [n]   (in/out)
+// acc    : fp32 push accumulator        [n]   (in/out, may be null)
+// mom    : fp32 momentum buffer         [n]   (in/out, may be null)
+// w16    : bf16 compute shadow of p     [n]   (out, may be null)
+__global__ void __launch_bounds__(256) asgd_fused_step_kernel(
+    const float4* __restrict__ g, float4* __restrict__ p, float4* __restrict__ acc,
+    float4* __restrict__ mom, bf16x4* __restrict__ w16, long long n4, float lr,
+    float weight_decay, float momentum, float dampening, int nesterov) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  asgd_fused_step_body<false>(g, p, acc, mom, w16, n4, lr, 1.f, weight_decay, momentum,
+                              dampening, nesterov,
+                              (long long)blockIdx.x * blockDim.x + threadIdx.x, stride);
+}
+
+// ---- device-resident optimizer state ("hyper block") ------------------------
+// One small fp32 / int32 buffer per optimizer holds everything about a step
+// that changes from step to step, so a captured step graph bakes none of it
+// in (the pattern of dropout.hip's device-side Philox offset).  Words:
+enum HyperWord {
+  kHStep = 0,       // int32  t: updates applied so far
+  kHLr = 1,         // lr_t of the current step
+  kHGscale = 2,     // grad_scale * clip coefficient
+  kHBc1 = 3,        // 1 - beta1^t
+  kHBc2 = 4,        // 1 - beta2^t
+  kHNorm = 5,       // grad_scale * ||g||  (0 with clipping off)
+  kHKind = 6,       // int32  0 constant, 1 warmup_cosine
+  kHBaseLr = 7,
+  kHLrMin = 8,
+  kHWarmup = 9,     // int32
+  kHTotal = 10,     // int32
+  kHBeta1 = 11,
+  kHBeta2 = 12,
+  kHMaxNorm = 13,   // <= 0: clipping off
+  kHGradScale = 14,
+  kHOmb1 = 15,      // 1 - beta1, rounded from the host's double (as torch passes it)
+  kHOmb2 = 16,      // 1 - beta2
+  kHyperWords = 20,
+};
+
+__device__ __forceinline__ float hyper_load(const float* hyper, int w) {
+  return __hip_atomic_load(hyper + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One block, once per step, on the step's stream BEFORE the update kernel.
+//   1. clipping on (nparts > 0): reduce the per-block partials that
+//      sumsq_partial_kernel just wrote, in a fixed order (thread t takes
+//      partials t, t+256, ...; then a fixed LDS tree), so the norm is a pure
+//      function of the gradient;  norm = grad_scale * sqrt(sum)
+//   2. clip = min(1, max_norm / (norm + 1e-6))  (torch clip_grad_norm_; a NaN
+//      norm stays NaN, an infinite one gives 0 and 0 * inf = NaN downstream)
+//   3. t += 1, lr_t from the schedule, bias corrections.
+// The scalar part runs on one thread in fp64 (cos / pow once per step): the
+// published fp32 values are then correctly rounded up to the fp32 inputs.
+__global__ void __launch_bounds__(256) optim_hyper_kernel(float* __restrict__ hyper,
+                                                          const float* __restrict__ partial,
+                                                          int nparts) {
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  if (nparts > 0) {
+    double s = 0.0;
+    for (int i = tid; i < nparts; i += 256) s += (double)partial[i];
+    red[tid] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+      if (tid < o) red[tid] += red[tid + o];
+      __syncthreads();
+    }
+  }
+  if (tid != 0) return;
+  int* hi = reinterpret_cast<int*>(hyper);
+  const float gs = hyper[kHGradScale];
+  const float max_norm = hyper[kHMaxNorm];
+  float norm = 0.f, clip = 1.f;
+  if (nparts > 0 && max_norm > 0.f) {
+    norm = gs * sqrtf((float)red[0]);
+    const float c = max_norm / (norm + 1e-6f);
+    clip = c < 1.f ? c : (c != c ? c : 1.f);
+  }
+  const int t = hi[kHStep] + 1;
+  const double base = (double)hyper[kHBaseLr], lmin = (double)hyper[kHLrMin];
+  const int warm = hi[kHWarmup], total = hi[kHTotal];
+  double lr = base;
+  if (hi[kHKind] == 1) {
+    if (t <= warm) lr = base * (double)t / (double)warm;
+    else if (t >= total) lr = lmin;
+    else lr = lmin + 0.5 * (base - lmin) *
+                  (1.0 + cos(3.14159265358979323846 * (double)(t - warm) / (double)(total - warm)));
+  }
+  const double b1 = 1.0 - (double)hyper[kHOmb1], b2 = 1.0 - (double)hyper[kHOmb2];
+  hi[kHStep] = t;
+  hyper[kHLr] = (float)lr;
+  hyper[kHGscale] = gs * clip;
+  hyper[kHBc1] = (float)(1.0 - pow(b1, (double)t));
+  hyper[kHBc2] = (float)(1.0 - pow(b2, (double)t));
+  hyper[kHNorm] = norm;
+}
+
+// SGD with lr and the gradient scale read from the hyper block (schedules and
+// clipping for the SGD paths); otherwise asgd_fused_step_kernel.
+__global__ void __launch_bounds__(256) asgd_fused_step_dev_kernel(
+    const float4* __restrict__ g, float4* __restrict__ p, float4* __restrict__ acc,
+    float4* __restrict__ mom, bf16x4* __restrict__ w16, long long n4,
+    const float* __restrict__ hyper, float weight_decay, float momentum, float dampening,
+    int nesterov) {
+  const float lr = hyper_load(hyper, kHLr);
+  const float gscale = hyper_load(hyper, kHGscale);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  asgd_fused_step_body<true>(g, p, acc, mom, w16, n4, lr, gscale, weight_decay, momentum,
+                             dampening, nesterov,
+                             (long long)blockIdx.x * blockDim.x + threadIdx.x, stride);
+}
+
+// AdamW (torch.optim.AdamW's form) in one pass over the flat arena:
+//   g' = gscale * g;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2
+//   p  = p (1 - lr wd decay) - (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)
+//   acc += p_new - p_old   (the Downpour push carries the applied update,
+//                           weight decay included)
+// decay : one uint8 per 64-element arena block (every parameter starts on a
+//         64-element boundary, so a float4 never straddles two blocks);
+//         null = decay everything.
+// Division and square root are the correctly rounded ones: the pass moves
+// ~38 B per element and has the VALU time to spare.
+__global__ void __launch_bounds__(256) adamw_fused_step_kernel(
+    const float4* __restrict__ g, float4* __restrict__ p, float4* __restrict__ acc,
+    float4* __restrict__ m, float4* __restrict__ v, bf16x4* __restrict__ w16,
+    const u8* __restrict__ decay, long long n4, const float* __restrict__ hyper,
+    float weight_decay, float eps) {
+  const float lr = hyper_load(hyper, kHLr);
+  const float gscale = hyper_load(hyper, kHGscale);
+  const float b1 = hyper_load(hyper, kHBeta1), b2 = hyper_load(hyper, kHBeta2);
+  const float omb1 = hyper_load(hyper, kHOmb1), omb2 = hyper_load(hyper, kHOmb2);
+  const float step = lr / hyper_load(hyper, kHBc1);
+  const float sbc2 = sqrtf(hyper_load(hyper, kHBc2));
+  // once per thread, in fp64: 1 - lr wd sits next to 1, where an fp32 product
+  // would cost an ulp of p on every step
+  const float keep = (float)(1.0 - (double)lr * (double)weight_decay);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4 gv = g[i];
+    const float4 p0 = p[i];
+    float4 mv = m[i], vv = v[i];
+    const float k = (!decay || decay[i >> 4]) ? keep : 1.f;
+    float4 pn;
+#define DMP_ADAMW_LANE(c)                                        \
+    {                                                            \
+      const float gs = gscale * gv.c;                            \
+      mv.c = b1 * mv.c + omb1 * gs;                              \
+      vv.c = b2 * vv.c + omb2 * (gs * gs);                       \
+      pn.c = p0.c * k - step * (mv.c / (sqrtf(vv.c) / sbc2 + eps)); \
+    }
+    DMP_ADAMW_LANE(x) DMP_ADAMW_LANE(y) DMP_ADAMW_LANE(z) DMP_ADAMW_LANE(w)
+#undef DMP_ADAMW_LANE
+    m[i] = mv;
+    v[i] = vv;
+    p[i] = pn;
+    if (acc) {
+      float4 a = acc[i];
+      a.x += pn.x - p0.x; a.y += pn.y - p0.y; a.z += pn.z - p0.z; a.w += pn.w - p0.w;
+      acc[i] = a;
+    }
+    if (w16) {
+      bf16x4 o;
+      o.v[0] = f2bf(pn.x); o.v[1] = f2bf(pn.y); o.v[2] = f2bf(pn.z); o.v[3] = f2bf(pn.w);
       w16[i] = o;
     }
   }
@@ -329,6 +503,36 @@ void launch_asgd_fused_step(const float* g, float* p, float* acc, float* mom, u1
   hipLaunchKernelGGL(asgd_fused_step_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
                      (const float4*)g, (float4*)p, (float4*)acc, (float4*)mom, (bf16x4*)w16, n4,
                      lr, wd, momentum, dampening, nesterov ? 1 : 0);
+}
+
+int launch_sumsq_partial(const float* x, float* partial, long long n, hipStream_t s);
+
+int optim_hyper_words() { return kHyperWords; }
+
+// `partial` non-null: clipping on -- the norm pass over g, then the hyper kernel
+// reduces its partials; null: no norm launch (gscale = grad_scale exactly)
+void launch_optim_hyper(float* hyper, const float* g, float* partial, long long n, hipStream_t s) {
+  int nparts = 0;
+  if (partial) nparts = launch_sumsq_partial(g, partial, n, s);
+  hipLaunchKernelGGL(optim_hyper_kernel, dim3(1), dim3(256), 0, s, hyper, partial, nparts);
+}
+
+void launch_asgd_fused_step_dev(const float* g, float* p, float* acc, float* mom, u16* w16,
+                                long long n, const float* hyper, float wd, float momentum,
+                                float dampening, bool nesterov, hipStream_t s) {
+  const long long n4 = n / 4;
+  hipLaunchKernelGGL(asgd_fused_step_dev_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
+                     (const float4*)g, (float4*)p, (float4*)acc, (float4*)mom, (bf16x4*)w16, n4,
+                     hyper, wd, momentum, dampening, nesterov ? 1 : 0);
+}
+
+void launch_adamw_fused_step(const float* g, float* p, float* acc, float* m, float* v, u16* w16,
+                             const u8* decay, long long n, const float* hyper, float wd,
+                             float eps, hipStream_t s) {
+  const long long n4 = n / 4;
+  hipLaunchKernelGGL(adamw_fused_step_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
+                     (const float4*)g, (float4*)p, (float4*)acc, (float4*)m, (float4*)v,
+                     (bf16x4*)w16, decay, n4, hyper, wd, eps);
 }
 
 void launch_ps_apply_f32(float* shard, const float* delta, u16* mirror, long long n, float scale,

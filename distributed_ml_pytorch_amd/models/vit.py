@@ -128,6 +128,10 @@ class VisionTransformer(nn.Module):
         w = self.patch_embed.weight
         nn.init.uniform_(w, -1 / math.sqrt(w[0].numel()), 1 / math.sqrt(w[0].numel()))
 
+    def no_weight_decay(self):
+        """Parameters AdamW's weight decay skips besides the 1-D ones."""
+        return {"cls_token", "pos_embed"}
+
     def forward(self, x):
         h = self.patch_embed(x)                       # [B, N, D]
         h = DF.vit_embed(h, self.cls_token, self.pos_embed)   # cat(cls, h) + pos

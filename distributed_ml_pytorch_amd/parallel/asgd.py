@@ -27,6 +27,7 @@ from torch.optim.optimizer import Optimizer, required
 
 from .arena import attach_arena, get_arena
 from .clients import GlooPSClient, LocalPSClient, PSClient
+from .fused_optim import FusedOptimCore, sync_base_lr
 
 
 def default_client(**kw) -> PSClient:
@@ -41,13 +42,17 @@ class Asynchronous(Optimizer):
                  client: PSClient | None = None, staleness: int = 1, momentum: float = 0.0,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
                  pull_mode: str = "overwrite", wire_dtype: torch.dtype = torch.float32,
-                 shadow_dtype: torch.dtype | None | str = "auto"):
+                 shadow_dtype: torch.dtype | None | str = "auto", optimizer: str = "sgd",
+                 betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0,
+                 schedule=None):
         if lr is required or n_push is required or n_pull is required or model is required:
             raise TypeError("Asynchronous needs lr, n_push, n_pull and model")
         if lr < 0.0:
             raise ValueError(f"Invalid learning rate: {lr}")
         if int(n_push) < 1 or int(n_pull) < 1:
             raise ValueError("n_push and n_pull must be >= 1")
+        if optimizer not in ("sgd", "adamw"):
+            raise ValueError(f"unknown optimizer {optimizer!r}; 'sgd' or 'adamw'")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
                         weight_decay=weight_decay)
         super().__init__(params, defaults)
@@ -68,7 +73,16 @@ class Asynchronous(Optimizer):
         dev = arena.device
         self.acc = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
         self._mom_steps = 0
-        self.mom = torch.zeros_like(self.acc) if momentum else None
+        self.mom = torch.zeros_like(self.acc) if momentum and optimizer == "sgd" else None
+        # AdamW, clipping or a per-step schedule: the update reads lr and the
+        # gradient scale from a device-resident hyper block (fused_optim.py);
+        # plain constant-lr SGD keeps the by-value kernel
+        self.core = None
+        if optimizer == "adamw" or max_grad_norm > 0 or schedule is not None:
+            self.core = FusedOptimCore(arena, optimizer, lr, betas=betas, eps=eps,
+                                       weight_decay=weight_decay, momentum=momentum,
+                                       nesterov=nesterov, max_grad_norm=max_grad_norm,
+                                       schedule=schedule, model=model)
         self.idx = 0
         self.timer = _NO_TIMER      # a utils.metrics.StepTimer when the trainer wires one
         self.client = client if client is not None else default_client(
@@ -101,6 +115,10 @@ class Asynchronous(Optimizer):
         # first update gives exactly that
         damp = g["dampening"] if self._mom_steps > 0 else 0.0
         self._mom_steps += 1
+        if self.core is not None:
+            sync_base_lr(self.core, lr)
+            self.core.step(a, self.acc, self.mom, damp)
+            return
         if self._nat is not None:
             self._nat.asgd_fused_step(a.g32, a.p32, self.acc, self.mom, a.w16, lr,
                                       g["weight_decay"], g["momentum"], damp, g["nesterov"])

@@ -30,6 +30,7 @@ import torch.distributed as dist
 from torch.optim.optimizer import Optimizer
 
 from .arena import FlatArena
+from .fused_optim import FusedOptimCore, sync_base_lr
 
 
 _CAL_MB = (2.0, 4.0, 8.0, 16.0, 32.0, 64.0)
@@ -162,13 +163,21 @@ class FusedSGD(Optimizer):
 
     def __init__(self, params, arena: FlatArena, lr: float, momentum: float = 0.0,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
-                 grad_scale: float = 1.0):
+                 grad_scale: float = 1.0, max_grad_norm: float = 0.0, schedule=None):
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening,
                                       nesterov=nesterov, weight_decay=weight_decay))
         self.arena = arena
         self.grad_scale = grad_scale
         self.mom = torch.zeros_like(arena.p32) if momentum else None
         self._mom_steps = 0
+        # clipping or a per-step schedule: lr and the gradient scale (1/W
+        # included) come from the device-resident hyper block (fused_optim.py)
+        self.core = None
+        if max_grad_norm > 0 or schedule is not None:
+            self.core = FusedOptimCore(arena, "sgd", lr, weight_decay=weight_decay,
+                                       momentum=momentum, nesterov=nesterov,
+                                       grad_scale=grad_scale, max_grad_norm=max_grad_norm,
+                                       schedule=schedule)
         self._nat = None
         if arena.device.type == "cuda":
             from ..ops._ext import native
@@ -197,6 +206,12 @@ class FusedSGD(Optimizer):
         a = self.arena
         lr = g["lr"]
         a.bump()
+        if self.core is not None:
+            damp = g["dampening"] if self._mom_steps > 0 else 0.0
+            self._mom_steps += 1
+            sync_base_lr(self.core, lr)
+            self.core.step(a, None, self.mom, damp)
+            return
         if self.grad_scale != 1.0:
             # fold the 1/W average into lr (and rescale weight decay so wd*p is not scaled)
             lr_eff = lr * self.grad_scale
@@ -223,3 +238,45 @@ class FusedSGD(Optimizer):
             a.p32.add_(d, alpha=-lr_eff)
             if a.w16 is not None:
                 a.w16.copy_(a.p32)
+
+
+class FusedAdamW(Optimizer):
+    """AdamW over a flat arena in one fused HIP kernel (``sync`` / ``single``).
+
+    Decoupled weight decay skips 1-D parameters and the names ``model``
+    lists in ``no_weight_decay()``; ``grad_scale`` (1/world for sync DP),
+    ``max_grad_norm`` (global-norm clipping, 0 = off) and ``schedule``
+    (:class:`~.fused_optim.Schedule`) act on the device: no gradient is
+    rescaled by a separate pass and a captured step is captured once.
+    """
+
+    def __init__(self, params, arena: FlatArena, lr: float = 1e-3, betas=(0.9, 0.999),
+                 eps: float = 1e-8, weight_decay: float = 0.01, grad_scale: float = 1.0,
+                 max_grad_norm: float = 0.0, schedule=None, model=None):
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.arena = arena
+        self.core = FusedOptimCore(arena, "adamw", lr, betas=betas, eps=eps,
+                                   weight_decay=weight_decay, grad_scale=grad_scale,
+                                   max_grad_norm=max_grad_norm, schedule=schedule, model=model)
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.arena.ensure_grads_attached()
+        self.arena.zero_grad()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.local_step()
+        return loss
+
+    def comm_step(self):
+        pass
+
+    @torch.no_grad()
+    def local_step(self):
+        self.arena.bump()
+        sync_base_lr(self.core, self.param_groups[0]["lr"])
+        self.core.step(self.arena, None)

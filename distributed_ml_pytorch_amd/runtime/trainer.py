@@ -36,7 +36,8 @@ from ..parallel.arena import attach_arena
 from ..parallel.asgd import Asynchronous
 from ..parallel.async_sharded import AsyncShardedPSClient
 from ..parallel.clients import (GlooPSClient, LocalPSClient, RcclPSClient, ShardedPSClient)
-from ..parallel.ddp import BucketedAllReduce, FusedSGD
+from ..parallel.ddp import BucketedAllReduce, FusedAdamW, FusedSGD
+from ..parallel.fused_optim import Schedule
 from ..parallel.server import ParameterServer, make_ps_groups
 from ..parallel.staleness import check_policy
 from ..utils import checkpoint as ckpt
@@ -67,7 +68,16 @@ class TrainConfig:
     lr: float = 0.008
     momentum: float = 0.0
     weight_decay: float = 0.0
-    lr_schedule: str = "constant"     # or "inv_epoch": the reference's LambdaLR(1/(epoch+1))
+    lr_schedule: str = "constant"     # "inv_epoch": the reference's LambdaLR(1/(epoch+1)), per
+                                      # epoch on the host; "warmup_cosine": per step on the device
+    optimizer: str = "sgd"            # sgd | adamw (parallel/fused_optim.py)
+    beta1: float = 0.9
+    beta2: float = 0.999
+    adam_eps: float = 1e-8
+    clip_grad_norm: float = 0.0       # global-norm gradient clipping; 0 = off
+    warmup_steps: int = 0             # warmup_cosine: linear warm-up updates
+    lr_min: float = 0.0               # warmup_cosine: floor reached at schedule_steps
+    schedule_steps: int | None = None  # warmup_cosine length; None: max_steps, else all epochs
     n_push: int = 10
     n_pull: int = 10
     staleness: int = 1
@@ -150,22 +160,46 @@ class Worker:
         if resume:
             self.step_idx = ckpt.load_worker_model(resume, self.model)
         params = list(self.model.parameters())
+        if cfg.lr_schedule not in ("constant", "inv_epoch", "warmup_cosine"):
+            raise ValueError(f"unknown lr_schedule {cfg.lr_schedule!r}")
+        if cfg.optimizer not in ("sgd", "adamw"):
+            raise ValueError(f"unknown optimizer {cfg.optimizer!r}; 'sgd' or 'adamw'")
+        # extra optimizer arguments: empty with the defaults, so the plain SGD
+        # constructors (and their by-value kernel) are reached exactly as before
+        okw = {}
+        if cfg.clip_grad_norm > 0:
+            okw["max_grad_norm"] = cfg.clip_grad_norm
+        if cfg.lr_schedule == "warmup_cosine":
+            total = cfg.schedule_steps or cfg.max_steps or \
+                cfg.epochs * max(1, cfg.n_train // cfg.batch_size)
+            okw["schedule"] = Schedule("warmup_cosine", cfg.warmup_steps, total, cfg.lr_min)
+        adam = dict(betas=(cfg.beta1, cfg.beta2), eps=cfg.adam_eps)
         if cfg.mode == "asgd":
             client = client if client is not None else self._make_client(ps_groups)
+            if cfg.optimizer == "adamw":
+                okw.update(optimizer="adamw", **adam)
             self.opt = Asynchronous(params, lr=cfg.lr, n_push=cfg.n_push, n_pull=cfg.n_pull,
                                     model=self.model, client=client, momentum=cfg.momentum,
-                                    weight_decay=cfg.weight_decay)
+                                    weight_decay=cfg.weight_decay, **okw)
         elif cfg.mode == "sync":
             world = dist.get_world_size() if info.is_distributed else 1
             if info.is_distributed:
                 dist.broadcast(self.arena.p32, 0)
                 self.arena.refresh_shadow()
             self.ddp = BucketedAllReduce(self.arena, bucket_mb=cfg.bucket_mb)
-            self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
-                                weight_decay=cfg.weight_decay, grad_scale=1.0 / world)
+            if cfg.optimizer == "adamw":
+                self.opt = FusedAdamW(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
+                                      grad_scale=1.0 / world, model=self.model, **adam, **okw)
+            else:
+                self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
+                                    weight_decay=cfg.weight_decay, grad_scale=1.0 / world, **okw)
         elif cfg.mode == "single":
-            self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
-                                weight_decay=cfg.weight_decay)
+            if cfg.optimizer == "adamw":
+                self.opt = FusedAdamW(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
+                                      model=self.model, **adam, **okw)
+            else:
+                self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
+                                    weight_decay=cfg.weight_decay, **okw)
         else:
             raise ValueError(f"unknown mode {cfg.mode!r}")
         if isinstance(self.opt, Asynchronous):
@@ -273,8 +307,16 @@ class Worker:
             self.graph = None
             return loss.clone(), hits.clone()
         self.graph = g
-        self._graph_key = (tuple(x.shape), x.dtype, self.opt.param_groups[0]["lr"])
+        self._graph_key = self._make_graph_key(x)
         return loss.clone(), hits.clone()
+
+    def _make_graph_key(self, x):
+        """A by-value lr is baked into the captured update kernel, so it keys the
+        graph; with the device-resident hyper block (``opt.core``) the kernels
+        read lr from memory and the graph survives any learning rate."""
+        lr = None if getattr(self.opt, "core", None) is not None else \
+            self.opt.param_groups[0]["lr"]
+        return (tuple(x.shape), x.dtype, lr)
 
     def _capture_agreed(self, ok: bool) -> bool:
         """MIN-all-reduce of the local capture verdict over the sync-DP group."""
@@ -285,7 +327,7 @@ class Worker:
         return bool(flag.item())
 
     def _graph_step(self, x, y, keep: bool = True):
-        key = (tuple(x.shape), x.dtype, self.opt.param_groups[0]["lr"])
+        key = self._make_graph_key(x)
         if self.graph is None or key != self._graph_key:
             return self._capture(x, y)
         with self.timer.time("compute_launch"):
@@ -380,6 +422,9 @@ class Worker:
     def set_lr(self, lr: float):
         for g in self.opt.param_groups:
             g["lr"] = lr
+        core = getattr(self.opt, "core", None)
+        if core is not None:          # between steps, never inside a capture
+            core.set_base_lr(lr)
 
     def finish(self):
         if isinstance(self.opt, Asynchronous):
@@ -458,6 +503,10 @@ def run_training(cfg: TrainConfig, info: DistInfo):
         tr = torch.utils.data.Subset(tr, idx)
     train_loader, test_loader = make_loaders(tr, te, cfg.batch_size, cfg.test_batch_size,
                                              shuffle_seed=cfg.seed + info.rank)
+    core = getattr(w.opt, "core", None)
+    if core is not None and cfg.lr_schedule == "warmup_cosine" and \
+            not (cfg.schedule_steps or cfg.max_steps) and core.t == 0:
+        core.set_total_steps(max(cfg.epochs * len(train_loader), cfg.warmup_steps + 1))
     log = IterationLog()
     log_phases = bool(cfg.log_interval)
     meter = Throughput(sync_cuda=w.device.type == "cuda")
@@ -477,6 +526,8 @@ def run_training(cfg: TrainConfig, info: DistInfo):
             if cfg.log_interval and i % cfg.log_interval == 0 and i > 0:
                 row["samples_per_sec"] = meter.rate()
                 row["param_norm"] = w.param_norm()
+                if core is not None:      # the only read-back of the hyper block
+                    row["lr"], row["grad_norm"] = core.lr(), core.grad_norm()
                 if cfg.divergence_check and not math.isfinite(row["param_norm"]):
                     raise DivergenceError(
                         f"rank {info.rank}: non-finite parameters at epoch {epoch} iteration {i} "

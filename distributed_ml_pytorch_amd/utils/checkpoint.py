@@ -2,7 +2,8 @@
 
 The PS shard is the single source of truth in Downpour SGD, so the server
 checkpoints ``{flat fp32 params, version, stats}``; a worker checkpoint adds
-its step counter, push accumulator, momentum and model buffers (BN running
+its step counter, push accumulator, momentum, AdamW moments with their step
+count and schedule, and model buffers (BN running
 statistics are not part of the pushed vector, as in the reference's ravel).
 
 Files are written atomically (tmp + rename) and loaded with
@@ -49,6 +50,10 @@ def save_worker_checkpoint(path: str, model: torch.nn.Module, optimizer=None, st
             "acc": acc.detach().cpu() if acc is not None else None,
             "mom": mom.detach().cpu() if mom is not None else None,
         }
+        core = getattr(optimizer, "core", None)
+        if core is not None:
+            # AdamW moments, step count and schedule (parallel/fused_optim.py)
+            sd["opt"].update(core.state_dict())
         client = getattr(optimizer, "client", None)
         if client is not None:
             # PS state held on this worker (in-process master / its sharded-PS shard)
@@ -101,6 +106,9 @@ def load_worker_optimizer(path: str, optimizer) -> None:
             if o.get("mom") is not None and getattr(optimizer, "mom", None) is not None:
                 optimizer.mom.copy_(o["mom"])
                 optimizer._mom_steps = max(1, int(o.get("idx", 1)))   # buffer already seeded
+        core = getattr(optimizer, "core", None)
+        if core is not None and "t" in o:     # absent in checkpoints of plain SGD runs
+            core.load_state_dict(o)
     client = getattr(optimizer, "client", None)
     if client is not None and sd.get("client"):
         client.load_state_dict(sd["client"])
