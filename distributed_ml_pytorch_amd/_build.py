@@ -1,13 +1,14 @@
 """In-tree build of the gfx950 HIP extension (`distributed_ml_pytorch_amd/_native*.so`).
 
 Drives ``hipcc --offload-arch=gfx950`` directly (no hipify, no multi-arch):
-each ``csrc/*.hip`` kernel file compiles to an object in parallel, the single
-``bindings.cpp`` (the only TU that sees torch headers) compiles once, and they
+each ``csrc/*.hip`` kernel file compiles to an object in parallel, so does each
+per-family ``csrc/bind/*.cpp`` (the only TUs that see torch headers), and they
 link into one Python extension that resolves ``libamdhip64.so.7`` to the HIP
 runtime torch has already loaded.
 
-Incremental: an object is rebuilt only when its source or any header in
-``csrc/`` is newer.  ``python -m distributed_ml_pytorch_amd._build`` builds.
+Incremental: a kernel object is rebuilt only when its source or any header in
+``csrc/`` is newer; a binding object also when a header in ``csrc/bind/`` is.
+``python -m distributed_ml_pytorch_amd._build`` builds.
 """
 from __future__ import annotations
 
@@ -101,17 +102,20 @@ def build(verbose: bool = False, jobs: int | None = None, force: bool = False) -
             jobs_list.append([hipcc, *common, "-x", "hip", "-c", str(src), "-o", str(obj)])
     inc, libdirs, defs = _torch_flags()
     py_inc = sysconfig.get_paths()["include"]
-    bsrc = CSRC / "bindings.cpp"
-    bobj = BUILD / "bindings.o"
-    objs.append(bobj)
-    if force or _needs(bobj, [bsrc, *headers]):
-        cmd = ["g++", "-O2", "-fPIC", "-std=c++17", "-I", str(CSRC), "-I", py_inc,
-               "-Wno-unused-result", "-Wno-deprecated-declarations", "-Wno-unknown-pragmas",
-               "-Wno-ignored-attributes"]
-        for i in inc:
-            cmd += ["-isystem", i]
-        cmd += defs + ["-D__HIP_PLATFORM_AMD__=1", "-c", str(bsrc), "-o", str(bobj)]
-        jobs_list.append(cmd)
+    # bindings: objects in their own directory (bind/optim.cpp vs optim.hip)
+    (BUILD / "bind").mkdir(exist_ok=True)
+    bind_headers = sorted((CSRC / "bind").glob("*.h"))
+    for bsrc in sorted((CSRC / "bind").glob("*.cpp")):
+        bobj = BUILD / "bind" / (bsrc.stem + ".o")
+        objs.append(bobj)
+        if force or _needs(bobj, [bsrc, *headers, *bind_headers]):
+            cmd = ["g++", "-O2", "-fPIC", "-std=c++17", "-I", str(CSRC), "-I", py_inc,
+                   "-Wno-unused-result", "-Wno-deprecated-declarations", "-Wno-unknown-pragmas",
+                   "-Wno-ignored-attributes"]
+            for i in inc:
+                cmd += ["-isystem", i]
+            cmd += defs + ["-D__HIP_PLATFORM_AMD__=1", "-c", str(bsrc), "-o", str(bobj)]
+            jobs_list.append(cmd)
     # runtime (host-only C++) sources
     for src in sorted(CSRC.glob("*.cc")):
         obj = BUILD / (src.stem + ".o")

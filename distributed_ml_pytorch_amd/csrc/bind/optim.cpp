@@ -1,0 +1,258 @@
+// optim.hip: fused optimizer steps, parameter-server applies and stamps, arena
+// hand-offs, casts and fills.
+#include "util.h"
+
+namespace dmp::bind {
+namespace {
+
+// flat fp32 arena of n elements; `len` names it in the message
+int64_t flat_len(const Tensor& t, const char* len) {
+  TORCH_CHECK(t.numel() % 4 == 0, len, " must be a multiple of 4");
+  return t.numel();
+}
+
+void check_flat_opt(const optional<Tensor>& t, at::ScalarType dt, int64_t n, const char* name) {
+  if (has(t)) check_flat(*t, dt, n, name);
+}
+
+void asgd_fused_step(Tensor g, Tensor p, optional<Tensor> acc, optional<Tensor> mom,
+                     optional<Tensor> w16, double lr, double wd, double momentum,
+                     double dampening, bool nesterov) {
+  const int64_t n = flat_len(p, "flat arena length");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat(g, at::kFloat, n, "g");
+  check_flat_opt(acc, at::kFloat, n, "acc");
+  check_flat_opt(mom, at::kFloat, n, "mom");
+  check_flat_opt(w16, at::kBFloat16, n, "w16");
+  dmp::launch_asgd_fused_step(g.data_ptr<float>(), p.data_ptr<float>(), ptr_or_null<float>(acc),
+                              ptr_or_null<float>(mom), bf16_or_null(w16), n, (float)lr, (float)wd,
+                              (float)momentum, (float)dampening, nesterov, cur_stream());
+}
+
+// Hyper block of one optimizer (optim.hip): optim_hyper_words() fp32 words on
+// the arena's device
+void check_hyper(const Tensor& hyper, const Tensor& like) {
+  TORCH_CHECK(hyper.is_cuda() && hyper.scalar_type() == at::kFloat && hyper.is_contiguous() &&
+                  hyper.numel() == dmp::optim_hyper_words() && hyper.device() == like.device(),
+              "hyper block must be a contiguous fp32 tensor of optim_hyper_words() elements on "
+              "the parameters' device");
+}
+
+// One optimizer step of the hyper block on the current stream.  `g` + `partials`
+// (a persistent 1024-element fp32 buffer) given: clipping on, the gradient norm
+// is taken first; both None: no norm launch.
+void optim_hyper(Tensor hyper, optional<Tensor> g, optional<Tensor> partials) {
+  check_hyper(hyper, hyper);
+  TORCH_CHECK(has(g) == has(partials),
+              "optim_hyper: pass the gradient and the partials buffer together");
+  int64_t n = 0;
+  if (has(g)) {
+    n = flat_len(*g, "flat arena length");
+    check_flat(*g, at::kFloat, n, "g");
+    check_flat(*partials, at::kFloat, 1024, "partials");
+    TORCH_CHECK(g->device() == hyper.device() && partials->device() == hyper.device(),
+                "optim_hyper: g, partials and the hyper block must share a device");
+  }
+  dmp::launch_optim_hyper(hyper.data_ptr<float>(), ptr_or_null<const float>(g),
+                          ptr_or_null<float>(partials), n, cur_stream());
+}
+
+void asgd_fused_step_dev(Tensor g, Tensor p, optional<Tensor> acc, optional<Tensor> mom,
+                         optional<Tensor> w16, Tensor hyper, double wd, double momentum,
+                         double dampening, bool nesterov) {
+  const int64_t n = flat_len(p, "flat arena length");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat(g, at::kFloat, n, "g");
+  check_flat_opt(acc, at::kFloat, n, "acc");
+  check_flat_opt(mom, at::kFloat, n, "mom");
+  check_flat_opt(w16, at::kBFloat16, n, "w16");
+  check_hyper(hyper, p);
+  TORCH_CHECK(g.device() == p.device(), "g and p must share a device");
+  dmp::launch_asgd_fused_step_dev(g.data_ptr<float>(), p.data_ptr<float>(),
+                                  ptr_or_null<float>(acc), ptr_or_null<float>(mom),
+                                  bf16_or_null(w16), n, hyper.data_ptr<float>(), (float)wd,
+                                  (float)momentum, (float)dampening, nesterov, cur_stream());
+}
+
+// `decay`: uint8 mask, one entry per 64-element arena block (None: decay all)
+void adamw_fused_step(Tensor g, Tensor p, optional<Tensor> acc, Tensor m, Tensor v,
+                      optional<Tensor> w16, optional<Tensor> decay, Tensor hyper, double wd,
+                      double eps) {
+  const int64_t n = flat_len(p, "flat arena length");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat(g, at::kFloat, n, "g");
+  check_flat(m, at::kFloat, n, "m");
+  check_flat(v, at::kFloat, n, "v");
+  check_flat_opt(acc, at::kFloat, n, "acc");
+  check_flat_opt(w16, at::kBFloat16, n, "w16");
+  check_hyper(hyper, p);
+  TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device(),
+              "g, p, m and v must share a device");
+  if (has(decay)) {
+    TORCH_CHECK(n % 64 == 0, "a decay mask needs an arena length that is a multiple of 64");
+    TORCH_CHECK(decay->is_cuda() && decay->scalar_type() == at::kByte && decay->is_contiguous() &&
+                    decay->numel() == n / 64 && decay->device() == p.device(),
+                "decay mask must be a contiguous uint8 tensor of n / 64 elements on the "
+                "parameters' device");
+  }
+  dmp::launch_adamw_fused_step(g.data_ptr<float>(), p.data_ptr<float>(), ptr_or_null<float>(acc),
+                               m.data_ptr<float>(), v.data_ptr<float>(), bf16_or_null(w16),
+                               ptr_or_null<const uint8_t>(decay), n, hyper.data_ptr<float>(),
+                               (float)wd, (float)eps, cur_stream());
+}
+
+// `factor`: the {factor, tau} slot ps_stale_factor wrote on the current stream
+// (staleness damping: scale * factor is applied); None = the plain apply
+void ps_apply(Tensor shard, Tensor delta, optional<Tensor> mirror, double scale, bool atomic,
+              optional<Tensor> factor) {
+  const int64_t n = flat_len(shard, "shard length");
+  check_flat(shard, at::kFloat, n, "shard");
+  check_flat_opt(mirror, at::kBFloat16, n, "mirror");
+  if (has(factor))
+    TORCH_CHECK(factor->is_cuda() && factor->scalar_type() == at::kFloat &&
+                    factor->numel() >= 1 && factor->is_contiguous() &&
+                    factor->device() == shard.device(),
+                "ps_apply: factor must be a contiguous fp32 tensor on the shard's device");
+  const float* fac = ptr_or_null<const float>(factor);
+  const bool bf = delta.scalar_type() == at::kBFloat16;
+  if (atomic) {
+    // concurrent applies on several streams: no mirror (it would race)
+    TORCH_CHECK(!has(mirror), "ps_apply: atomic applies take no bf16 mirror");
+    check_flat(delta, bf ? at::kBFloat16 : at::kFloat, n, "delta");
+    dmp::launch_ps_apply_atomic(shard.data_ptr<float>(), delta.data_ptr(), bf, n, (float)scale,
+                                cur_stream(), fac);
+  } else if (delta.scalar_type() == at::kFloat) {
+    check_flat(delta, at::kFloat, n, "delta");
+    dmp::launch_ps_apply_f32(shard.data_ptr<float>(), delta.data_ptr<float>(),
+                             bf16_or_null(mirror), n, (float)scale, cur_stream(), fac);
+  } else {
+    check_flat(delta, at::kBFloat16, n, "delta");
+    dmp::launch_ps_apply_bf16(shard.data_ptr<float>(), bf16(delta), bf16_or_null(mirror), n,
+                              (float)scale, cur_stream(), fac);
+  }
+}
+
+// PS applied-count (server.py / async_sharded.py version stamps): ps_count adds
+// `add` to (or, set=True, sets) the int32 counter on the current stream;
+// ps_stamp writes float(counter) into the 1-element fp32 `dst`
+int* counter_ptr(const Tensor& cnt, const char* fn) {
+  TORCH_CHECK(cnt.is_cuda() && cnt.scalar_type() == at::kInt && cnt.numel() == 1, fn,
+              ": counter must be a 1-element int32 GPU tensor");
+  return cnt.data_ptr<int>();
+}
+
+void ps_count(Tensor cnt, int64_t add, bool set) {
+  dmp::launch_ps_count(counter_ptr(cnt, "ps_count"), (int)add, set, cur_stream());
+}
+
+void ps_stamp(Tensor cnt, Tensor dst) {
+  int* c = counter_ptr(cnt, "ps_stamp");
+  TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == at::kFloat && dst.numel() == 1 &&
+                  dst.device() == cnt.device(),
+              "ps_stamp: dst must be a 1-element fp32 tensor on the counter's device");
+  dmp::launch_ps_stamp(c, dst.data_ptr<float>(), cur_stream());
+}
+
+// Staleness factor of the next apply on the current stream (parallel/staleness.py,
+// policy "damp"): tau = max(0, min(counter, cap) - base), f = 1 / (1 + max(0, tau - bound))
+// -> slot = {f, tau}; the apply index, max tau, damped count and a ring of
+// (tau, f) go to the int32 `log` (ps_stale_log_numel() elements).  `cap`: the
+// host's enqueue count when the push arrived (None = no clamp)
+void ps_stale_factor(Tensor cnt, int64_t base, int64_t bound, Tensor slot, Tensor log,
+                     optional<int64_t> cap) {
+  int* c = counter_ptr(cnt, "ps_stale_factor");
+  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kFloat && slot.numel() == 2 &&
+                  slot.is_contiguous() && slot.device() == cnt.device(),
+              "ps_stale_factor: slot must be a 2-element fp32 tensor on the counter's device");
+  TORCH_CHECK(log.is_cuda() && log.scalar_type() == at::kInt && log.is_contiguous() &&
+                  log.numel() == dmp::stale_log_numel() && log.device() == cnt.device(),
+              "ps_stale_factor: log must be an int32 tensor of ps_stale_log_numel() elements "
+              "on the counter's device");
+  const int64_t top = int64_t(1) << 30;
+  TORCH_CHECK(bound >= 0 && bound < top && base > -top && base < top,
+              "ps_stale_factor: bound must be in [0, 2^30) and |base| below 2^30");
+  const int capped = (int)std::min(std::max(cap.value_or(top), -top), top);
+  dmp::launch_ps_stale_factor(c, (int)base, (int)bound, capped, slot.data_ptr<float>(),
+                              log.data_ptr<int>(), cur_stream());
+}
+
+void pull_land(Tensor p, Tensor src, optional<Tensor> acc, optional<Tensor> w16) {
+  const int64_t n = flat_len(p, "arena length");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat_opt(acc, at::kFloat, n, "acc");
+  check_flat_opt(w16, at::kBFloat16, n, "w16");
+  if (src.scalar_type() == at::kFloat) {
+    check_flat(src, at::kFloat, n, "src");
+    dmp::launch_pull_land_f32(p.data_ptr<float>(), src.data_ptr<float>(), ptr_or_null<float>(acc),
+                              bf16_or_null(w16), n, cur_stream());
+  } else {
+    check_flat(src, at::kBFloat16, n, "src");
+    dmp::launch_pull_land_bf16(p.data_ptr<float>(), bf16(src), ptr_or_null<float>(acc),
+                               bf16_or_null(w16), n, cur_stream());
+  }
+}
+
+void push_handoff(Tensor acc, optional<Tensor> out32, optional<Tensor> out16) {
+  const int64_t n = flat_len(acc, "arena length");
+  check_flat(acc, at::kFloat, n, "acc");
+  check_flat_opt(out32, at::kFloat, n, "out32");
+  check_flat_opt(out16, at::kBFloat16, n, "out16");
+  dmp::launch_push_handoff(acc.data_ptr<float>(), ptr_or_null<float>(out32), bf16_or_null(out16),
+                           n, cur_stream());
+}
+
+void cast_f32_bf16(Tensor src, Tensor dst) {
+  const int64_t n = flat_len(src, "length");
+  check_flat(src, at::kFloat, n, "src");
+  check_flat(dst, at::kBFloat16, n, "dst");
+  dmp::launch_cast_f32_bf16(src.data_ptr<float>(), bf16(dst), n, cur_stream());
+}
+
+Tensor sumsq(Tensor x) {
+  const int64_t n = flat_len(x, "length");
+  check_flat(x, at::kFloat, n, "x");
+  auto part = at::empty({1024}, x.options());
+  const int g = dmp::launch_sumsq_partial(x.data_ptr<float>(), part.data_ptr<float>(), n,
+                                          cur_stream());
+  return part.narrow(0, 0, g).sum();
+}
+
+// Native zero fill of a dense tensor (the grad arena at every step start: no
+// ATen fill kernel).  Deliberately a kernel and not hipMemsetAsync: a captured
+// memset node raced with the previous graph replay (csrc/optim.hip zero_fill).
+void zero_(Tensor t) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous(), "zero_: a contiguous GPU tensor");
+  const long long bytes = (long long)t.numel() * t.element_size();
+  TORCH_CHECK(bytes % 4 == 0 && aligned(t), "zero_: a 16-B aligned tensor of whole dwords");
+  dmp::launch_zero_fill(t.data_ptr(), bytes, cur_stream());
+}
+
+}  // namespace
+
+void bind_optim(pybind11::module_& m) {
+  m.def("asgd_fused_step", &asgd_fused_step, "fused flat ASGD/SGD update");
+  m.def("optim_hyper_words", []() { return dmp::optim_hyper_words(); },
+        "fp32 words of an optimizer's device-resident hyper block");
+  m.def("optim_hyper", &optim_hyper, "advance a hyper block one step (norm, clip, schedule)");
+  m.def("asgd_fused_step_dev", &asgd_fused_step_dev,
+        "fused flat ASGD/SGD update, lr and gradient scale from the hyper block");
+  m.def("adamw_fused_step", &adamw_fused_step, "fused flat AdamW update");
+  m.def("ps_apply", &ps_apply, "parameter-server delta apply", py::arg("shard"), py::arg("delta"),
+        py::arg("mirror") = py::none(), py::arg("scale") = 1.0, py::arg("atomic") = false,
+        py::arg("factor") = py::none());
+  m.def("ps_count", &ps_count, "bump / set a PS applied-count", py::arg("cnt"),
+        py::arg("add") = 1, py::arg("set") = false);
+  m.def("ps_stamp", &ps_stamp, "copy a PS applied-count into a reply's version element");
+  m.def("ps_stale_factor", &ps_stale_factor, "publish the staleness factor of the next apply",
+        py::arg("cnt"), py::arg("base"), py::arg("bound"), py::arg("slot"), py::arg("log"),
+        py::arg("cap") = py::none());
+  m.def("ps_stale_log_numel", []() { return dmp::stale_log_numel(); },
+        "int32 elements of a ps_stale_factor log");
+  m.def("pull_land", &pull_land, "land a parameter pull into the worker arena");
+  m.def("push_handoff", &push_handoff, "snapshot+zero the push accumulator");
+  m.def("cast_f32_bf16", &cast_f32_bf16, "flat fp32 -> bf16");
+  m.def("sumsq", &sumsq, "sum of squares of a flat fp32 buffer");
+  m.def("zero_", &zero_, "native zero fill of a dense GPU tensor (a kernel, not a memset)");
+}
+
+}  // namespace dmp::bind

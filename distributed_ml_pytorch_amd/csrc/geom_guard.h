@@ -1,5 +1,5 @@
 // Host-side shape arithmetic and 32-bit offset guards shared by the PyTorch
-// bindings (bindings.cpp) and the sanitizer driver (host_check.cpp, `make asan`).
+// bindings (bind/*.cpp) and the sanitizer driver (host_check.cpp, `make asan`).
 //
 // Every HIP kernel here addresses its operands through buffer descriptors with
 // 32-bit BYTE offsets (num_records is a 32-bit field), so a tensor the kernels

@@ -63,7 +63,7 @@ def bias_grad_acc(dy, out):
 
 # ----------------------------------------------------------------- dispatcher
 def _mfma_ok(mode: int, M: int, N: int, K: int, *mats) -> bool:
-    """The MFMA tiles' layout constraints (mirrors the checks in bindings.cpp)."""
+    """The MFMA tiles' layout constraints (mirrors the checks in csrc/bind/gemm.cpp)."""
     for t in mats:
         if t is None:
             continue
