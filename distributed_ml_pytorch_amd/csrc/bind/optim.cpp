@@ -201,6 +201,50 @@ void push_handoff(Tensor acc, optional<Tensor> out32, optional<Tensor> out16) {
                            n, cur_stream());
 }
 
+// MX8 payload of an n-element arena: mx8_layout(n) uint8 bytes (parallel/wire8.py)
+uint8_t* mx8_payload(const Tensor& payload, int64_t n, const Tensor& like, const char* fn) {
+  const long long nbytes = dmp::mx8_layout(n, nullptr);
+  TORCH_CHECK(nbytes >= 0, fn, ": ", n, " elements are out of range for the MX8 wire");
+  check_flat(payload, at::kByte, nbytes, "payload");
+  TORCH_CHECK(payload.is_contiguous() && payload.device() == like.device(), fn,
+              ": payload must be contiguous and on the arena's device");
+  return payload.data_ptr<uint8_t>();
+}
+
+std::tuple<int64_t, int64_t, int64_t> mx8_layout(int64_t n) {
+  long long so = 0;
+  const long long nbytes = dmp::mx8_layout(n, &so);
+  TORCH_CHECK(nbytes >= 0, "mx8_layout: ", n, " elements are out of range");
+  return {0, so, nbytes};
+}
+
+// payload <- quantise(acc), acc <- residual (error feedback), one pass
+void push_handoff_mx8(Tensor acc, Tensor payload) {
+  const int64_t n = flat_len(acc, "arena length");
+  check_flat(acc, at::kFloat, n, "acc");
+  TORCH_CHECK(acc.is_contiguous(), "acc must be contiguous");
+  uint8_t* out = mx8_payload(payload, n, acc, "push_handoff_mx8");
+  dmp::launch_push_handoff_mx8(acc.data_ptr<float>(), out, n, cur_stream());
+}
+
+// ps_apply for an MX8 payload: the same three shapes (plain + mirror, atomic, factor)
+void ps_apply_mx8(Tensor shard, Tensor payload, optional<Tensor> mirror, double scale, bool atomic,
+                  optional<Tensor> factor) {
+  const int64_t n = flat_len(shard, "shard length");
+  check_flat(shard, at::kFloat, n, "shard");
+  TORCH_CHECK(shard.is_contiguous(), "shard must be contiguous");
+  check_flat_opt(mirror, at::kBFloat16, n, "mirror");
+  if (has(factor))
+    TORCH_CHECK(factor->is_cuda() && factor->scalar_type() == at::kFloat &&
+                    factor->numel() >= 1 && factor->is_contiguous() &&
+                    factor->device() == shard.device(),
+                "ps_apply_mx8: factor must be a contiguous fp32 tensor on the shard's device");
+  TORCH_CHECK(!(atomic && has(mirror)), "ps_apply_mx8: atomic applies take no bf16 mirror");
+  const uint8_t* in = mx8_payload(payload, n, shard, "ps_apply_mx8");
+  dmp::launch_ps_apply_mx8(shard.data_ptr<float>(), in, bf16_or_null(mirror), n, (float)scale,
+                           atomic, cur_stream(), ptr_or_null<const float>(factor));
+}
+
 void cast_f32_bf16(Tensor src, Tensor dst) {
   const int64_t n = flat_len(src, "length");
   check_flat(src, at::kFloat, n, "src");
@@ -250,6 +294,12 @@ void bind_optim(pybind11::module_& m) {
         "int32 elements of a ps_stale_factor log");
   m.def("pull_land", &pull_land, "land a parameter pull into the worker arena");
   m.def("push_handoff", &push_handoff, "snapshot+zero the push accumulator");
+  m.def("mx8_layout", &mx8_layout, "(codes_off, scales_off, nbytes) of an MX8 push payload");
+  m.def("push_handoff_mx8", &push_handoff_mx8,
+        "quantise the push accumulator into an MX8 payload, keep the residual");
+  m.def("ps_apply_mx8", &ps_apply_mx8, "parameter-server apply of an MX8 payload",
+        py::arg("shard"), py::arg("payload"), py::arg("mirror") = py::none(),
+        py::arg("scale") = 1.0, py::arg("atomic") = false, py::arg("factor") = py::none());
   m.def("cast_f32_bf16", &cast_f32_bf16, "flat fp32 -> bf16");
   m.def("sumsq", &sumsq, "sum of squares of a flat fp32 buffer");
   m.def("zero_", &zero_, "native zero fill of a dense GPU tensor (a kernel, not a memset)");

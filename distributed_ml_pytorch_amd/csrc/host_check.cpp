@@ -190,6 +190,25 @@ void check_guards() {
   }
 }
 
+// MX8 push payload (optim.hip mx8_layout): codes, 16-B aligned scale bytes,
+// total a multiple of 4, over the arena sizes and the edges of the range
+void check_mx8_layout() {
+  const long long sizes[] = {0, 4, 28, 32, 36, 64, 65540, 11173962 + 54, 86567656 + 24,
+                             (1LL << 31) - 4, 1LL << 31, 1LL << 40};
+  for (long long n : sizes) {
+    long long so = -1;
+    const long long nb = dmp::mx8_layout(n, &so);
+    const long long nblk = (n + 31) / 32;
+    EXPECT(nb >= 0 && so >= n && so - n < 16 && so % 16 == 0, "mx8 n %lld: scales at %lld", n, so);
+    EXPECT(nb % 4 == 0 && nb >= so + nblk && nb - (so + nblk) < 4, "mx8 n %lld: %lld bytes", n,
+           nb);
+  }
+  EXPECT(dmp::mx8_layout(4, nullptr) == 20 && dmp::mx8_layout(64, nullptr) == 68, "mx8 small");
+  EXPECT(dmp::mx8_layout(-4, nullptr) == -1 && dmp::mx8_layout((1LL << 40) + 4, nullptr) == -1 &&
+             dmp::mx8_layout(INT64_MAX, nullptr) == -1,
+         "mx8 lengths out of range must be rejected, not wrapped");
+}
+
 }  // namespace
 
 // DMP_ASAN_SELFTEST=asan|ubsan: a deliberate heap overflow / signed overflow,
@@ -236,6 +255,7 @@ int main() {
   EXPECT(dmp::bn_maxpool_supported(64, 3, 2, 1) && !dmp::bn_maxpool_supported(64, 2, 2, 0),
          "bn_maxpool window");
   check_guards();
+  check_mx8_layout();
   std::printf("host_check: %lld checks over %zu conv shapes, %d failed\n", g_checks, convs.size(),
               g_fail);
   return g_fail == 0 ? 0 : 1;

@@ -41,6 +41,13 @@ void launch_pull_land_f32(float* p, const float* src, const float* acc, uint16_t
 void launch_pull_land_bf16(float* p, const uint16_t* src, const float* acc, uint16_t* w16,
                            long long n, hipStream_t s);
 void launch_push_handoff(float* acc, float* out32, uint16_t* out16, long long n, hipStream_t s);
+// Block-scaled 8-bit push wire (MXFP8; parallel/wire8.py).  mx8_layout: bytes of
+// the payload of n elements (codes at 0, scale bytes at *scales_off), -1 for a
+// length out of range.  The kernels take n % 4 == 0 and a 16-B aligned payload.
+long long mx8_layout(long long n, long long* scales_off);
+void launch_push_handoff_mx8(float* acc, uint8_t* payload, long long n, hipStream_t s);
+void launch_ps_apply_mx8(float* shard, const uint8_t* payload, uint16_t* mirror, long long n,
+                         float scale, bool atomic, hipStream_t s, const float* factor = nullptr);
 void launch_cast_f32_bf16(const float* src, uint16_t* dst, long long n, hipStream_t s);
 int launch_sumsq_partial(const float* x, float* partial, long long n, hipStream_t s);
 void launch_zero_fill(void* p, long long bytes, hipStream_t s);

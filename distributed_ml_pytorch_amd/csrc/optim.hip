@@ -442,6 +442,144 @@ __global__ void __launch_bounds__(256) push_handoff_kernel(
   }
 }
 
+// ---- block-scaled 8-bit push wire (OCP MXFP8; specification: parallel/wire8.py)
+// Payload of n elements: n E4M3 code bytes, then (at the next multiple of 16)
+// ceil(n / 32) E8M0 scale bytes, the total padded to a multiple of 4.  The one
+// host-side definition; -1 for a length the kernels do not take.
+long long mx8_layout(long long n, long long* scales_off) {
+  if (n < 0 || n > (1LL << 40)) return -1;
+  const long long so = (n + 15) / 16 * 16;
+  if (scales_off) *scales_off = so;
+  return (so + (n + 31) / 32 + 3) / 4 * 4;
+}
+
+// gfx950's FP8 conversions are the OCP ones (e4m3fn), round to nearest even.
+// Two floats -> two code bytes in the low half of the result.
+__device__ __forceinline__ u32 mx8_encode2(float a, float b, int down) {
+  a = fminf(fmaxf(ldexpf(a, down), -448.f), 448.f);
+  b = fminf(fmaxf(ldexpf(b, down), -448.f), 448.f);
+  return (u32)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffffu;
+}
+
+// code byte `sel` of `codes` times 2^up; NaN for a block sent as E8M0 NaN
+__device__ __forceinline__ float mx8_decode(u32 codes, int sel, int up, bool nan) {
+  float f;
+  switch (sel) {
+    case 0: f = __builtin_amdgcn_cvt_f32_fp8((int)codes, 0); break;
+    case 1: f = __builtin_amdgcn_cvt_f32_fp8((int)codes, 1); break;
+    case 2: f = __builtin_amdgcn_cvt_f32_fp8((int)codes, 2); break;
+    default: f = __builtin_amdgcn_cvt_f32_fp8((int)codes, 3); break;
+  }
+  return nan ? __uint_as_float(0x7fc00000u) : ldexpf(f, up);
+}
+
+// s + scale * d with the product and the sum rounded separately (contraction
+// off for this statement): the same value as the atomic form and as the fp32
+// expression of the CPU path.  A fused multiply-add rounds once, and against a
+// twice-rounded reference that is many ulps of a result that cancels.
+__device__ __forceinline__ float mx8_axpy(float s, float scale, float d) {
+#pragma clang fp contract(off)
+  const float p = scale * d;
+  return s + p;
+}
+
+// (f32x4, the native vector type: the hand-off's 16-B loads and stores stay whole)
+__device__ __forceinline__ u32 mx8_mag(f32x4 v) {
+  const u32 a = __float_as_uint(v[0]) & 0x7fffffffu, b = __float_as_uint(v[1]) & 0x7fffffffu;
+  const u32 c = __float_as_uint(v[2]) & 0x7fffffffu, d = __float_as_uint(v[3]) & 0x7fffffffu;
+  return max(max(a, b), max(c, d));
+}
+
+// Four elements: codes into one dword, v <- residual (x - dequant, exact in fp32)
+__device__ __forceinline__ u32 mx8_quant4(f32x4& v, int down) {
+  const u32 lo = mx8_encode2(v[0], v[1], down), hi = mx8_encode2(v[2], v[3], down);
+  const u32 c = lo | (hi << 16);
+  v[0] -= mx8_decode(c, 0, -down, false); v[1] -= mx8_decode(c, 1, -down, false);
+  v[2] -= mx8_decode(c, 2, -down, false); v[3] -= mx8_decode(c, 3, -down, false);
+  return c;
+}
+
+// Push hand-off on the MX8 wire: payload = quantise(acc), acc = residual, one
+// pass (the residual is the error feedback: the next push carries it).
+// A lane owns one float4 (16-B load and store, 4 code bytes as one dword: every
+// wave-instruction is contiguous), 8 lanes own a block of 32: the block amax
+// is three cross-lane DPP steps on the magnitude bits (unsigned order =
+// magnitude order, and an exponent field of 255 marks a non-finite block) --
+// no LDS, no atomics.  The loop bound is the block's first float4, so all
+// eight lanes of a block are active for the cross-lane steps; a lane past the
+// end (n % 32 != 0) counts as zeros and stores nothing.
+__global__ void __launch_bounds__(256) push_handoff_mx8_kernel(
+    f32x4* __restrict__ acc, u8* __restrict__ payload, long long n4, long long scales_off) {
+  const long long stride = (long long)gridDim.x * blockDim.x;     // a multiple of 8
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  u32* __restrict__ codes = reinterpret_cast<u32*>(payload);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; (i & ~7LL) < n4;
+       i += stride) {
+    const bool v = i < n4;
+    f32x4 a = z;
+    if (v) a = acc[i];
+    u32 m = mx8_mag(a);
+    // lane ^ 1 and lane ^ 2 (quad permutes [1,0,3,2], [2,3,0,1]), then the other
+    // quad of the 8 (row_half_mirror: lane i <-> 7 - i, both hold their quad's max)
+    m = max(m, (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true));
+    m = max(m, (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true));
+    m = max(m, (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, true));
+    const int e = (int)(m >> 23);
+    const bool bad = e == 255;
+    const int sb = bad ? 255 : max(e - 8, 0);       // e <= 254: never above 246
+    u32 c = 0;
+    if (bad) a = z;
+    else c = mx8_quant4(a, 127 - sb);
+    if (v) {
+      codes[i] = c;
+      acc[i] = a;
+      if ((i & 7) == 0) payload[scales_off + (i >> 3)] = (u8)sb;
+    }
+  }
+}
+
+// shard += scale * dequant(payload) (MX8 wire), optional bf16 mirror: the
+// shape of ps_apply_bf16_kernel with 4 code bytes and the block's scale byte
+// (8 float4 items per block) in place of the bf16x4.
+__global__ void __launch_bounds__(256) ps_apply_mx8_kernel(
+    float4* __restrict__ shard, const u8* __restrict__ payload, bf16x4* __restrict__ mirror,
+    long long n4, long long scales_off, float scale, const float* factor = nullptr) {
+  scale = ps_scale(scale, factor);
+  const u32* __restrict__ codes = reinterpret_cast<const u32*>(payload);
+  const u8* __restrict__ scales = payload + scales_off;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 s = shard[i];
+    const u32 c = codes[i];
+    const int sb = scales[i >> 3];
+    const bool nan = sb == 255;
+    s.x = mx8_axpy(s.x, scale, mx8_decode(c, 0, sb - 127, nan));
+    s.y = mx8_axpy(s.y, scale, mx8_decode(c, 1, sb - 127, nan));
+    s.z = mx8_axpy(s.z, scale, mx8_decode(c, 2, sb - 127, nan));
+    s.w = mx8_axpy(s.w, scale, mx8_decode(c, 3, sb - 127, nan));
+    shard[i] = s;
+    if (mirror) {
+      bf16x4 o;
+      o.v[0] = f2bf(s.x); o.v[1] = f2bf(s.y); o.v[2] = f2bf(s.z); o.v[3] = f2bf(s.w);
+      mirror[i] = o;
+    }
+  }
+}
+
+// The atomic form (completion-ordered link streams): one element per lane, as
+// ps_apply_atomic_kernel -- every wave-instruction adds 256 contiguous bytes.
+__global__ void __launch_bounds__(256) ps_apply_mx8_atomic_kernel(
+    float* __restrict__ shard, const u8* __restrict__ payload, long long n, long long scales_off,
+    float scale, const float* factor = nullptr) {
+  scale = ps_scale(scale, factor);
+  const u8* __restrict__ scales = payload + scales_off;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int sb = scales[i >> 5];
+    unsafeAtomicAdd(shard + i, scale * mx8_decode(payload[i], 0, sb - 127, sb == 255));
+  }
+}
+
 // fp32 -> bf16 cast (flat), used to initialise the compute shadow.
 __global__ void __launch_bounds__(256) cast_f32_bf16_kernel(
     const float4* __restrict__ src, bf16x4* __restrict__ dst, long long n4) {
@@ -595,6 +733,32 @@ void launch_push_handoff(float* acc, float* out32, u16* out16, long long n, hipS
   const long long n4 = n / 4;
   hipLaunchKernelGGL(push_handoff_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
                      (float4*)acc, (float4*)out32, (bf16x4*)out16, n4);
+}
+
+// payload: mx8_layout(n) bytes, 16-B aligned; n % 4 == 0 (checked by the binding)
+void launch_push_handoff_mx8(float* acc, u8* payload, long long n, hipStream_t s) {
+  if (n <= 0) return;
+  long long so = 0;
+  mx8_layout(n, &so);
+  const long long n4 = n / 4;
+  hipLaunchKernelGGL(push_handoff_mx8_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
+                     (f32x4*)acc, payload, n4, so);
+}
+
+void launch_ps_apply_mx8(float* shard, const u8* payload, u16* mirror, long long n, float scale,
+                         bool atomic, hipStream_t s, const float* factor) {
+  if (n <= 0) return;
+  long long so = 0;
+  mx8_layout(n, &so);
+  if (atomic) {
+    const int grid = (int)std::min<long long>((n + 255) / 256, 256LL * 16);
+    hipLaunchKernelGGL(ps_apply_mx8_atomic_kernel, dim3(grid), dim3(256), 0, s, shard, payload, n,
+                       so, scale, factor);
+  } else {
+    const long long n4 = n / 4;
+    hipLaunchKernelGGL(ps_apply_mx8_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
+                       (float4*)shard, payload, (bf16x4*)mirror, n4, so, scale, factor);
+  }
 }
 
 void launch_cast_f32_bf16(const float* src, u16* dst, long long n, hipStream_t s) {

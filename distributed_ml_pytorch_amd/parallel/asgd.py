@@ -26,7 +26,7 @@ import torch.distributed as dist
 from torch.optim.optimizer import Optimizer, required
 
 from .arena import attach_arena, get_arena
-from .clients import GlooPSClient, LocalPSClient, PSClient
+from .clients import GlooPSClient, LocalPSClient, PSClient, check_push_wire
 from .fused_optim import FusedOptimCore, sync_base_lr
 
 
@@ -44,7 +44,11 @@ class Asynchronous(Optimizer):
                  pull_mode: str = "overwrite", wire_dtype: torch.dtype = torch.float32,
                  shadow_dtype: torch.dtype | None | str = "auto", optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0,
-                 schedule=None):
+                 schedule=None, push_wire: str = "same"):
+        """``push_wire="mx8"``: pushes travel as block-scaled 8-bit payloads
+        (:mod:`.wire8`) and the accumulator keeps the quantisation residual, so
+        nothing is lost, only delayed to the next push.  Local and central PS
+        clients only; ``"same"`` (default) pushes in ``wire_dtype``."""
         if lr is required or n_push is required or n_pull is required or model is required:
             raise TypeError("Asynchronous needs lr, n_push, n_pull and model")
         if lr < 0.0:
@@ -85,8 +89,12 @@ class Asynchronous(Optimizer):
                                        schedule=schedule, model=model)
         self.idx = 0
         self.timer = _NO_TIMER      # a utils.metrics.StepTimer when the trainer wires one
-        self.client = client if client is not None else default_client(
-            staleness=staleness, pull_mode=pull_mode, wire_dtype=wire_dtype)
+        if client is None:
+            client = default_client(staleness=staleness, pull_mode=pull_mode,
+                                    wire_dtype=wire_dtype, push_wire=push_wire)
+        elif check_push_wire(push_wire) != "same":
+            client.push_wire = push_wire       # an explicit client takes the optimizer's knob
+        self.client = client
         self.client.attach(self)
         self.client.init()
         self._nat = None

@@ -30,9 +30,20 @@ import torch
 import torch.distributed as dist
 
 from . import messaging as M
+from . import wire8
 from .links import warm_stream
 
 _LOG = logging.getLogger(__name__)
+
+
+MX8_FLAVOURS = ("the local PS (LocalPSClient) and the central PS over gloo or RCCL "
+                "(GlooPSClient, RcclPSClient)")
+
+
+def check_push_wire(push_wire: str) -> str:
+    if push_wire not in ("same", "mx8"):
+        raise ValueError(f"push_wire must be 'same' or 'mx8', got {push_wire!r}")
+    return push_wire
 
 
 class _Pending:
@@ -47,8 +58,14 @@ class _Pending:
 class PSClient:
     """Base class: owns staging buffers and the landing logic."""
 
+    # clients whose push can travel as a block-scaled 8-bit payload (wire8.py)
+    MX8_WIRE = False
+
     def __init__(self, staleness: int = 1, pull_mode: str = "overwrite",
-                 wire_dtype: torch.dtype = torch.float32):
+                 wire_dtype: torch.dtype = torch.float32, push_wire: str = "same"):
+        """``push_wire``: ``"same"`` pushes in ``wire_dtype``; ``"mx8"`` pushes the
+        MXFP8 payload of :mod:`.wire8` and keeps the quantisation residual in the
+        accumulator (error feedback).  Pulls always use ``wire_dtype``."""
         if staleness < 0:
             raise ValueError("staleness must be >= 0")
         if pull_mode not in ("overwrite", "rebase"):
@@ -56,6 +73,7 @@ class PSClient:
         self.staleness = staleness
         self.pull_mode = pull_mode
         self.wire_dtype = wire_dtype
+        self.push_wire = check_push_wire(push_wire)
         self.pending: deque[_Pending] = deque()
         self.version = 0            # version of the PS params last landed
         self.pushes = 0
@@ -71,6 +89,11 @@ class PSClient:
 
     # -- wiring ------------------------------------------------------------
     def attach(self, opt):
+        if self.push_wire == "mx8" and not self.MX8_WIRE:
+            raise ValueError(
+                f"push_wire='mx8' is not supported by {type(self).__name__}: the 8-bit push "
+                f"wire runs on {MX8_FLAVOURS}")
+        self.mx8 = self.push_wire == "mx8"
         self.opt = opt
         self.arena = opt.arena
         self.device = self.arena.device
@@ -97,6 +120,26 @@ class PSClient:
             prev.wait()
             self._send_work[slot] = None
         buf = self._send[slot]
+        if self.mx8:
+            # payload = quantise(acc), acc = residual: the rounding error of this
+            # push stays in the accumulator and travels with the next one
+            if buf is None:
+                # zeroed once: the layout's pad bytes are never written again
+                buf = torch.empty(wire8.layout(acc.numel())[2], dtype=torch.uint8,
+                                  device=self.device)
+                if self.cuda:
+                    self.nat.zero_(buf)
+                else:
+                    buf.zero_()
+                self._send[slot] = buf
+            if self.cuda:
+                self.nat.push_handoff_mx8(acc, buf)
+            else:
+                payload, resid = wire8.quantize(acc)
+                buf.copy_(payload)
+                acc.copy_(resid)
+            self._cur_slot = slot
+            return buf
         if buf is None or buf.numel() != acc.numel():
             buf = torch.empty(acc.numel(), dtype=self.wire_dtype, device=self.device)
             self._send[slot] = buf
@@ -262,6 +305,7 @@ class LocalPSClient(PSClient):
     # default keeps the apply and the snapshot on the compute stream; DMP_LOCAL_PS_SIDE=1
     # selects the side-stream placement described above (the N > 1 structure).
     SIDE = os.environ.get("DMP_LOCAL_PS_SIDE", "0") == "1"
+    MX8_WIRE = True
 
     def init(self):
         self.master = self.arena.p32.detach().clone()
@@ -283,11 +327,16 @@ class LocalPSClient(PSClient):
             with torch.cuda.stream(self.side):
                 self.side.wait_event(ev)
                 with self._timed("push"):
-                    self.nat.ps_apply(self.master, buf, None, 1.0)
+                    if self.mx8:
+                        self.nat.ps_apply_mx8(self.master, buf, None, 1.0)
+                    else:
+                        self.nat.ps_apply(self.master, buf, None, 1.0)
                 done = torch.cuda.Event()
                 done.record()
             # the hand-off slot is refilled two pushes later: after this apply read it
             self._send_work[self._cur_slot] = _EventWork(done)
+        elif self.mx8:
+            self.master.add_(wire8.dequantize(buf, self.master.numel()))
         else:
             self.master.add_(buf.to(torch.float32))
         self.ps_version += 1
@@ -440,6 +489,8 @@ class SharedPSClient(PSClient):
 class GlooPSClient(PSClient):
     """Reference topology over gloo: ``send_message`` to the PS, reply on TAG_REPLY."""
 
+    MX8_WIRE = True
+
     def __init__(self, ps_rank: int = 0, group=None, **kw):
         super().__init__(**kw)
         self.ps_rank = ps_rank
@@ -459,8 +510,10 @@ class GlooPSClient(PSClient):
     def push(self, step: int):
         buf = self._handoff()
         self._resolve_versions()
+        # MX8: the header still counts elements, the payload is layout(n) bytes
+        hdr = dict(nelem=self.opt.acc.numel(), dtype=M.MX8) if self.mx8 else {}
         works = M.send_message(M.MessageCode.GradientUpdate, self._cpu(buf), self.ps_rank,
-                               step=step, version=self.version, group=self.group)
+                               step=step, version=self.version, group=self.group, **hdr)
         if not self.cuda:
             # gloo reads an unbound CPU send buffer only when the PS posts its recv:
             # the slot must not be refilled (two pushes later) before that happens
@@ -496,6 +549,8 @@ class GlooPSClient(PSClient):
 class RcclPSClient(PSClient):
     """Central PS on GPUs: control header on gloo, payload over a per-pair RCCL comm."""
 
+    MX8_WIRE = True
+
     def __init__(self, ps_rank: int, control_group, pair_group, **kw):
         super().__init__(**kw)
         self.ps_rank = ps_rank
@@ -518,8 +573,12 @@ class RcclPSClient(PSClient):
     def push(self, step: int):
         buf = self._handoff()
         self._resolve_versions()
-        header = M.make_header(M.MessageCode.GradientUpdate, dist.get_rank(), step, self.version,
-                               buf.numel(), buf.dtype)
+        if self.mx8:
+            header = M.make_header(M.MessageCode.GradientUpdate, dist.get_rank(), step,
+                                   self.version, self.opt.acc.numel(), M.MX8)
+        else:
+            header = M.make_header(M.MessageCode.GradientUpdate, dist.get_rank(), step,
+                                   self.version, buf.numel(), buf.dtype)
         M.SENDS.add(dist.isend(header, self.ps_rank, group=self.ctrl, tag=M.TAG_HEADER), header)
         self._send_work[self._cur_slot] = self._send_payload(buf)
         self.pushes += 1

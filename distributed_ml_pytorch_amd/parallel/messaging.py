@@ -35,7 +35,11 @@ TAG_PAYLOAD = 12
 TAG_REPLY = 13
 HEADER_LEN = 6
 
-_DTYPES = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16}
+# header dtype of a block-scaled 8-bit push (parallel/wire8.py): ``nelem`` stays the
+# element count, the payload is ``wire8.layout(nelem).nbytes`` uint8 bytes
+MX8 = "mx8"
+
+_DTYPES = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16, 3: MX8}
 _DTYPE_CODES = {v: k for k, v in _DTYPES.items()}
 
 
@@ -134,8 +138,11 @@ def parse_header(h: torch.Tensor):
 
 
 def send_message(message_code, payload: torch.Tensor | None = None, dst: int = 0, step: int = 0,
-                 version: int = 0, group=None, tracker: SendTracker | None = None):
+                 version: int = 0, group=None, tracker: SendTracker | None = None,
+                 nelem: int | None = None, dtype=None):
     """Fire-and-track send of a header (+ payload) to ``dst`` (default: the PS, rank 0).
+    ``nelem`` / ``dtype``: what the header says when the payload is not one tensor
+    element per element (:data:`MX8`: uint8 bytes of ``nelem`` quantised elements).
 
     Signature-compatible with the reference's ``send_message(code, payload)``
     call sites (Asynchronous.py:34,49,59); a ParameterRequest's payload is
@@ -145,14 +152,26 @@ def send_message(message_code, payload: torch.Tensor | None = None, dst: int = 0
     rank = dist.get_rank()
     if message_code == MessageCode.ParameterRequest:
         payload = None
-    nelem = 0 if payload is None else payload.numel()
-    dt = torch.float32 if payload is None else payload.dtype
+    if nelem is None:
+        nelem = 0 if payload is None else payload.numel()
+    if payload is None:
+        nelem = 0
+    dt = dtype if dtype is not None else (torch.float32 if payload is None else payload.dtype)
     header = make_header(message_code, rank, step, version, nelem, dt)
     works = [tracker.add(dist.isend(header, dst, group=group, tag=TAG_HEADER), header)]
     if nelem:
         buf = payload.detach().contiguous()
         works.append(tracker.add(dist.isend(buf, dst, group=group, tag=TAG_PAYLOAD), buf))
     return works
+
+
+def payload_buffer(nelem: int, dtype, device=None) -> torch.Tensor:
+    """An empty receive buffer for the payload a header announces."""
+    if dtype == MX8:
+        from .wire8 import layout
+
+        return torch.empty(layout(nelem)[2], dtype=torch.uint8, device=device)
+    return torch.empty(nelem, dtype=dtype, device=device)
 
 
 def recv_header(src: int | None = None, group=None):
@@ -194,7 +213,7 @@ class MessageListener(threading.Thread):
                 code, sender, step, version, nelem, dt = recv_header(self.src, self.group)
                 payload = None
                 if nelem:
-                    payload = torch.empty(nelem, dtype=dt)
+                    payload = payload_buffer(nelem, dt)
                     dist.recv(payload, src=sender, group=self.group, tag=TAG_PAYLOAD)
                 if code == MessageCode.Shutdown:
                     break

@@ -42,6 +42,7 @@ import torch
 import torch.distributed as dist
 
 from . import messaging as M
+from . import wire8
 from .arena import FlatArena
 from .links import AppliedCount, PairGroupTransport, PairLinks, wait_on
 from .staleness import DeviceStaleLog, StalenessGate
@@ -155,6 +156,8 @@ class ParameterServer:
             for w in self.workers:
                 for dt in (torch.float32, torch.bfloat16):
                     self.links.reserve(w, self.numel, dt, alloc=padded)
+                if self._mx8_ok():
+                    self.links.reserve(w, wire8.layout(self.numel)[2], torch.uint8)
                 self.links.reserve(w, self.numel + 1, torch.float32, send=True)
             torch.cuda.synchronize(self.device)
         if self.device.type == "cuda":
@@ -175,6 +178,19 @@ class ParameterServer:
         if self.links is not None:
             self._warm_kernels(padded)
 
+    def _mx8_ok(self) -> bool:
+        """The MX8 kernels take whole float4 items (every model arena is a
+        multiple of 64 elements); the CPU path takes any length."""
+        return self.device.type != "cuda" or self.numel % 4 == 0
+
+    def _ps_apply(self, delta: torch.Tensor, atomic: bool = False, factor=None):
+        """``shard += delta_scale [* factor] * delta`` on the current stream; a
+        ``uint8`` delta is an MX8 payload (:mod:`.wire8`)."""
+        if delta.dtype == torch.uint8:
+            self._native.ps_apply_mx8(self.shard, delta, None, self.delta_scale, atomic, factor)
+        else:
+            self._native.ps_apply(self.shard, delta, None, self.delta_scale, atomic, factor)
+
     def _warm_kernels(self, padded: int):
         """Launch every kernel of the apply / reply path once, before any transfer.
         HIP loads a kernel's code object at its first launch, and that load waited
@@ -190,6 +206,16 @@ class ParameterServer:
                     one = torch.ones(2, device=self.device)
                     self._native.ps_apply(self.shard, z, None, self.delta_scale, False, one)
                     self._native.ps_apply(self.shard, z, None, self.delta_scale, True, one)
+            if self._mx8_ok():
+                # an all-zero payload: codes 0 at scale 2^-127, adds +0
+                z = torch.zeros(wire8.layout(self.numel)[2], dtype=torch.uint8,
+                                device=self.device)
+                self._ps_apply(z)
+                self._ps_apply(z, True)
+                if self.stale_dev is not None:
+                    one = torch.ones(2, device=self.device)
+                    self._ps_apply(z, False, one)
+                    self._ps_apply(z, True, one)
             if self.stale_dev is not None:
                 # a log of its own: the warm-up launch is no apply
                 warm = DeviceStaleLog(self.device, self._native, self.applied, 0)
@@ -210,7 +236,15 @@ class ParameterServer:
         if nelem != self.numel:
             raise RuntimeError(f"PS: worker {sender} sent {nelem} elements, the shard has "
                                f"{self.numel} (model/arena layout mismatch)")
-        padded = nelem + ((-nelem) % 4)
+        if dtype == M.MX8:
+            # a block-scaled 8-bit push: layout(nelem) bytes, no padding of its own
+            if not self._mx8_ok():
+                raise RuntimeError(f"PS: an MX8 push needs a shard length that is a multiple "
+                                   f"of 4 on the GPU, the shard has {self.numel}")
+            nelem = padded = wire8.layout(nelem)[2]
+            dtype = torch.uint8
+        else:
+            padded = nelem + ((-nelem) % 4)
         self.bytes_in += nelem * torch.empty(0, dtype=dtype).element_size()
         if self.links is not None:
             slot, ready = self.links.recv(sender, nelem, dtype, alloc=padded)
@@ -275,7 +309,7 @@ class ParameterServer:
             with torch.cuda.stream(s):
                 wait_on(s, ready)
                 wait_on(s, self._init_ev)
-                self._native.ps_apply(self.shard, delta, None, self.delta_scale, True)
+                self._ps_apply(delta, True)
                 self.applied.bump()            # counted once this apply has landed
                 if slot is not None:
                     self.links.release(slot, s)
@@ -283,14 +317,15 @@ class ParameterServer:
         elif self._native is not None:
             with torch.cuda.stream(self.stream):
                 wait_on(self.stream, ready)
-                self._native.ps_apply(self.shard, delta, None, self.delta_scale)
+                self._ps_apply(delta)
                 self.applied.bump()
                 if slot is not None:
                     self.links.release(slot, self.stream)
         else:
             f = self.gate.note_push(sender, tau) if base is not None else 1.0
-            self.shard[: self.numel].add_(delta[: self.numel].to(torch.float32),
-                                          alpha=self.delta_scale * f)
+            d32 = wire8.dequantize(delta, self.numel) if delta.dtype == torch.uint8 else \
+                delta[: self.numel].to(torch.float32)
+            self.shard[: self.numel].add_(d32, alpha=self.delta_scale * f)
             self.applied.bump()
         self.version += 1
 
@@ -305,7 +340,7 @@ class ParameterServer:
             if links:
                 wait_on(s, self._init_ev)
             fac = self.stale_dev.factor(sender if links else None, base, cap=self.version)
-            self._native.ps_apply(self.shard, delta, None, self.delta_scale, links, fac)
+            self._ps_apply(delta, links, fac)
             self.applied.bump()
             if slot is not None:
                 self.links.release(slot, s)
@@ -345,6 +380,9 @@ class ParameterServer:
             if self.checkpoint_every and self.version % self.checkpoint_every == 0:
                 self.save_checkpoint()
         elif code == M.MessageCode.ParameterUpdate:
+            if dtype == M.MX8:
+                raise RuntimeError(f"PS: worker {sender} sent parameters on the MX8 wire; only "
+                                   "pushed deltas are quantised")
             params, ready, slot = self._recv_payload(sender, nelem, dtype)
             if not self.initialized or self.init_policy == "last":
                 self._set(params, ready, slot)

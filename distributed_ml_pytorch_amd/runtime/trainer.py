@@ -35,7 +35,8 @@ from ..ops.functional import softmax_cross_entropy, unit_grad
 from ..parallel.arena import attach_arena
 from ..parallel.asgd import Asynchronous
 from ..parallel.async_sharded import AsyncShardedPSClient
-from ..parallel.clients import (GlooPSClient, LocalPSClient, RcclPSClient, ShardedPSClient)
+from ..parallel.clients import (MX8_FLAVOURS, GlooPSClient, LocalPSClient, RcclPSClient,
+                                ShardedPSClient, check_push_wire)
 from ..parallel.ddp import BucketedAllReduce, FusedAdamW, FusedSGD
 from ..parallel.fused_optim import Schedule
 from ..parallel.server import ParameterServer, make_ps_groups
@@ -83,6 +84,7 @@ class TrainConfig:
     staleness: int = 1
     pull_mode: str = "overwrite"
     wire_dtype: str = "fp32"
+    push_wire: str = "same"           # same | mx8 (parallel/wire8.py; local and central PS only)
     mode: str = "asgd"                # asgd | sync | single
     ps: str = "central"               # central | sharded | sharded_async | local
     payload: str = "auto"             # central PS payload transport: gloo | rccl | auto
@@ -122,6 +124,7 @@ class Worker:
         self.cfg = cfg
         self.info = info
         check_stale_config(cfg, info)
+        check_push_wire_config(cfg, client)
         if cfg.deterministic:
             cfg = self.cfg = enable_determinism(cfg)
         torch.manual_seed(cfg.seed + info.rank)
@@ -178,6 +181,8 @@ class Worker:
             client = client if client is not None else self._make_client(ps_groups)
             if cfg.optimizer == "adamw":
                 okw.update(optimizer="adamw", **adam)
+            if cfg.push_wire != "same":      # an explicit client takes the configured wire too
+                okw["push_wire"] = cfg.push_wire
             self.opt = Asynchronous(params, lr=cfg.lr, n_push=cfg.n_push, n_pull=cfg.n_pull,
                                     model=self.model, client=client, momentum=cfg.momentum,
                                     weight_decay=cfg.weight_decay, **okw)
@@ -210,7 +215,7 @@ class Worker:
     def _make_client(self, ps_groups):
         cfg, info = self.cfg, self.info
         kw = dict(staleness=cfg.staleness, pull_mode=cfg.pull_mode,
-                  wire_dtype=_dtype(cfg.wire_dtype))
+                  wire_dtype=_dtype(cfg.wire_dtype), push_wire=cfg.push_wire)
         if cfg.ps == "local" or not info.is_distributed:
             return LocalPSClient(**kw)
         if cfg.ps == "sharded":
@@ -449,6 +454,23 @@ def check_stale_config(cfg: TrainConfig, info: DistInfo):
             "(the local PS has one worker, the collective sharded PS is lock-step)")
 
 
+def check_push_wire_config(cfg: TrainConfig, client=None):
+    """The 8-bit push wire exists where one worker's push reaches one server:
+    the local PS and the central PS.  Anywhere else it is an error at start-up."""
+    if check_push_wire(cfg.push_wire) == "same":
+        return
+    what = None
+    if cfg.mode != "asgd":
+        what = f"--mode {cfg.mode}"
+    elif client is not None and not client.MX8_WIRE:
+        what = f"{type(client).__name__} (virtual workers)"
+    elif client is None and cfg.ps in ("sharded", "sharded_async"):
+        what = f"--ps {cfg.ps}"
+    if what:
+        raise ValueError(f"--push-wire mx8 is not supported with {what}: the 8-bit push wire "
+                         f"runs on {MX8_FLAVOURS}")
+
+
 def _payload(cfg: TrainConfig, info: DistInfo) -> str:
     if cfg.payload != "auto":
         return cfg.payload
@@ -482,6 +504,7 @@ def run_server(cfg: TrainConfig, info: DistInfo, ps_groups):
 def run_training(cfg: TrainConfig, info: DistInfo):
     """Entry point for every rank. Returns a result dict (worker) or PS stats."""
     check_stale_config(cfg, info)
+    check_push_wire_config(cfg)
     ps_groups = None
     central = cfg.mode == "asgd" and cfg.ps == "central" and info.is_distributed
     if central:
