@@ -101,10 +101,19 @@ void adamw_fused_step(Tensor g, Tensor p, optional<Tensor> acc, Tensor m, Tensor
                                (float)wd, (float)eps, cur_stream());
 }
 
-// `factor`: the {factor, tau} slot ps_stale_factor wrote on the current stream
-// (staleness damping: scale * factor is applied); None = the plain apply
-void ps_apply(Tensor shard, Tensor delta, optional<Tensor> mirror, double scale, bool atomic,
-              optional<Tensor> factor) {
+// fp32 or bf16 wire payload of n elements (`name`s it in the message)
+dmp::Wire dense_wire(const Tensor& t, int64_t n, const char* name) {
+  const bool bf = t.scalar_type() != at::kFloat;
+  check_flat(t, bf ? at::kBFloat16 : at::kFloat, n, name);
+  return {bf ? dmp::Wire::kBF16 : dmp::Wire::kF32, t.data_ptr()};
+}
+
+// What every apply checks before its payload (`fn` prefixes the messages): the
+// shard, the optional bf16 mirror, the staleness factor, and that an atomic
+// apply (concurrent on several streams) takes no mirror: it would race.
+// -> the shard length
+int64_t check_apply(const char* fn, const Tensor& shard, const optional<Tensor>& mirror,
+                    bool atomic, const optional<Tensor>& factor) {
   const int64_t n = flat_len(shard, "shard length");
   check_flat(shard, at::kFloat, n, "shard");
   check_flat_opt(mirror, at::kBFloat16, n, "mirror");
@@ -112,24 +121,19 @@ void ps_apply(Tensor shard, Tensor delta, optional<Tensor> mirror, double scale,
     TORCH_CHECK(factor->is_cuda() && factor->scalar_type() == at::kFloat &&
                     factor->numel() >= 1 && factor->is_contiguous() &&
                     factor->device() == shard.device(),
-                "ps_apply: factor must be a contiguous fp32 tensor on the shard's device");
-  const float* fac = ptr_or_null<const float>(factor);
-  const bool bf = delta.scalar_type() == at::kBFloat16;
-  if (atomic) {
-    // concurrent applies on several streams: no mirror (it would race)
-    TORCH_CHECK(!has(mirror), "ps_apply: atomic applies take no bf16 mirror");
-    check_flat(delta, bf ? at::kBFloat16 : at::kFloat, n, "delta");
-    dmp::launch_ps_apply_atomic(shard.data_ptr<float>(), delta.data_ptr(), bf, n, (float)scale,
-                                cur_stream(), fac);
-  } else if (delta.scalar_type() == at::kFloat) {
-    check_flat(delta, at::kFloat, n, "delta");
-    dmp::launch_ps_apply_f32(shard.data_ptr<float>(), delta.data_ptr<float>(),
-                             bf16_or_null(mirror), n, (float)scale, cur_stream(), fac);
-  } else {
-    check_flat(delta, at::kBFloat16, n, "delta");
-    dmp::launch_ps_apply_bf16(shard.data_ptr<float>(), bf16(delta), bf16_or_null(mirror), n,
-                              (float)scale, cur_stream(), fac);
-  }
+                fn, ": factor must be a contiguous fp32 tensor on the shard's device");
+  TORCH_CHECK(!(atomic && has(mirror)), fn, ": atomic applies take no bf16 mirror");
+  return n;
+}
+
+// `factor`: the {factor, tau} slot ps_stale_factor wrote on the current stream
+// (staleness damping: scale * factor is applied); None = the plain apply
+void ps_apply(Tensor shard, Tensor delta, optional<Tensor> mirror, double scale, bool atomic,
+              optional<Tensor> factor) {
+  const int64_t n = check_apply("ps_apply", shard, mirror, atomic, factor);
+  dmp::launch_ps_apply(shard.data_ptr<float>(), dense_wire(delta, n, "delta"),
+                       bf16_or_null(mirror), n, (float)scale, atomic, cur_stream(),
+                       ptr_or_null<const float>(factor));
 }
 
 // PS applied-count (server.py / async_sharded.py version stamps): ps_count adds
@@ -181,15 +185,8 @@ void pull_land(Tensor p, Tensor src, optional<Tensor> acc, optional<Tensor> w16)
   check_flat(p, at::kFloat, n, "p");
   check_flat_opt(acc, at::kFloat, n, "acc");
   check_flat_opt(w16, at::kBFloat16, n, "w16");
-  if (src.scalar_type() == at::kFloat) {
-    check_flat(src, at::kFloat, n, "src");
-    dmp::launch_pull_land_f32(p.data_ptr<float>(), src.data_ptr<float>(), ptr_or_null<float>(acc),
-                              bf16_or_null(w16), n, cur_stream());
-  } else {
-    check_flat(src, at::kBFloat16, n, "src");
-    dmp::launch_pull_land_bf16(p.data_ptr<float>(), bf16(src), ptr_or_null<float>(acc),
-                               bf16_or_null(w16), n, cur_stream());
-  }
+  dmp::launch_pull_land(p.data_ptr<float>(), dense_wire(src, n, "src"), ptr_or_null<float>(acc),
+                        bf16_or_null(w16), n, cur_stream());
 }
 
 void push_handoff(Tensor acc, optional<Tensor> out32, optional<Tensor> out16) {
@@ -230,19 +227,11 @@ void push_handoff_mx8(Tensor acc, Tensor payload) {
 // ps_apply for an MX8 payload: the same three shapes (plain + mirror, atomic, factor)
 void ps_apply_mx8(Tensor shard, Tensor payload, optional<Tensor> mirror, double scale, bool atomic,
                   optional<Tensor> factor) {
-  const int64_t n = flat_len(shard, "shard length");
-  check_flat(shard, at::kFloat, n, "shard");
+  const int64_t n = check_apply("ps_apply_mx8", shard, mirror, atomic, factor);
   TORCH_CHECK(shard.is_contiguous(), "shard must be contiguous");
-  check_flat_opt(mirror, at::kBFloat16, n, "mirror");
-  if (has(factor))
-    TORCH_CHECK(factor->is_cuda() && factor->scalar_type() == at::kFloat &&
-                    factor->numel() >= 1 && factor->is_contiguous() &&
-                    factor->device() == shard.device(),
-                "ps_apply_mx8: factor must be a contiguous fp32 tensor on the shard's device");
-  TORCH_CHECK(!(atomic && has(mirror)), "ps_apply_mx8: atomic applies take no bf16 mirror");
   const uint8_t* in = mx8_payload(payload, n, shard, "ps_apply_mx8");
-  dmp::launch_ps_apply_mx8(shard.data_ptr<float>(), in, bf16_or_null(mirror), n, (float)scale,
-                           atomic, cur_stream(), ptr_or_null<const float>(factor));
+  dmp::launch_ps_apply(shard.data_ptr<float>(), {dmp::Wire::kMX8, in}, bf16_or_null(mirror), n,
+                       (float)scale, atomic, cur_stream(), ptr_or_null<const float>(factor));
 }
 
 void cast_f32_bf16(Tensor src, Tensor dst) {

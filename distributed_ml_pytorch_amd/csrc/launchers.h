@@ -23,31 +23,30 @@ void launch_asgd_fused_step_dev(const float* g, float* p, float* acc, float* mom
 void launch_adamw_fused_step(const float* g, float* p, float* acc, float* m, float* v,
                              uint16_t* w16, const uint8_t* decay, long long n, const float* hyper,
                              float wd, float eps, hipStream_t s);
-// `factor`: one device fp32 published by launch_ps_stale_factor on the same
-// stream (staleness damping); null = the plain apply
-void launch_ps_apply_atomic(float* shard, const void* delta, bool bf16, long long n, float scale,
-                            hipStream_t s, const float* factor = nullptr);
-void launch_ps_apply_f32(float* shard, const float* delta, uint16_t* mirror, long long n,
-                         float scale, hipStream_t s, const float* factor = nullptr);
-void launch_ps_apply_bf16(float* shard, const uint16_t* delta, uint16_t* mirror, long long n,
-                          float scale, hipStream_t s, const float* factor = nullptr);
+// A payload on the wire: n fp32 or bf16 elements, or the MX8 payload of n
+// elements (mx8_layout(n) bytes, 16-B aligned, n % 4 == 0; parallel/wire8.py)
+struct Wire {
+  enum Kind { kF32, kBF16, kMX8 } kind;
+  const void* data;
+};
+// shard += scale * delta.  `atomic`: fp32 atomics (concurrent applies on several
+// streams; no mirror).  `factor`: one device fp32 published by
+// launch_ps_stale_factor on the same stream (staleness damping); null = undamped
+void launch_ps_apply(float* shard, Wire delta, uint16_t* mirror, long long n, float scale,
+                     bool atomic, hipStream_t s, const float* factor = nullptr);
 void launch_ps_count(int* cnt, int add, bool set, hipStream_t s);
 void launch_ps_stamp(int* cnt, float* dst, hipStream_t s);
 int stale_log_numel();
 void launch_ps_stale_factor(int* cnt, int base, int bound, int cap, float* slot, int* log,
                             hipStream_t s);
-void launch_pull_land_f32(float* p, const float* src, const float* acc, uint16_t* w16,
-                          long long n, hipStream_t s);
-void launch_pull_land_bf16(float* p, const uint16_t* src, const float* acc, uint16_t* w16,
-                           long long n, hipStream_t s);
+void launch_pull_land(float* p, Wire src, const float* acc, uint16_t* w16, long long n,
+                      hipStream_t s);   // src: kF32 or kBF16
 void launch_push_handoff(float* acc, float* out32, uint16_t* out16, long long n, hipStream_t s);
 // Block-scaled 8-bit push wire (MXFP8; parallel/wire8.py).  mx8_layout: bytes of
 // the payload of n elements (codes at 0, scale bytes at *scales_off), -1 for a
 // length out of range.  The kernels take n % 4 == 0 and a 16-B aligned payload.
 long long mx8_layout(long long n, long long* scales_off);
 void launch_push_handoff_mx8(float* acc, uint8_t* payload, long long n, hipStream_t s);
-void launch_ps_apply_mx8(float* shard, const uint8_t* payload, uint16_t* mirror, long long n,
-                         float scale, bool atomic, hipStream_t s, const float* factor = nullptr);
 void launch_cast_f32_bf16(const float* src, uint16_t* dst, long long n, hipStream_t s);
 int launch_sumsq_partial(const float* x, float* partial, long long n, hipStream_t s);
 void launch_zero_fill(void* p, long long bytes, hipStream_t s);

@@ -13,10 +13,19 @@
 // All buffers are padded by the arena to a multiple of 64 elements and are
 // 256-B aligned, so n % 4 == 0 always holds (asserted on the host side).
 #include "common.h"
+#include "launchers.h"
 
 #include <algorithm>
 
 namespace dmp {
+
+// dst[i] = bf16(v): four round-to-nearest-even casts, one 8-B store
+__device__ __forceinline__ void store_bf16x4(bf16x4* __restrict__ dst, long long i,
+                                             const float4& v) {
+  bf16x4 o;
+  o.v[0] = f2bf(v.x); o.v[1] = f2bf(v.y); o.v[2] = f2bf(v.z); o.v[3] = f2bf(v.w);
+  dst[i] = o;
+}
 
 // One grid-stride pass of the SGD update, shared by the two kernels below.
 // `gscale` (device-hyper variant only, SCALE = true) multiplies the gradient
@@ -61,11 +70,7 @@ __device__ __forceinline__ void asgd_fused_step_body(
     }
     pv.x += d.x; pv.y += d.y; pv.z += d.z; pv.w += d.w;
     p[i] = pv;
-    if (w16) {
-      bf16x4 o;
-      o.v[0] = f2bf(pv.x); o.v[1] = f2bf(pv.y); o.v[2] = f2bf(pv.z); o.v[3] = f2bf(pv.w);
-      w16[i] = o;
-    }
+    if (w16) store_bf16x4(w16, i, pv);
   }
 }
 
@@ -230,82 +235,7 @@ __global__ void __launch_bounds__(256) adamw_fused_step_kernel(
       a.x += pn.x - p0.x; a.y += pn.y - p0.y; a.z += pn.z - p0.z; a.w += pn.w - p0.w;
       acc[i] = a;
     }
-    if (w16) {
-      bf16x4 o;
-      o.v[0] = f2bf(pn.x); o.v[1] = f2bf(pn.y); o.v[2] = f2bf(pn.z); o.v[3] = f2bf(pn.w);
-      w16[i] = o;
-    }
-  }
-}
-
-// Staleness damping (parallel/staleness.py, policy "damp"): an apply may take a
-// pointer to ONE fp32 factor that ps_stale_factor_kernel (below) published on
-// the same stream before this kernel started.  Every thread loads it once (an
-// agent-scope load: served by L2, the same word for the whole grid) and uses
-// scale * factor; a null pointer is the undamped apply.
-__device__ __forceinline__ float ps_scale(float scale, const float* factor) {
-  return factor ? scale * __hip_atomic_load(factor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-                : scale;
-}
-
-// shard += scale * delta (fp32 delta)      -- PS GradientUpdate apply
-// optional: mirror the new shard into bf16 for low-precision pulls.
-__global__ void __launch_bounds__(256) ps_apply_f32_kernel(
-    float4* __restrict__ shard, const float4* __restrict__ delta, bf16x4* __restrict__ mirror,
-    long long n4, float scale, const float* factor = nullptr) {
-  scale = ps_scale(scale, factor);
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 s = shard[i];
-    const float4 d = delta[i];
-    s.x += scale * d.x; s.y += scale * d.y; s.z += scale * d.z; s.w += scale * d.w;
-    shard[i] = s;
-    if (mirror) {
-      bf16x4 o;
-      o.v[0] = f2bf(s.x); o.v[1] = f2bf(s.y); o.v[2] = f2bf(s.z); o.v[3] = f2bf(s.w);
-      mirror[i] = o;
-    }
-  }
-}
-
-// shard += scale * delta (bf16 wire-format delta)
-__global__ void __launch_bounds__(256) ps_apply_bf16_kernel(
-    float4* __restrict__ shard, const bf16x4* __restrict__ delta, bf16x4* __restrict__ mirror,
-    long long n4, float scale, const float* factor = nullptr) {
-  scale = ps_scale(scale, factor);
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 s = shard[i];
-    const bf16x4 d = delta[i];
-    s.x += scale * bf2f(d.v[0]); s.y += scale * bf2f(d.v[1]);
-    s.z += scale * bf2f(d.v[2]); s.w += scale * bf2f(d.v[3]);
-    shard[i] = s;
-    if (mirror) {
-      bf16x4 o;
-      o.v[0] = f2bf(s.x); o.v[1] = f2bf(s.y); o.v[2] = f2bf(s.z); o.v[3] = f2bf(s.w);
-      mirror[i] = o;
-    }
-  }
-}
-
-// shard += scale * delta with fp32 global atomics (no-return
-// global_atomic_add_f32): the completion-ordered PS applies each worker's delta
-// on that worker's own link stream, so applies of different workers may run at
-// the same time on one shard (SURVEY §7.3(3): "or use fp32 atomics").  Lane i
-// of a wave adds element base + i: every wave-instruction covers 256 contiguous
-// bytes, the full-rate shape of MI355X_MICROARCH.md §Global float atomics.
-template <typename D>
-__global__ void __launch_bounds__(256) ps_apply_atomic_kernel(float* __restrict__ shard,
-                                                              const D* __restrict__ delta,
-                                                              long long n, float scale,
-                                                              const float* factor = nullptr) {
-  scale = ps_scale(scale, factor);
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    float d;
-    if constexpr (sizeof(D) == 4) d = delta[i];
-    else d = bf2f(delta[i]);
-    unsafeAtomicAdd(shard + i, scale * d);
+    if (w16) store_bf16x4(w16, i, pn);
   }
 }
 
@@ -379,49 +309,6 @@ __global__ void __launch_bounds__(64) ps_stale_factor_kernel(int* __restrict__ c
   }
 }
 
-// Pull landing: p = src (fp32 or bf16 wire), w16 = bf16(p). Optionally the
-// delta the worker accumulated since the snapshot is re-applied on top
-// (keep_local: p = src + acc), which keeps not-yet-pushed local progress
-// instead of discarding it (the reference overwrote it, SURVEY.md D13).
-__global__ void __launch_bounds__(256) pull_land_f32_kernel(
-    float4* __restrict__ p, const float4* __restrict__ src, const float4* __restrict__ acc,
-    bf16x4* __restrict__ w16, long long n4) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    float4 v = src[i];
-    if (acc) {
-      const float4 a = acc[i];
-      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-    }
-    p[i] = v;
-    if (w16) {
-      bf16x4 o;
-      o.v[0] = f2bf(v.x); o.v[1] = f2bf(v.y); o.v[2] = f2bf(v.z); o.v[3] = f2bf(v.w);
-      w16[i] = o;
-    }
-  }
-}
-
-__global__ void __launch_bounds__(256) pull_land_bf16_kernel(
-    float4* __restrict__ p, const bf16x4* __restrict__ src, const float4* __restrict__ acc,
-    bf16x4* __restrict__ w16, long long n4) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const bf16x4 s = src[i];
-    float4 v = make_float4(bf2f(s.v[0]), bf2f(s.v[1]), bf2f(s.v[2]), bf2f(s.v[3]));
-    if (acc) {
-      const float4 a = acc[i];
-      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-    }
-    p[i] = v;
-    if (w16) {
-      bf16x4 o;
-      o.v[0] = f2bf(v.x); o.v[1] = f2bf(v.y); o.v[2] = f2bf(v.z); o.v[3] = f2bf(v.w);
-      w16[i] = o;
-    }
-  }
-}
-
 // Push hand-off: out = acc (fp32 or bf16 wire), acc = 0. One pass replaces the
 // reference's "send(acc); acc.zero_()" (Asynchronous.py:58-60) and makes the
 // send buffer a private snapshot so the next step may keep accumulating.
@@ -433,11 +320,7 @@ __global__ void __launch_bounds__(256) push_handoff_kernel(
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     const float4 a = acc[i];
     if (out32) out32[i] = a;
-    if (out16) {
-      bf16x4 o;
-      o.v[0] = f2bf(a.x); o.v[1] = f2bf(a.y); o.v[2] = f2bf(a.z); o.v[3] = f2bf(a.w);
-      out16[i] = o;
-    }
+    if (out16) store_bf16x4(out16, i, a);
     acc[i] = z;
   }
 }
@@ -538,45 +421,123 @@ __global__ void __launch_bounds__(256) push_handoff_mx8_kernel(
   }
 }
 
-// shard += scale * dequant(payload) (MX8 wire), optional bf16 mirror: the
-// shape of ps_apply_bf16_kernel with 4 code bytes and the block's scale byte
-// (8 float4 items per block) in place of the bf16x4.
-__global__ void __launch_bounds__(256) ps_apply_mx8_kernel(
-    float4* __restrict__ shard, const u8* __restrict__ payload, bf16x4* __restrict__ mirror,
-    long long n4, long long scales_off, float scale, const float* factor = nullptr) {
+// ---- wire readers: how a payload on the wire becomes fp32 ----------------------
+// One per format.  A reader knows
+//   load4(i)  float4 item i, the plain 16-B-per-lane shape;
+//   load1(i)  element i, the atomic one-element-per-lane shape;
+//   axpy      how s + scale * d is formed in the plain apply.  This is where the
+//             bit-for-bit claims of a wire live.  fp32 and bf16: the plain
+//             expression, which the compiler contracts into one fused
+//             multiply-add (one rounding).  MX8: mx8_axpy, contraction off, the
+//             product and the sum rounded separately -- the value the atomic
+//             form and the CPU path (parallel/wire8.py) give.
+// The atomic apply rounds scale * d on its own and adds it in memory: two
+// roundings on every wire.
+struct WireF32 {
+  const float* __restrict__ p;
+  __device__ __forceinline__ float4 load4(long long i) const {
+    return reinterpret_cast<const float4*>(p)[i];
+  }
+  __device__ __forceinline__ float load1(long long i) const { return p[i]; }
+  static __device__ __forceinline__ float axpy(float s, float scale, float d) {
+    return s + scale * d;
+  }
+};
+
+struct WireBF16 {
+  const u16* __restrict__ p;
+  __device__ __forceinline__ float4 load4(long long i) const {
+    const bf16x4 d = reinterpret_cast<const bf16x4*>(p)[i];
+    return make_float4(bf2f(d.v[0]), bf2f(d.v[1]), bf2f(d.v[2]), bf2f(d.v[3]));
+  }
+  __device__ __forceinline__ float load1(long long i) const { return bf2f(p[i]); }
+  static __device__ __forceinline__ float axpy(float s, float scale, float d) {
+    return s + scale * d;
+  }
+};
+
+// 4 code bytes as one dword and the block's scale byte (8 float4 items, 32
+// elements per block)
+struct WireMX8 {
+  const u8* __restrict__ p;
+  long long scales_off;
+  __device__ __forceinline__ float4 load4(long long i) const {
+    const u32 c = reinterpret_cast<const u32*>(p)[i];
+    const int sb = p[scales_off + (i >> 3)];
+    const bool nan = sb == 255;
+    return make_float4(mx8_decode(c, 0, sb - 127, nan), mx8_decode(c, 1, sb - 127, nan),
+                       mx8_decode(c, 2, sb - 127, nan), mx8_decode(c, 3, sb - 127, nan));
+  }
+  __device__ __forceinline__ float load1(long long i) const {
+    const int sb = p[scales_off + (i >> 5)];
+    return mx8_decode(p[i], 0, sb - 127, sb == 255);
+  }
+  static __device__ __forceinline__ float axpy(float s, float scale, float d) {
+    return mx8_axpy(s, scale, d);
+  }
+};
+
+// Staleness damping (parallel/staleness.py, policy "damp"): an apply may take a
+// pointer to ONE fp32 factor that ps_stale_factor_kernel (above) published on
+// the same stream before this kernel started.  Every thread loads it once (an
+// agent-scope load: served by L2, the same word for the whole grid) and uses
+// scale * factor; a null pointer is the undamped apply.
+__device__ __forceinline__ float ps_scale(float scale, const float* factor) {
+  return factor ? scale * __hip_atomic_load(factor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                : scale;
+}
+
+// shard += scale * delta      -- PS GradientUpdate apply
+// optional: mirror the new shard into bf16 for low-precision pulls.
+template <typename W>
+__global__ void __launch_bounds__(256) ps_apply_kernel(float4* __restrict__ shard, const W delta,
+                                                       bf16x4* __restrict__ mirror, long long n4,
+                                                       float scale, const float* factor) {
   scale = ps_scale(scale, factor);
-  const u32* __restrict__ codes = reinterpret_cast<const u32*>(payload);
-  const u8* __restrict__ scales = payload + scales_off;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
     float4 s = shard[i];
-    const u32 c = codes[i];
-    const int sb = scales[i >> 3];
-    const bool nan = sb == 255;
-    s.x = mx8_axpy(s.x, scale, mx8_decode(c, 0, sb - 127, nan));
-    s.y = mx8_axpy(s.y, scale, mx8_decode(c, 1, sb - 127, nan));
-    s.z = mx8_axpy(s.z, scale, mx8_decode(c, 2, sb - 127, nan));
-    s.w = mx8_axpy(s.w, scale, mx8_decode(c, 3, sb - 127, nan));
+    const float4 d = delta.load4(i);
+    s.x = W::axpy(s.x, scale, d.x); s.y = W::axpy(s.y, scale, d.y);
+    s.z = W::axpy(s.z, scale, d.z); s.w = W::axpy(s.w, scale, d.w);
     shard[i] = s;
-    if (mirror) {
-      bf16x4 o;
-      o.v[0] = f2bf(s.x); o.v[1] = f2bf(s.y); o.v[2] = f2bf(s.z); o.v[3] = f2bf(s.w);
-      mirror[i] = o;
-    }
+    if (mirror) store_bf16x4(mirror, i, s);
   }
 }
 
-// The atomic form (completion-ordered link streams): one element per lane, as
-// ps_apply_atomic_kernel -- every wave-instruction adds 256 contiguous bytes.
-__global__ void __launch_bounds__(256) ps_apply_mx8_atomic_kernel(
-    float* __restrict__ shard, const u8* __restrict__ payload, long long n, long long scales_off,
-    float scale, const float* factor = nullptr) {
+// shard += scale * delta with fp32 global atomics (no-return
+// global_atomic_add_f32): the completion-ordered PS applies each worker's delta
+// on that worker's own link stream, so applies of different workers may run at
+// the same time on one shard (SURVEY §7.3(3): "or use fp32 atomics").  Lane i
+// of a wave adds element base + i: every wave-instruction covers 256 contiguous
+// bytes, the full-rate shape of MI355X_MICROARCH.md §Global float atomics.
+template <typename W>
+__global__ void __launch_bounds__(256) ps_apply_atomic_kernel(float* __restrict__ shard,
+                                                              const W delta, long long n,
+                                                              float scale, const float* factor) {
   scale = ps_scale(scale, factor);
-  const u8* __restrict__ scales = payload + scales_off;
   const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int sb = scales[i >> 5];
-    unsafeAtomicAdd(shard + i, scale * mx8_decode(payload[i], 0, sb - 127, sb == 255));
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    unsafeAtomicAdd(shard + i, scale * delta.load1(i));
+}
+
+// Pull landing: p = src (fp32 or bf16 wire), w16 = bf16(p). Optionally the
+// delta the worker accumulated since the snapshot is re-applied on top
+// (keep_local: p = src + acc), which keeps not-yet-pushed local progress
+// instead of discarding it (the reference overwrote it, SURVEY.md D13).
+template <typename W>
+__global__ void __launch_bounds__(256) pull_land_kernel(float4* __restrict__ p, const W src,
+                                                        const float4* __restrict__ acc,
+                                                        bf16x4* __restrict__ w16, long long n4) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 v = src.load4(i);
+    if (acc) {
+      const float4 a = acc[i];
+      v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+    }
+    p[i] = v;
+    if (w16) store_bf16x4(w16, i, v);
   }
 }
 
@@ -585,10 +546,7 @@ __global__ void __launch_bounds__(256) cast_f32_bf16_kernel(
     const float4* __restrict__ src, bf16x4* __restrict__ dst, long long n4) {
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const float4 a = src[i];
-    bf16x4 o;
-    o.v[0] = f2bf(a.x); o.v[1] = f2bf(a.y); o.v[2] = f2bf(a.z); o.v[3] = f2bf(a.w);
-    dst[i] = o;
+    store_bf16x4(dst, i, src[i]);
   }
 }
 
@@ -673,30 +631,39 @@ void launch_adamw_fused_step(const float* g, float* p, float* acc, float* m, flo
                      (bf16x4*)w16, decay, n4, hyper, wd, eps);
 }
 
-void launch_ps_apply_f32(float* shard, const float* delta, u16* mirror, long long n, float scale,
-                         hipStream_t s, const float* factor) {
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(ps_apply_f32_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                     (float4*)shard, (const float4*)delta, (bf16x4*)mirror, n4, scale, factor);
+// One launch shape per form: the plain apply takes 16 B per lane (stream_grid),
+// the atomic one an element per lane on at most 4096 blocks.
+template <typename W>
+static void ps_apply_as(float* shard, W delta, u16* mirror, long long n, float scale, bool atomic,
+                        hipStream_t s, const float* factor) {
+  if (atomic) {
+    const int grid = (int)std::min<long long>((n + 255) / 256, 256LL * 16);
+    hipLaunchKernelGGL(ps_apply_atomic_kernel<W>, dim3(grid), dim3(256), 0, s, shard, delta, n,
+                       scale, factor);
+  } else {
+    const long long n4 = n / 4;
+    hipLaunchKernelGGL(ps_apply_kernel<W>, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
+                       (float4*)shard, delta, (bf16x4*)mirror, n4, scale, factor);
+  }
 }
 
-void launch_ps_apply_bf16(float* shard, const u16* delta, u16* mirror, long long n, float scale,
-                          hipStream_t s, const float* factor) {
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(ps_apply_bf16_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                     (float4*)shard, (const bf16x4*)delta, (bf16x4*)mirror, n4, scale, factor);
-}
-
-void launch_ps_apply_atomic(float* shard, const void* delta, bool bf16, long long n, float scale,
-                            hipStream_t s, const float* factor) {
-  if (n <= 0) return;   // an empty shard: nothing to add (a 0-block grid is invalid)
-  const int grid = (int)std::min<long long>((n + 255) / 256, 256LL * 16);
-  if (bf16)
-    hipLaunchKernelGGL(ps_apply_atomic_kernel<u16>, dim3(grid), dim3(256), 0, s, shard,
-                       (const u16*)delta, n, scale, factor);
-  else
-    hipLaunchKernelGGL(ps_apply_atomic_kernel<float>, dim3(grid), dim3(256), 0, s, shard,
-                       (const float*)delta, n, scale, factor);
+void launch_ps_apply(float* shard, Wire delta, u16* mirror, long long n, float scale, bool atomic,
+                     hipStream_t s, const float* factor) {
+  // an empty shard: nothing to add (a 0-block grid is invalid; MX8 has no layout)
+  if (n <= 0 && (atomic || delta.kind == Wire::kMX8)) return;
+  long long so = 0;
+  switch (delta.kind) {
+    case Wire::kF32:
+      return ps_apply_as(shard, WireF32{(const float*)delta.data}, mirror, n, scale, atomic, s,
+                         factor);
+    case Wire::kBF16:
+      return ps_apply_as(shard, WireBF16{(const u16*)delta.data}, mirror, n, scale, atomic, s,
+                         factor);
+    case Wire::kMX8:
+      mx8_layout(n, &so);
+      return ps_apply_as(shard, WireMX8{(const u8*)delta.data, so}, mirror, n, scale, atomic, s,
+                         factor);
+  }
 }
 
 void launch_ps_count(int* cnt, int add, bool set, hipStream_t s) {
@@ -715,18 +682,16 @@ void launch_ps_stale_factor(int* cnt, int base, int bound, int cap, float* slot,
                      slot, log);
 }
 
-void launch_pull_land_f32(float* p, const float* src, const float* acc, u16* w16, long long n,
-                          hipStream_t s) {
+// src: fp32 or bf16 (parameters never travel as MX8)
+void launch_pull_land(float* p, Wire src, const float* acc, u16* w16, long long n, hipStream_t s) {
   const long long n4 = n / 4;
-  hipLaunchKernelGGL(pull_land_f32_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                     (float4*)p, (const float4*)src, (const float4*)acc, (bf16x4*)w16, n4);
-}
-
-void launch_pull_land_bf16(float* p, const u16* src, const float* acc, u16* w16, long long n,
-                           hipStream_t s) {
-  const long long n4 = n / 4;
-  hipLaunchKernelGGL(pull_land_bf16_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                     (float4*)p, (const bf16x4*)src, (const float4*)acc, (bf16x4*)w16, n4);
+  const dim3 grid(stream_grid(n4, 256));
+  if (src.kind == Wire::kF32)
+    hipLaunchKernelGGL(pull_land_kernel<WireF32>, grid, dim3(256), 0, s, (float4*)p,
+                       WireF32{(const float*)src.data}, (const float4*)acc, (bf16x4*)w16, n4);
+  else
+    hipLaunchKernelGGL(pull_land_kernel<WireBF16>, grid, dim3(256), 0, s, (float4*)p,
+                       WireBF16{(const u16*)src.data}, (const float4*)acc, (bf16x4*)w16, n4);
 }
 
 void launch_push_handoff(float* acc, float* out32, u16* out16, long long n, hipStream_t s) {
@@ -743,22 +708,6 @@ void launch_push_handoff_mx8(float* acc, u8* payload, long long n, hipStream_t s
   const long long n4 = n / 4;
   hipLaunchKernelGGL(push_handoff_mx8_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
                      (f32x4*)acc, payload, n4, so);
-}
-
-void launch_ps_apply_mx8(float* shard, const u8* payload, u16* mirror, long long n, float scale,
-                         bool atomic, hipStream_t s, const float* factor) {
-  if (n <= 0) return;
-  long long so = 0;
-  mx8_layout(n, &so);
-  if (atomic) {
-    const int grid = (int)std::min<long long>((n + 255) / 256, 256LL * 16);
-    hipLaunchKernelGGL(ps_apply_mx8_atomic_kernel, dim3(grid), dim3(256), 0, s, shard, payload, n,
-                       so, scale, factor);
-  } else {
-    const long long n4 = n / 4;
-    hipLaunchKernelGGL(ps_apply_mx8_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                       (float4*)shard, payload, (bf16x4*)mirror, n4, so, scale, factor);
-  }
 }
 
 void launch_cast_f32_bf16(const float* src, u16* dst, long long n, hipStream_t s) {

@@ -51,6 +51,7 @@ import torch
 import torch.distributed as dist
 
 from . import messaging as M
+from . import wire
 from .clients import PSClient, _EventWork, _Pending
 from .links import AppliedCount, PairGroupTransport, PairLinks, wait_on, warm_stream
 from .staleness import DeviceStaleLog, StalenessGate, check_policy
@@ -151,24 +152,18 @@ class ShardServer:
         self.staleness: list[int] = []
         self.error: BaseException | None = None
         self.n = self.master.numel()
+        codecs = (wire.FP32, wire.BF16)  # the wires a peer may push on (no MX8 here)
         for p in peers:                  # payload rings up front (see PairLinks.reserve)
-            for dt in (torch.float32, torch.bfloat16):
-                self.rx.reserve(p, self.n, dt)
+            for c in codecs:
+                nelem, _, dt = c.payload_shape(self.n)   # received unpadded: see _recv_push
+                self.rx.reserve(p, nelem, dt)
             self.tx.reserve(p, self.n + 1, torch.float32, send=True)
         if self.cuda and peers:
-            # load the apply kernels before any transfer: a kernel's first launch
-            # loads its code object, and that waited for the transfers in flight
-            # (ParameterServer._warm_kernels); a zero delta changes nothing
+            # load the apply kernels before any transfer (wire.warm_applies); every
+            # apply here is atomic
             with torch.cuda.stream(self.stream):
-                for dt in (torch.float32, torch.bfloat16):
-                    self.nat.ps_apply(self.master, torch.zeros(self.n, dtype=dt,
-                                                               device=self.device),
-                                      None, self.scale, True)
-                    if self.stale_dev is not None:
-                        self.nat.ps_apply(self.master, torch.zeros(self.n, dtype=dt,
-                                                                   device=self.device),
-                                          None, self.scale, True,
-                                          torch.ones(2, device=self.device))
+                wire.warm_applies(self.master, codecs, self.scale,
+                                  with_factor=self.stale_dev is not None, atomic_only=True)
                 if self.stale_dev is not None:
                     # a log of its own: the warm-up launch is no apply
                     DeviceStaleLog(self.device, self.nat, self.applied, 0).factor(0, 0)
@@ -187,19 +182,19 @@ class ShardServer:
     # --------------------------------------------------------------- apply
     def _apply_locked(self, delta: torch.Tensor, base_version: int | None, sender: int):
         tau = self.version - base_version if base_version is not None else None
+        codec = wire.codec(delta)
         if self.cuda:
             # fp32 atomics: the local apply (self.stream) and every peer's apply
             # (its own link stream, _recv_push) may run at the same time
+            fac = None
             if self.stale_dev is not None and tau is not None:
                 # damp: the factor from the device count, on this applying stream
                 fac = self.stale_dev.factor(sender, base_version, cap=self.version)
-                self.nat.ps_apply(self.master, delta, None, self.scale, True, fac)
                 self.gate.log.append((sender, tau, None))
-            else:
-                self.nat.ps_apply(self.master, delta, None, self.scale, True)
+            codec.apply(self.master, delta, self.scale, True, fac)
         else:
             f = self.gate.note_push(sender, tau) if tau is not None else 1.0
-            self.master.add_(delta.to(torch.float32), alpha=self.scale * f)
+            codec.apply(self.master, delta, self.scale * f)
         self.applied.bump()        # GPU: on the applying stream, counted once landed
         if tau is not None:
             self.staleness.append(tau)

@@ -30,7 +30,7 @@ import torch
 import torch.distributed as dist
 
 from . import messaging as M
-from . import wire8
+from . import wire
 from .links import warm_stream
 
 _LOG = logging.getLogger(__name__)
@@ -59,7 +59,7 @@ class PSClient:
     """Base class: owns staging buffers and the landing logic."""
 
     # clients whose push can travel as a block-scaled 8-bit payload (wire8.py)
-    MX8_WIRE = False
+    supports_mx8 = False
 
     def __init__(self, staleness: int = 1, pull_mode: str = "overwrite",
                  wire_dtype: torch.dtype = torch.float32, push_wire: str = "same"):
@@ -89,11 +89,12 @@ class PSClient:
 
     # -- wiring ------------------------------------------------------------
     def attach(self, opt):
-        if self.push_wire == "mx8" and not self.MX8_WIRE:
+        if self.push_wire == "mx8" and not self.supports_mx8:
             raise ValueError(
                 f"push_wire='mx8' is not supported by {type(self).__name__}: the 8-bit push "
                 f"wire runs on {MX8_FLAVOURS}")
-        self.mx8 = self.push_wire == "mx8"
+        # pushes travel through this codec; pulls always in wire_dtype
+        self.push_codec = wire.MX8 if self.push_wire == "mx8" else wire.codec(self.wire_dtype)
         self.opt = opt
         self.arena = opt.arena
         self.device = self.arena.device
@@ -109,6 +110,10 @@ class PSClient:
     def init(self):
         pass
 
+    @property
+    def mx8(self) -> bool:
+        return self.push_codec is wire.MX8
+
     # -- push --------------------------------------------------------------
     def _handoff(self, n: int | None = None) -> torch.Tensor:
         """Snapshot the accumulator into a send buffer and zero it."""
@@ -120,37 +125,9 @@ class PSClient:
             prev.wait()
             self._send_work[slot] = None
         buf = self._send[slot]
-        if self.mx8:
-            # payload = quantise(acc), acc = residual: the rounding error of this
-            # push stays in the accumulator and travels with the next one
-            if buf is None:
-                # zeroed once: the layout's pad bytes are never written again
-                buf = torch.empty(wire8.layout(acc.numel())[2], dtype=torch.uint8,
-                                  device=self.device)
-                if self.cuda:
-                    self.nat.zero_(buf)
-                else:
-                    buf.zero_()
-                self._send[slot] = buf
-            if self.cuda:
-                self.nat.push_handoff_mx8(acc, buf)
-            else:
-                payload, resid = wire8.quantize(acc)
-                buf.copy_(payload)
-                acc.copy_(resid)
-            self._cur_slot = slot
-            return buf
-        if buf is None or buf.numel() != acc.numel():
-            buf = torch.empty(acc.numel(), dtype=self.wire_dtype, device=self.device)
-            self._send[slot] = buf
-        if self.cuda:
-            if self.wire_dtype == torch.float32:
-                self.nat.push_handoff(acc, buf, None)
-            else:
-                self.nat.push_handoff(acc, None, buf)
-        else:
-            buf.copy_(acc)
-            acc.zero_()
+        if buf is None or buf.numel() != self.push_codec.payload_shape(acc.numel())[0]:
+            buf = self._send[slot] = self.push_codec.new_payload(acc.numel(), self.device)
+        self.push_codec.handoff(acc, buf)
         self._cur_slot = slot
         return buf
 
@@ -305,7 +282,7 @@ class LocalPSClient(PSClient):
     # default keeps the apply and the snapshot on the compute stream; DMP_LOCAL_PS_SIDE=1
     # selects the side-stream placement described above (the N > 1 structure).
     SIDE = os.environ.get("DMP_LOCAL_PS_SIDE", "0") == "1"
-    MX8_WIRE = True
+    supports_mx8 = True
 
     def init(self):
         self.master = self.arena.p32.detach().clone()
@@ -327,26 +304,20 @@ class LocalPSClient(PSClient):
             with torch.cuda.stream(self.side):
                 self.side.wait_event(ev)
                 with self._timed("push"):
-                    if self.mx8:
-                        self.nat.ps_apply_mx8(self.master, buf, None, 1.0)
-                    else:
-                        self.nat.ps_apply(self.master, buf, None, 1.0)
+                    self.push_codec.apply(self.master, buf, 1.0)
                 done = torch.cuda.Event()
                 done.record()
             # the hand-off slot is refilled two pushes later: after this apply read it
             self._send_work[self._cur_slot] = _EventWork(done)
-        elif self.mx8:
-            self.master.add_(wire8.dequantize(buf, self.master.numel()))
         else:
-            self.master.add_(buf.to(torch.float32))
+            self.push_codec.apply(self.master, buf, 1.0)
         self.ps_version += 1
         self.pushes += 1
         self.bytes_sent += buf.numel() * buf.element_size()
 
     def request_pull(self, step: int):
         if not self.cuda:
-            snap = self.master.clone() if self.wire_dtype == torch.float32 else \
-                self.master.to(self.wire_dtype)
+            snap = wire.copy_as(self.master, self.wire_dtype)
             self.pending.append(_Pending(step, snap, version=self.ps_version))
             self.bytes_recv += snap.numel() * snap.element_size()
             return
@@ -411,7 +382,6 @@ class SharedPS:
         self.master = None
         self.version = 0
         self.stream = None
-        self.nat = None
 
     def adopt_or_set(self, p32: torch.Tensor) -> bool:
         """First caller seeds the master (the worker's init ParameterUpdate,
@@ -420,9 +390,6 @@ class SharedPS:
             return False
         self.master = p32.detach().to(torch.float32).clone()
         if self.master.device.type == "cuda":
-            from ..ops._ext import native
-
-            self.nat = native()
             self.stream = torch.cuda.Stream(self.master.device)
             self.stream.wait_stream(torch.cuda.current_stream())
         return True
@@ -432,11 +399,11 @@ class SharedPS:
         returns the event marking the apply done (``None`` on CPU)."""
         self.version += 1
         if self.stream is None:
-            self.master.add_(delta.to(torch.float32))
+            wire.codec(delta).apply(self.master, delta, 1.0)
             return None
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
-            self.nat.ps_apply(self.master, delta, None, 1.0)
+            wire.codec(delta).apply(self.master, delta, 1.0)
             done = torch.cuda.Event()
             done.record()
         return done
@@ -444,12 +411,10 @@ class SharedPS:
     def snapshot(self, wire_dtype: torch.dtype):
         """Copy of the master as of every apply enqueued so far -> (buf, event)."""
         if self.stream is None:
-            return self.master.clone() if wire_dtype == torch.float32 else \
-                self.master.to(wire_dtype), None
+            return wire.copy_as(self.master, wire_dtype), None
         caller = torch.cuda.current_stream()
         with torch.cuda.stream(self.stream):
-            buf = self.master.clone() if wire_dtype == torch.float32 else \
-                self.master.to(wire_dtype)
+            buf = wire.copy_as(self.master, wire_dtype)
             ev = torch.cuda.Event()
             ev.record()
         buf.record_stream(caller)    # landed (read) on the worker's stream
@@ -489,7 +454,7 @@ class SharedPSClient(PSClient):
 class GlooPSClient(PSClient):
     """Reference topology over gloo: ``send_message`` to the PS, reply on TAG_REPLY."""
 
-    MX8_WIRE = True
+    supports_mx8 = True
 
     def __init__(self, ps_rank: int = 0, group=None, **kw):
         super().__init__(**kw)
@@ -510,10 +475,10 @@ class GlooPSClient(PSClient):
     def push(self, step: int):
         buf = self._handoff()
         self._resolve_versions()
-        # MX8: the header still counts elements, the payload is layout(n) bytes
-        hdr = dict(nelem=self.opt.acc.numel(), dtype=M.MX8) if self.mx8 else {}
+        # the header counts elements on every wire (an MX8 payload is layout(n) bytes)
         works = M.send_message(M.MessageCode.GradientUpdate, self._cpu(buf), self.ps_rank,
-                               step=step, version=self.version, group=self.group, **hdr)
+                               step=step, version=self.version, group=self.group,
+                               nelem=self.opt.acc.numel(), dtype=self.push_codec.header)
         if not self.cuda:
             # gloo reads an unbound CPU send buffer only when the PS posts its recv:
             # the slot must not be refilled (two pushes later) before that happens
@@ -549,7 +514,7 @@ class GlooPSClient(PSClient):
 class RcclPSClient(PSClient):
     """Central PS on GPUs: control header on gloo, payload over a per-pair RCCL comm."""
 
-    MX8_WIRE = True
+    supports_mx8 = True
 
     def __init__(self, ps_rank: int, control_group, pair_group, **kw):
         super().__init__(**kw)
@@ -573,12 +538,8 @@ class RcclPSClient(PSClient):
     def push(self, step: int):
         buf = self._handoff()
         self._resolve_versions()
-        if self.mx8:
-            header = M.make_header(M.MessageCode.GradientUpdate, dist.get_rank(), step,
-                                   self.version, self.opt.acc.numel(), M.MX8)
-        else:
-            header = M.make_header(M.MessageCode.GradientUpdate, dist.get_rank(), step,
-                                   self.version, buf.numel(), buf.dtype)
+        header = M.make_header(M.MessageCode.GradientUpdate, dist.get_rank(), step,
+                               self.version, self.opt.acc.numel(), self.push_codec.header)
         M.SENDS.add(dist.isend(header, self.ps_rank, group=self.ctrl, tag=M.TAG_HEADER), header)
         self._send_work[self._cur_slot] = self._send_payload(buf)
         self.pushes += 1
@@ -654,14 +615,16 @@ class ShardedPSClient(PSClient):
         # the W bf16 slices of its shard unreduced and adds them to its fp32
         # master one by one -- no bf16 partial sums (a bf16 reduce-scatter would
         # round the running sum to 8 bits at every hop of the ring)
-        self.bf16_wire = self.wire_dtype == torch.bfloat16
-        if self.bf16_wire:
-            self.delta_slices = torch.zeros(self.world * self.shard_n, dtype=torch.bfloat16,
-                                            device=self.device)
-            self.master16 = torch.zeros(self.shard_n, dtype=torch.bfloat16, device=self.device)
-        else:
-            self.delta_shard = torch.zeros(self.shard_n, dtype=self.wire_dtype,
-                                           device=self.device)
+        self.unreduced = self.push_codec is wire.BF16
+        nslices = self.world if self.unreduced else 1
+        self.delta_buf = torch.zeros(nslices * self.shard_n, dtype=self.wire_dtype,
+                                     device=self.device)
+        # what _apply_delta adds to the master: W unreduced slices or the one reduced shard
+        self.deltas = self.delta_buf.chunk(nslices)
+        # pulls travel in the master's dtype or as its bf16 cast
+        self.pull_dtype = torch.bfloat16 if self.unreduced else torch.float32
+        self.master16 = torch.zeros(self.shard_n, dtype=torch.bfloat16, device=self.device) \
+            if self.unreduced else None
         self.side = torch.cuda.Stream(self.device) if self.cuda else None
         if self.side is not None:
             warm_stream(self.side)     # bind its queue now, not mid-step
@@ -669,33 +632,28 @@ class ShardedPSClient(PSClient):
         self._push_event = None
 
     def _apply_delta(self):
-        if self.bf16_wire:
-            sn = self.shard_n
-            for k in range(self.world):            # fp32 accumulation, one slice at a time
-                sl = self.delta_slices[k * sn:(k + 1) * sn]
-                if self.cuda:
-                    self.nat.ps_apply(self.master, sl, None, self.scale)
-                else:
-                    self.master.add_(sl.to(torch.float32), alpha=self.scale)
-        elif self.cuda:
-            self.nat.ps_apply(self.master, self.delta_shard, None, self.scale)
-        else:
-            self.master.add_(self.delta_shard.to(torch.float32), alpha=self.scale)
+        for sl in self.deltas:                     # fp32 accumulation, one slice at a time
+            self.push_codec.apply(self.master, sl, self.scale)
+
+    def _pull_src(self) -> torch.Tensor:
+        """The shard as a pull carries it: the master, or its RNE cast (taken on
+        the current stream)."""
+        return self.master if self.master16 is None else self.master16.copy_(self.master)
 
     def _exchange_deltas(self, buf, async_op: bool):
         """Deltas of every rank for this rank's shard: reduce-scatter (fp32 wire)
         or all-to-all of the bf16 slices (bf16 wire)."""
         gloo = dist.get_backend(self.group) == "gloo"
-        if self.bf16_wire:
+        if self.unreduced:
             if gloo:
-                dist.all_to_all_single(self.delta_slices, buf, group=self.group)
+                dist.all_to_all_single(self.delta_buf, buf, group=self.group)
                 return None
-            return dist.all_to_all_single(self.delta_slices, buf, group=self.group,
+            return dist.all_to_all_single(self.delta_buf, buf, group=self.group,
                                           async_op=async_op)
         if gloo:
             self._gloo_reduce_scatter(buf)
             return None
-        return dist.reduce_scatter_tensor(self.delta_shard, buf, group=self.group,
+        return dist.reduce_scatter_tensor(self.delta_buf, buf, group=self.group,
                                           async_op=async_op)
 
     def push(self, step: int):
@@ -703,10 +661,7 @@ class ShardedPSClient(PSClient):
         self.pushes += 1
         self.bytes_sent += buf.numel() * buf.element_size() * (self.world - 1) // max(self.world, 1)
         if self.world == 1 and not self.force:
-            if self.cuda:
-                self.nat.ps_apply(self.master, buf, None, 1.0)
-            else:
-                self.master.add_(buf.to(torch.float32))
+            self.push_codec.apply(self.master, buf, 1.0)
             return
         if self.cuda:
             ev = torch.cuda.Event()
@@ -730,11 +685,11 @@ class ShardedPSClient(PSClient):
         tmp = buf.clone()
         dist.all_reduce(tmp, group=self.group)
         lo = self.rank * self.shard_n
-        self.delta_shard.copy_(tmp[lo: lo + self.shard_n])
+        self.delta_buf.copy_(tmp[lo: lo + self.shard_n])
 
     def request_pull(self, step: int):
         n = self.arena.numel
-        wdt = torch.bfloat16 if self.bf16_wire else torch.float32
+        wdt = self.pull_dtype
         if self.cuda and (self.world > 1 or self.force):
             with torch.cuda.stream(self.side):
                 # allocated on the side stream that fills it (see LocalPSClient)
@@ -755,21 +710,14 @@ class ShardedPSClient(PSClient):
                 if free_ev is not None:
                     self.side.wait_event(free_ev)   # previous land kernel done reading buf
                 with self._timed("pull"):
-                    src = self.master
-                    if self.bf16_wire:
-                        self.master16.copy_(self.master)    # RNE cast on the side stream
-                        src = self.master16
-                    work = dist.all_gather_into_tensor(buf, src, group=self.group,
+                    work = dist.all_gather_into_tensor(buf, self._pull_src(), group=self.group,
                                                        async_op=True)
                     work.wait()
                 ev = torch.cuda.Event()
                 ev.record()
             self.pending.append(_Pending(step, buf, event=ev))
         else:
-            src = self.master
-            if self.bf16_wire:
-                self.master16.copy_(self.master)
-                src = self.master16
+            src = self._pull_src()
             work = dist.all_gather_into_tensor(buf, src, group=self.group, async_op=True) \
                 if dist.get_backend(self.group) != "gloo" else self._gloo_all_gather(buf, src)
             self.pending.append(_Pending(step, buf, work=work))

@@ -42,7 +42,7 @@ import torch
 import torch.distributed as dist
 
 from . import messaging as M
-from . import wire8
+from . import wire
 from .arena import FlatArena
 from .links import AppliedCount, PairGroupTransport, PairLinks, wait_on
 from .staleness import DeviceStaleLog, StalenessGate
@@ -150,14 +150,12 @@ class ParameterServer:
         self._touched_on: set = set()
         self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
         if self.links is not None:
-            # every worker's payload rings up front (fp32 and bf16 wire), not at
-            # the first transfer while other workers' transfers are in flight
-            padded = self.numel + pad
+            # every worker's payload rings up front (every wire it may push on), not
+            # at the first transfer while other workers' transfers are in flight
             for w in self.workers:
-                for dt in (torch.float32, torch.bfloat16):
-                    self.links.reserve(w, self.numel, dt, alloc=padded)
-                if self._mx8_ok():
-                    self.links.reserve(w, wire8.layout(self.numel)[2], torch.uint8)
+                for c in self._codecs():
+                    nelem, alloc, dt = c.payload_shape(self.numel)
+                    self.links.reserve(w, nelem, dt, alloc=alloc)
                 self.links.reserve(w, self.numel + 1, torch.float32, send=True)
             torch.cuda.synchronize(self.device)
         if self.device.type == "cuda":
@@ -176,46 +174,27 @@ class ParameterServer:
             self.stale_dev = DeviceStaleLog(self.device, self._native, self.applied,
                                             stale_bound, keys=[*self.workers, None])
         if self.links is not None:
-            self._warm_kernels(padded)
+            self._warm_kernels()
 
     def _mx8_ok(self) -> bool:
         """The MX8 kernels take whole float4 items (every model arena is a
         multiple of 64 elements); the CPU path takes any length."""
         return self.device.type != "cuda" or self.numel % 4 == 0
 
-    def _ps_apply(self, delta: torch.Tensor, atomic: bool = False, factor=None):
-        """``shard += delta_scale [* factor] * delta`` on the current stream; a
-        ``uint8`` delta is an MX8 payload (:mod:`.wire8`)."""
-        if delta.dtype == torch.uint8:
-            self._native.ps_apply_mx8(self.shard, delta, None, self.delta_scale, atomic, factor)
-        else:
-            self._native.ps_apply(self.shard, delta, None, self.delta_scale, atomic, factor)
+    def _codecs(self):
+        """The wires a worker may push on."""
+        return (wire.FP32, wire.BF16, wire.MX8) if self._mx8_ok() else (wire.FP32, wire.BF16)
 
-    def _warm_kernels(self, padded: int):
-        """Launch every kernel of the apply / reply path once, before any transfer.
-        HIP loads a kernel's code object at its first launch, and that load waited
-        for the work in flight: the PS's first apply stalled every other link until
-        the first receive had landed (tests/test_links_gpu.py).  A zero delta leaves
-        the shard unchanged."""
+    def _ps_apply(self, delta: torch.Tensor, atomic: bool = False, factor=None):
+        """``shard += delta_scale [* factor] * delta`` on the current stream."""
+        wire.codec(delta).apply(self.shard, delta, self.delta_scale, atomic, factor)
+
+    def _warm_kernels(self):
+        """Launch every kernel of the apply / reply path once, before any transfer
+        (:func:`.wire.warm_applies`)."""
         with torch.cuda.stream(self.stream):
-            for dt in (torch.float32, torch.bfloat16):
-                z = torch.zeros(padded, dtype=dt, device=self.device)
-                self._native.ps_apply(self.shard, z, None, self.delta_scale)
-                self._native.ps_apply(self.shard, z, None, self.delta_scale, True)
-                if self.stale_dev is not None:
-                    one = torch.ones(2, device=self.device)
-                    self._native.ps_apply(self.shard, z, None, self.delta_scale, False, one)
-                    self._native.ps_apply(self.shard, z, None, self.delta_scale, True, one)
-            if self._mx8_ok():
-                # an all-zero payload: codes 0 at scale 2^-127, adds +0
-                z = torch.zeros(wire8.layout(self.numel)[2], dtype=torch.uint8,
-                                device=self.device)
-                self._ps_apply(z)
-                self._ps_apply(z, True)
-                if self.stale_dev is not None:
-                    one = torch.ones(2, device=self.device)
-                    self._ps_apply(z, False, one)
-                    self._ps_apply(z, True, one)
+            wire.warm_applies(self.shard, self._codecs(), self.delta_scale,
+                              with_factor=self.stale_dev is not None, atomic_only=False)
             if self.stale_dev is not None:
                 # a log of its own: the warm-up launch is no apply
                 warm = DeviceStaleLog(self.device, self._native, self.applied, 0)
@@ -236,15 +215,10 @@ class ParameterServer:
         if nelem != self.numel:
             raise RuntimeError(f"PS: worker {sender} sent {nelem} elements, the shard has "
                                f"{self.numel} (model/arena layout mismatch)")
-        if dtype == M.MX8:
-            # a block-scaled 8-bit push: layout(nelem) bytes, no padding of its own
-            if not self._mx8_ok():
-                raise RuntimeError(f"PS: an MX8 push needs a shard length that is a multiple "
-                                   f"of 4 on the GPU, the shard has {self.numel}")
-            nelem = padded = wire8.layout(nelem)[2]
-            dtype = torch.uint8
-        else:
-            padded = nelem + ((-nelem) % 4)
+        if dtype == M.MX8 and not self._mx8_ok():
+            raise RuntimeError(f"PS: an MX8 push needs a shard length that is a multiple "
+                               f"of 4 on the GPU, the shard has {self.numel}")
+        nelem, padded, dtype = wire.codec(dtype).payload_shape(nelem)
         self.bytes_in += nelem * torch.empty(0, dtype=dtype).element_size()
         if self.links is not None:
             slot, ready = self.links.recv(sender, nelem, dtype, alloc=padded)
@@ -323,9 +297,7 @@ class ParameterServer:
                     self.links.release(slot, self.stream)
         else:
             f = self.gate.note_push(sender, tau) if base is not None else 1.0
-            d32 = wire8.dequantize(delta, self.numel) if delta.dtype == torch.uint8 else \
-                delta[: self.numel].to(torch.float32)
-            self.shard[: self.numel].add_(d32, alpha=self.delta_scale * f)
+            wire.codec(delta).apply(self.shard[: self.numel], delta, self.delta_scale * f)
             self.applied.bump()
         self.version += 1
 

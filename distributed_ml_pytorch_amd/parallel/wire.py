@@ -1,0 +1,133 @@
+"""The wire formats of a push, as codecs: fp32, bf16 and MX8 (:mod:`.wire8`).
+
+Every client and server asks a codec how a push accumulator becomes a payload
+(``handoff``), how large the payload of ``n`` elements is and what its header
+says (``payload_shape``, ``header``), and how a payload lands in an fp32 master
+(``apply``).  On the GPU these are the native kernels (``csrc/optim.hip``: one
+wire reader per format); on the CPU the torch expressions below, which the
+kernels match bit for bit (``tests/test_wire_codec_gpu.py``).  The codecs hold
+no state: :data:`FP32`, :data:`BF16` and :data:`MX8` are shared by everyone.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import messaging as M
+from . import wire8
+
+
+def _native():
+    from ..ops._ext import native
+
+    return native()
+
+
+class _Dense:
+    """One fp32 / bf16 element per element."""
+
+    def __init__(self, dtype: torch.dtype):
+        self.dtype = self.header = dtype        # payload dtype = the header's dtype field
+
+    def payload_shape(self, n: int):
+        """``(nelem, alloc, dtype)``: elements on the wire, elements of the buffer
+        they land in (the apply kernels take whole float4 items), torch dtype."""
+        return n, n + (-n) % 4, self.dtype
+
+    def new_payload(self, n: int, device) -> torch.Tensor:
+        return torch.empty(n, dtype=self.dtype, device=device)
+
+    def handoff(self, acc: torch.Tensor, buf: torch.Tensor):
+        """``buf = acc`` in the wire's dtype, ``acc = 0``."""
+        if acc.is_cuda:
+            outs = (buf, None) if self.dtype == torch.float32 else (None, buf)
+            _native().push_handoff(acc, *outs)
+        else:
+            buf.copy_(acc)
+            acc.zero_()
+
+    def decode(self, payload: torch.Tensor, n: int) -> torch.Tensor:
+        return payload[:n].to(torch.float32)
+
+    def apply(self, master: torch.Tensor, payload: torch.Tensor, scale: float,
+              atomic: bool = False, factor=None):
+        """``master += scale [* factor] * payload``; ``atomic`` and ``factor``
+        (a device slot of ``ps_stale_factor``) exist on the GPU only."""
+        if master.is_cuda:
+            _native().ps_apply(master, payload, None, scale, atomic, factor)
+        else:
+            master.add_(self.decode(payload, master.numel()), alpha=scale)
+
+
+class _MX8:
+    """Block-scaled 8-bit payload: ``wire8.layout(n)`` bytes for ``n`` elements."""
+
+    dtype = torch.uint8
+    header = M.MX8
+
+    def payload_shape(self, n: int):
+        nbytes = wire8.layout(n)[2]         # no padding of its own
+        return nbytes, nbytes, torch.uint8
+
+    def new_payload(self, n: int, device) -> torch.Tensor:
+        # zeroed once: the layout's pad bytes are never written again
+        buf = torch.empty(wire8.layout(n)[2], dtype=torch.uint8, device=device)
+        if buf.is_cuda:
+            _native().zero_(buf)
+        else:
+            buf.zero_()
+        return buf
+
+    def handoff(self, acc: torch.Tensor, buf: torch.Tensor):
+        """``buf = quantise(acc)``, ``acc = residual``: the rounding error of this
+        push stays in the accumulator and travels with the next one."""
+        if acc.is_cuda:
+            _native().push_handoff_mx8(acc, buf)
+        else:
+            payload, resid = wire8.quantize(acc)
+            buf.copy_(payload)
+            acc.copy_(resid)
+
+    def decode(self, payload: torch.Tensor, n: int) -> torch.Tensor:
+        return wire8.dequantize(payload, n)
+
+    def apply(self, master: torch.Tensor, payload: torch.Tensor, scale: float,
+              atomic: bool = False, factor=None):
+        if master.is_cuda:
+            _native().ps_apply_mx8(master, payload, None, scale, atomic, factor)
+        else:
+            master.add_(self.decode(payload, master.numel()), alpha=scale)
+
+
+FP32, BF16, MX8 = _Dense(torch.float32), _Dense(torch.bfloat16), _MX8()
+_CODECS = {torch.float32: FP32, torch.bfloat16: BF16, M.MX8: MX8, torch.uint8: MX8}
+
+
+def codec(what):
+    """The codec of a torch dtype, of a header's dtype field (:data:`.messaging.MX8`
+    included) or of a payload tensor (``uint8`` bytes are an MX8 payload)."""
+    key = what.dtype if torch.is_tensor(what) else what
+    if key == torch.float16 and key not in _CODECS:
+        _CODECS[key] = _Dense(key)      # a CPU-only wire: the dense expressions in fp16
+    return _CODECS[key]
+
+
+def copy_as(master: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """A copy of the master in ``dtype`` (``.to()`` of the same dtype would alias it)."""
+    return master.clone() if master.dtype == dtype else master.to(dtype)
+
+
+def warm_applies(master: torch.Tensor, codecs, scale: float, with_factor: bool,
+                 atomic_only: bool):
+    """Launch every apply kernel a server may need once, on the current stream,
+    before any transfer.  HIP loads a kernel's code object at its first launch,
+    and that load waited for the work in flight: the first apply stalled every
+    other link until the first receive had landed (tests/test_links_gpu.py).
+    An all-zero payload leaves the master unchanged (MX8: codes 0 at scale
+    2^-127 add +0).  ``with_factor``: the damped forms too (policy "damp")."""
+    factors = (None, torch.ones(2, device=master.device)) if with_factor else (None,)
+    for c in codecs:
+        _, alloc, dtype = c.payload_shape(master.numel())
+        z = torch.zeros(alloc, dtype=dtype, device=master.device)
+        for factor in factors:
+            for atomic in ((True,) if atomic_only else (False, True)):
+                c.apply(master, z, scale, atomic, factor)

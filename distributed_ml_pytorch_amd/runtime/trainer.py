@@ -462,7 +462,7 @@ def check_push_wire_config(cfg: TrainConfig, client=None):
     what = None
     if cfg.mode != "asgd":
         what = f"--mode {cfg.mode}"
-    elif client is not None and not client.MX8_WIRE:
+    elif client is not None and not client.supports_mx8:
         what = f"{type(client).__name__} (virtual workers)"
     elif client is None and cfg.ps in ("sharded", "sharded_async"):
         what = f"--ps {cfg.ps}"

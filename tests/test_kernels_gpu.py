@@ -76,16 +76,25 @@ def test_ps_apply_and_pull_land(nat):
     mirror = torch.empty(n, device="cuda", dtype=torch.bfloat16)
     nat.ps_apply(shard, delta, mirror, 0.5)
     torch.testing.assert_close(shard, ref)
+    # a power-of-two scale: the product is exact, so the kernel's fused multiply-add
+    # and the reference's multiply-then-add round once each, to the same bits
+    assert torch.equal(shard, ref)
     torch.testing.assert_close(mirror, ref.to(torch.bfloat16), rtol=0, atol=0)
     d16 = delta.to(torch.bfloat16)
     ref2 = shard + d16.float()
     nat.ps_apply(shard, d16, None, 1.0)
     torch.testing.assert_close(shard, ref2)
+    assert torch.equal(shard, ref2)
+    ref3 = shard + 0.5 * d16.float()
+    nat.ps_apply(shard, d16, None, 0.5)
+    assert torch.equal(shard, ref3)
     p = torch.empty(n, device="cuda")
     acc = torch.randn(n, device="cuda")
     w16 = torch.empty(n, device="cuda", dtype=torch.bfloat16)
     nat.pull_land(p, shard, acc, w16)
     torch.testing.assert_close(p, shard + acc)
+    assert torch.equal(p, shard + acc)
+    assert torch.equal(w16, (shard + acc).to(torch.bfloat16))
     nat.pull_land(p, shard, None, w16)
     torch.testing.assert_close(p, shard)
     torch.testing.assert_close(w16, shard.to(torch.bfloat16), rtol=0, atol=0)
