@@ -7,7 +7,7 @@ Reference flags (same names, defaults and meaning): --batch-size 64,
 central topology (reference roles, Makefile:13-20).
 
 Additional flags select the model, data, parallel mode, PS topology,
-staleness bound, precision, checkpointing and resume.
+staleness bound, delay compensation, precision, checkpointing and resume.
 """
 from __future__ import annotations
 
@@ -100,6 +100,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "push clock is more than S ahead of the slowest active worker "
                         "(stale-synchronous parallel); 'damp' applies a push that is tau > S "
                         "versions stale at weight 1 / (1 + tau - S); 'off' only reports")
+    p.add_argument("--delay-comp", type=float, default=0.0, metavar="LAMBDA",
+                   help="central PS: delay compensation (DC-ASGD).  The PS keeps the parameters "
+                        "it last sent each worker and applies that worker's delta d as "
+                        "d - c d*d (w_now - w_sent), c = LAMBDA / (lr * num-push); costs one "
+                        "fp32 copy of the model per worker on the PS.  SGD only; 0 = off")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log-dir", default="log")
     p.add_argument("--no-eval", action="store_true", default=False)
@@ -121,7 +126,7 @@ def config_from_args(a) -> TrainConfig:
         log_dir=a.log_dir, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every,
         resume=a.resume, ps_resume=a.ps_resume, delta_scale=a.delta_scale,
         ps_worker_timeout=a.ps_worker_timeout, stale_bound=a.stale_bound,
-        stale_policy=a.stale_policy, bucket_mb=a.bucket_mb,
+        stale_policy=a.stale_policy, delay_comp=a.delay_comp, bucket_mb=a.bucket_mb,
         label_smoothing=a.label_smoothing, divergence_check=not a.no_divergence_check,
         deterministic=a.deterministic, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
         adam_eps=a.adam_eps, clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,

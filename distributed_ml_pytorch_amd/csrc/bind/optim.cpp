@@ -234,6 +234,69 @@ void ps_apply_mx8(Tensor shard, Tensor payload, optional<Tensor> mirror, double 
                        (float)scale, atomic, cur_stream(), ptr_or_null<const float>(factor));
 }
 
+// ---- delay compensation: what a compensated apply checks on top of check_apply
+// the storage ranges of a and b overlap
+bool overlaps(const Tensor& a, const Tensor& b) {
+  const char* a0 = static_cast<const char*>(a.data_ptr());
+  const char* b0 = static_cast<const char*>(b.data_ptr());
+  return a0 < b0 + b.numel() * b.element_size() && b0 < a0 + a.numel() * a.element_size();
+}
+
+// `bak`: the worker's backup, at least n contiguous fp32 on the shard's device;
+// `c`: the compensation coefficient lambda / (lr n_push)
+const float* check_dc(const char* fn, const Tensor& shard, const Tensor& bak, int64_t n,
+                      double c) {
+  TORCH_CHECK(bak.is_cuda() && bak.scalar_type() == at::kFloat && bak.is_contiguous() &&
+                  bak.device() == shard.device() && aligned(bak),
+              fn, ": bak must be a contiguous, 16-byte aligned fp32 tensor on the shard's device");
+  TORCH_CHECK(bak.numel() >= n, fn, ": bak has ", bak.numel(), " elements, the shard has ", n);
+  TORCH_CHECK(!overlaps(bak, shard), fn, ": bak must not alias the shard");
+  TORCH_CHECK(std::isfinite(c) && c >= 0.0 && std::isfinite((float)c), fn,
+              ": the compensation coefficient c must be finite and >= 0, got ", c);
+  return bak.data_ptr<float>();
+}
+
+void ps_apply_dc(Tensor shard, Tensor delta, Tensor bak, optional<Tensor> mirror, double scale,
+                 double c, bool atomic, optional<Tensor> factor) {
+  const int64_t n = check_apply("ps_apply_dc", shard, mirror, atomic, factor);
+  const float* b = check_dc("ps_apply_dc", shard, bak, n, c);
+  dmp::launch_ps_apply_dc(shard.data_ptr<float>(), dense_wire(delta, n, "delta"), b,
+                          bf16_or_null(mirror), n, (float)scale, (float)c, atomic, cur_stream(),
+                          ptr_or_null<const float>(factor));
+}
+
+void ps_apply_dc_mx8(Tensor shard, Tensor payload, Tensor bak, optional<Tensor> mirror,
+                     double scale, double c, bool atomic, optional<Tensor> factor) {
+  const int64_t n = check_apply("ps_apply_dc_mx8", shard, mirror, atomic, factor);
+  TORCH_CHECK(shard.is_contiguous(), "shard must be contiguous");
+  const float* b = check_dc("ps_apply_dc_mx8", shard, bak, n, c);
+  const uint8_t* in = mx8_payload(payload, n, shard, "ps_apply_dc_mx8");
+  dmp::launch_ps_apply_dc(shard.data_ptr<float>(), {dmp::Wire::kMX8, in}, b, bf16_or_null(mirror),
+                          n, (float)scale, (float)c, atomic, cur_stream(),
+                          ptr_or_null<const float>(factor));
+}
+
+// One read of the shard into any of out32 (fp32 copy), out16 (bf16 copy) and
+// bak (the backup a later ps_apply_dc compensates against); at least one
+void ps_snapshot(Tensor shard, optional<Tensor> out32, optional<Tensor> out16,
+                 optional<Tensor> bak) {
+  const int64_t n = flat_len(shard, "shard length");
+  check_flat(shard, at::kFloat, n, "shard");
+  TORCH_CHECK(shard.is_contiguous(), "shard must be contiguous");
+  TORCH_CHECK(has(out32) || has(out16) || has(bak), "ps_snapshot: no output given");
+  check_flat_opt(out32, at::kFloat, n, "out32");
+  check_flat_opt(out16, at::kBFloat16, n, "out16");
+  check_flat_opt(bak, at::kFloat, n, "bak");
+  for (const optional<Tensor>* o : {&out32, &out16, &bak})
+    if (has(*o))
+      TORCH_CHECK((*o)->is_contiguous() && (*o)->device() == shard.device() &&
+                      !overlaps(**o, shard),
+                  "ps_snapshot: every output must be contiguous, on the shard's device and "
+                  "must not alias the shard");
+  dmp::launch_ps_snapshot(shard.data_ptr<float>(), ptr_or_null<float>(out32), bf16_or_null(out16),
+                          ptr_or_null<float>(bak), n, cur_stream());
+}
+
 void cast_f32_bf16(Tensor src, Tensor dst) {
   const int64_t n = flat_len(src, "length");
   check_flat(src, at::kFloat, n, "src");
@@ -289,6 +352,17 @@ void bind_optim(pybind11::module_& m) {
   m.def("ps_apply_mx8", &ps_apply_mx8, "parameter-server apply of an MX8 payload",
         py::arg("shard"), py::arg("payload"), py::arg("mirror") = py::none(),
         py::arg("scale") = 1.0, py::arg("atomic") = false, py::arg("factor") = py::none());
+  m.def("ps_apply_dc", &ps_apply_dc, "delay-compensated parameter-server apply",
+        py::arg("shard"), py::arg("delta"), py::arg("bak"), py::arg("mirror") = py::none(),
+        py::arg("scale") = 1.0, py::arg("c") = 0.0, py::arg("atomic") = false,
+        py::arg("factor") = py::none());
+  m.def("ps_apply_dc_mx8", &ps_apply_dc_mx8, "delay-compensated apply of an MX8 payload",
+        py::arg("shard"), py::arg("payload"), py::arg("bak"), py::arg("mirror") = py::none(),
+        py::arg("scale") = 1.0, py::arg("c") = 0.0, py::arg("atomic") = false,
+        py::arg("factor") = py::none());
+  m.def("ps_snapshot", &ps_snapshot, "one read of a shard into fp32 / bf16 copies and a backup",
+        py::arg("shard"), py::arg("out32") = py::none(), py::arg("out16") = py::none(),
+        py::arg("bak") = py::none());
   m.def("cast_f32_bf16", &cast_f32_bf16, "flat fp32 -> bf16");
   m.def("sumsq", &sumsq, "sum of squares of a flat fp32 buffer");
   m.def("zero_", &zero_, "native zero fill of a dense GPU tensor (a kernel, not a memset)");

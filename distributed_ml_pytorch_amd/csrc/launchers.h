@@ -34,6 +34,15 @@ struct Wire {
 // launch_ps_stale_factor on the same stream (staleness damping); null = undamped
 void launch_ps_apply(float* shard, Wire delta, uint16_t* mirror, long long n, float scale,
                      bool atomic, hipStream_t s, const float* factor = nullptr);
+// Delay-compensated apply (DC-ASGD): shard += scale * (d - c * d*d * (shard - bak)),
+// `bak` the fp32 parameters last sent to the pushing worker; otherwise as above
+void launch_ps_apply_dc(float* shard, Wire delta, const float* bak, uint16_t* mirror, long long n,
+                        float scale, float c, bool atomic, hipStream_t s,
+                        const float* factor = nullptr);
+// One read of the shard into any of: an fp32 copy, a bf16 copy, the backup
+// (null = skip); n % 4 == 0
+void launch_ps_snapshot(const float* shard, float* out32, uint16_t* out16, float* bak,
+                        long long n, hipStream_t s);
 void launch_ps_count(int* cnt, int add, bool set, hipStream_t s);
 void launch_ps_stamp(int* cnt, float* dst, hipStream_t s);
 int stale_log_numel();

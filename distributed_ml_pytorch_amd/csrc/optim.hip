@@ -521,6 +521,77 @@ __global__ void __launch_bounds__(256) ps_apply_atomic_kernel(float* __restrict_
     unsafeAtomicAdd(shard + i, scale * delta.load1(i));
 }
 
+// ---- delay compensation (DC-ASGD; specification: parallel/wire.py dc_delta) ----
+// The PS keeps `bak`, the parameters it last sent the pushing worker, and
+// corrects the delta to first order for how far the shard has moved since:
+//   e = d - c * d*d * (s - bak),   s' = s + sc * e
+// Seven fp32 operations, each rounded on its own, in this order (contraction
+// off, as in mx8_axpy): the torch expressions of the CPU path give the same
+// bits on every wire.  dc_term is sc * e, what the atomic form adds in memory.
+__device__ __forceinline__ float dc_term(float s, float d, float b, float c, float sc) {
+#pragma clang fp contract(off)
+  const float t = s - b;
+  const float q = d * d;
+  const float r = q * t;
+  const float u = c * r;
+  const float e = d - u;
+  return sc * e;
+}
+
+__device__ __forceinline__ float dc_axpy(float s, float d, float b, float c, float sc) {
+#pragma clang fp contract(off)
+  const float p = dc_term(s, d, b, c, sc);
+  return s + p;
+}
+
+// shard += scale * e(delta, shard, bak): the plain apply with a third stream
+// (16 B per parameter on the fp32 wire against 12), same launch shape.
+template <typename W>
+__global__ void __launch_bounds__(256) ps_apply_dc_kernel(
+    float4* __restrict__ shard, const W delta, const float4* __restrict__ bak,
+    bf16x4* __restrict__ mirror, long long n4, float scale, float c, const float* factor) {
+  scale = ps_scale(scale, factor);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 s = shard[i];
+    const float4 b = bak[i];
+    const float4 d = delta.load4(i);
+    s.x = dc_axpy(s.x, d.x, b.x, c, scale); s.y = dc_axpy(s.y, d.y, b.y, c, scale);
+    s.z = dc_axpy(s.z, d.z, b.z, c, scale); s.w = dc_axpy(s.w, d.w, b.w, c, scale);
+    shard[i] = s;
+    if (mirror) store_bf16x4(mirror, i, s);
+  }
+}
+
+// The atomic form (the shape of ps_apply_atomic_kernel): shard[i] is read with a
+// plain load for s - bak, then scale * e is added in memory.  An apply running
+// on another link stream at the same time may or may not show in that load:
+// the correction is first order in s - bak either way, and no add is lost.
+template <typename W>
+__global__ void __launch_bounds__(256) ps_apply_dc_atomic_kernel(
+    float* __restrict__ shard, const W delta, const float* __restrict__ bak, long long n,
+    float scale, float c, const float* factor) {
+  scale = ps_scale(scale, factor);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    unsafeAtomicAdd(shard + i, dc_term(shard[i], delta.load1(i), bak[i], c, scale));
+}
+
+// Reply snapshot: ONE read of the shard feeds the fp32 payload, the bf16
+// payload and the worker's backup (any of them null), so the backup is the very
+// values that were sent even while other link streams add to the shard.
+__global__ void __launch_bounds__(256) ps_snapshot_kernel(
+    const float4* __restrict__ shard, float4* __restrict__ out32, bf16x4* __restrict__ out16,
+    float4* __restrict__ bak, long long n4) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4 s = shard[i];
+    if (out32) out32[i] = s;
+    if (out16) store_bf16x4(out16, i, s);
+    if (bak) bak[i] = s;
+  }
+}
+
 // Pull landing: p = src (fp32 or bf16 wire), w16 = bf16(p). Optionally the
 // delta the worker accumulated since the snapshot is re-applied on top
 // (keep_local: p = src + acc), which keeps not-yet-pushed local progress
@@ -664,6 +735,49 @@ void launch_ps_apply(float* shard, Wire delta, u16* mirror, long long n, float s
       return ps_apply_as(shard, WireMX8{(const u8*)delta.data, so}, mirror, n, scale, atomic, s,
                          factor);
   }
+}
+
+// The launch shapes of ps_apply_as, with the backup as third operand.
+template <typename W>
+static void ps_apply_dc_as(float* shard, W delta, const float* bak, u16* mirror, long long n,
+                           float scale, float c, bool atomic, hipStream_t s,
+                           const float* factor) {
+  if (atomic) {
+    const int grid = (int)std::min<long long>((n + 255) / 256, 256LL * 16);
+    hipLaunchKernelGGL(ps_apply_dc_atomic_kernel<W>, dim3(grid), dim3(256), 0, s, shard, delta,
+                       bak, n, scale, c, factor);
+  } else {
+    const long long n4 = n / 4;
+    hipLaunchKernelGGL(ps_apply_dc_kernel<W>, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
+                       (float4*)shard, delta, (const float4*)bak, (bf16x4*)mirror, n4, scale, c,
+                       factor);
+  }
+}
+
+void launch_ps_apply_dc(float* shard, Wire delta, const float* bak, u16* mirror, long long n,
+                        float scale, float c, bool atomic, hipStream_t s, const float* factor) {
+  if (n <= 0) return;
+  long long so = 0;
+  switch (delta.kind) {
+    case Wire::kF32:
+      return ps_apply_dc_as(shard, WireF32{(const float*)delta.data}, bak, mirror, n, scale, c,
+                            atomic, s, factor);
+    case Wire::kBF16:
+      return ps_apply_dc_as(shard, WireBF16{(const u16*)delta.data}, bak, mirror, n, scale, c,
+                            atomic, s, factor);
+    case Wire::kMX8:
+      mx8_layout(n, &so);
+      return ps_apply_dc_as(shard, WireMX8{(const u8*)delta.data, so}, bak, mirror, n, scale, c,
+                            atomic, s, factor);
+  }
+}
+
+void launch_ps_snapshot(const float* shard, float* out32, u16* out16, float* bak, long long n,
+                        hipStream_t s) {
+  if (n <= 0) return;
+  const long long n4 = n / 4;
+  hipLaunchKernelGGL(ps_snapshot_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
+                     (const float4*)shard, (float4*)out32, (bf16x4*)out16, (float4*)bak, n4);
 }
 
 void launch_ps_count(int* cnt, int add, bool set, hipStream_t s) {

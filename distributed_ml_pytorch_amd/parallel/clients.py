@@ -376,12 +376,23 @@ class SharedPS:
     on the PS's own stream, so concurrent pushes from different worker streams
     are serialised exactly as the central PS serialises its receive loop, and a
     pull observes every push enqueued before it.
+
+    ``delay_comp``: the coefficient ``c`` of delay compensation
+    (:func:`.wire.dc_delta`; ``0`` = off, nothing changes).  With ``c > 0`` and a
+    ``worker`` id on :meth:`snapshot` / :meth:`apply`, the PS keeps per worker the
+    fp32 master its last snapshot was formed from (also on a bf16 pull wire) and
+    compensates that worker's pushes against it.
     """
 
-    def __init__(self):
+    def __init__(self, delay_comp: float = 0.0):
         self.master = None
         self.version = 0
         self.stream = None
+        self.delay_comp = float(delay_comp)
+        if not (0.0 <= self.delay_comp < float("inf")):
+            raise ValueError(f"delay_comp must be finite and >= 0, got {delay_comp!r}")
+        self.bak: dict = {}         # worker -> fp32 backup, from its first snapshot on
+        self.compensated = self.uncompensated = 0
 
     def adopt_or_set(self, p32: torch.Tensor) -> bool:
         """First caller seeds the master (the worker's init ParameterUpdate,
@@ -394,39 +405,81 @@ class SharedPS:
             self.stream.wait_stream(torch.cuda.current_stream())
         return True
 
-    def apply(self, delta: torch.Tensor):
+    def _add(self, delta: torch.Tensor, worker):
+        """``master += delta`` on the current stream, compensated once ``worker``
+        has taken a snapshot."""
+        bak = self.bak.get(worker) if self.delay_comp > 0 else None
+        if bak is None:
+            wire.codec(delta).apply(self.master, delta, 1.0)
+        else:
+            wire.codec(delta).apply_dc(self.master, bak, delta, 1.0, self.delay_comp)
+        if self.delay_comp > 0:
+            self.compensated += bak is not None
+            self.uncompensated += bak is None
+
+    def apply(self, delta: torch.Tensor, worker=None):
         """``master += delta`` after the caller's stream reaches this point;
         returns the event marking the apply done (``None`` on CPU)."""
         self.version += 1
         if self.stream is None:
-            wire.codec(delta).apply(self.master, delta, 1.0)
+            self._add(delta, worker)
             return None
         self.stream.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self.stream):
-            wire.codec(delta).apply(self.master, delta, 1.0)
+            self._add(delta, worker)
             done = torch.cuda.Event()
             done.record()
         return done
 
-    def snapshot(self, wire_dtype: torch.dtype):
+    def _copy(self, wire_dtype: torch.dtype, worker) -> torch.Tensor:
+        """The master in ``wire_dtype`` on the current stream.  Delay compensation:
+        ``worker``'s backup is written by the same read of the master
+        (``ps_snapshot``), so it is exactly what the copy was formed from."""
+        if self.delay_comp <= 0 or worker is None:
+            return wire.copy_as(self.master, wire_dtype)
+        bak = self.bak.get(worker)
+        if bak is None:
+            bak = self.bak[worker] = torch.empty_like(self.master)
+        if not self.master.is_cuda:
+            bak.copy_(self.master)
+            return wire.copy_as(bak, wire_dtype)
+        if wire_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"delay compensation on the GPU pulls in fp32 or bf16, "
+                             f"not {wire_dtype}")
+        from ..ops._ext import native
+
+        buf = torch.empty(self.master.numel(), dtype=wire_dtype, device=self.master.device)
+        outs = (buf, None) if wire_dtype == torch.float32 else (None, buf)
+        native().ps_snapshot(self.master, *outs, bak)
+        return buf
+
+    def snapshot(self, wire_dtype: torch.dtype, worker=None):
         """Copy of the master as of every apply enqueued so far -> (buf, event)."""
         if self.stream is None:
-            return wire.copy_as(self.master, wire_dtype), None
+            return self._copy(wire_dtype, worker), None
         caller = torch.cuda.current_stream()
         with torch.cuda.stream(self.stream):
-            buf = wire.copy_as(self.master, wire_dtype)
+            buf = self._copy(wire_dtype, worker)
             ev = torch.cuda.Event()
             ev.record()
         buf.record_stream(caller)    # landed (read) on the worker's stream
         return buf, ev
 
+    def stats(self) -> dict:
+        return {"version": self.version, "delay_comp": self.delay_comp,
+                "compensated": self.compensated, "uncompensated": self.uncompensated}
+
 
 class SharedPSClient(PSClient):
     """Worker side of :class:`SharedPS` (virtual workers on one device)."""
 
-    def __init__(self, shared: SharedPS, **kw):
+    def __init__(self, shared: SharedPS, worker: int | None = None, **kw):
+        """``worker``: this client's id at the PS; with delay compensation on, the
+        PS keeps one backup per id."""
         super().__init__(**kw)
         self.shared = shared
+        # passed on only when the PS compensates: otherwise the calls are as before
+        self._who = {"worker": worker} if shared.delay_comp > 0 and worker is not None else {}
 
     def init(self):
         if not self.shared.adopt_or_set(self.arena.p32):
@@ -438,7 +491,7 @@ class SharedPSClient(PSClient):
 
     def push(self, step: int):
         buf = self._handoff()
-        done = self.shared.apply(buf)
+        done = self.shared.apply(buf, **self._who)
         if done is not None:
             # the send buffer is reused two pushes later: wait for this apply first
             self._send_work[self._cur_slot] = _EventWork(done)
@@ -446,7 +499,7 @@ class SharedPSClient(PSClient):
         self.bytes_sent += buf.numel() * buf.element_size()
 
     def request_pull(self, step: int):
-        buf, ev = self.shared.snapshot(self.wire_dtype)
+        buf, ev = self.shared.snapshot(self.wire_dtype, **self._who)
         self.pending.append(_Pending(step, buf, event=ev, version=self.shared.version))
         self.bytes_recv += buf.numel() * buf.element_size()
 

@@ -11,7 +11,8 @@ worker side /root/reference/asgd/optim/Asynchronous.py:34,49,59:
 until every worker has sent ``Shutdown`` (the reference's loop never ended,
 SURVEY D9).  Additions: a version counter (number of applied deltas; pushes
 report the version their base params came from, so the server measures
-staleness), per-worker liveness, periodic checkpoints, and two payload paths:
+staleness), opt-in delay compensation of stale pushes (``delay_comp``), per-worker
+liveness, periodic checkpoints, and two payload paths:
 
 * ``payload="gloo"`` - headers and payloads on the (CPU) gloo group;
 * ``payload="rccl"`` - headers on a CPU gloo control group, payloads on a
@@ -76,7 +77,7 @@ class ParameterServer:
                  checkpoint_path: str | None = None, checkpoint_every: int = 0,
                  worker_timeout: float | None = None, delta_scale: str | float = "sum",
                  transport=None, trace_links: bool = False, stale_bound: int = 0,
-                 stale_policy: str = "off"):
+                 stale_policy: str = "off", delay_comp: float = 0.0):
         """``delta_scale``: factor on every pushed delta -- ``"sum"`` (1.0, the
         reference Downpour PS: /root/reference/asgd/optim/Asynchronous.py:48-55
         ships raw accumulated updates that the PS adds), ``"mean"`` (1 / #workers:
@@ -87,9 +88,21 @@ class ParameterServer:
         (:mod:`.staleness`): ``"block"`` defers a worker's pulls while its push
         clock is more than ``stale_bound`` ahead of the slowest active worker,
         ``"damp"`` scales a push more than ``stale_bound`` versions stale by
-        ``1 / (1 + tau - stale_bound)``; ``"off"`` (default) only keeps the clocks."""
+        ``1 / (1 + tau - stale_bound)``; ``"off"`` (default) only keeps the clocks.
+
+        ``delay_comp``: the coefficient ``c = lambda / (lr * n_push)`` of delay
+        compensation (DC-ASGD; :func:`.wire.dc_delta`), ``0`` = off.  With ``c > 0``
+        the server keeps, per worker, an fp32 backup of the parameters it last sent
+        that worker (``len(workers) * numel * 4`` bytes, allocated here) and applies
+        the worker's delta ``d`` as ``d - c * d*d * (shard - backup)``.  It composes
+        with both policies (``damp``'s factor multiplies the scale).  A worker's
+        pushes are uncompensated until its first reply after an initialisation or
+        a checkpoint load: backups are not checkpointed."""
         if not dist.is_initialized():
             raise RuntimeError("ParameterServer needs torch.distributed to be initialised")
+        self.delay_comp = float(delay_comp)
+        if not (0.0 <= self.delay_comp < float("inf")):
+            raise ValueError(f"delay_comp must be finite and >= 0, got {delay_comp!r}")
         self.rank = dist.get_rank()
         world = dist.get_world_size()
         self.workers = list(workers) if workers is not None else [
@@ -129,6 +142,19 @@ class ParameterServer:
         pad = (-self.numel) % 4
         self.shard = torch.zeros(self.numel + pad, dtype=torch.float32, device=self.device)
         self.shard[: self.numel].copy_(flat)
+        # delay compensation: every worker's backup up front (nothing is allocated
+        # between transfers), valid from the worker's first reply on
+        self.bak = None
+        self.has_backup = {w: False for w in self.workers}
+        self.dc_log: list = []      # ("reply", w) / ("push", w, compensated), as handled
+        self.compensated = self.uncompensated = 0
+        if self.delay_comp > 0:
+            if self.device.type == "cuda" and self.numel % 4:
+                raise ValueError(f"delay_comp on the GPU needs a shard length that is a "
+                                 f"multiple of 4 (every model arena is), got {self.numel}")
+            self.bak = torch.zeros(len(self.workers), self.shard.numel(), dtype=torch.float32,
+                                   device=self.device)
+            self._bak_row = {w: i for i, w in enumerate(self.workers)}
         self.version = 0
         self.initialized = False
         self.init_policy = init_policy
@@ -185,16 +211,40 @@ class ParameterServer:
         """The wires a worker may push on."""
         return (wire.FP32, wire.BF16, wire.MX8) if self._mx8_ok() else (wire.FP32, wire.BF16)
 
-    def _ps_apply(self, delta: torch.Tensor, atomic: bool = False, factor=None):
-        """``shard += delta_scale [* factor] * delta`` on the current stream."""
-        wire.codec(delta).apply(self.shard, delta, self.delta_scale, atomic, factor)
+    def _backup(self, worker) -> torch.Tensor | None:
+        """``worker``'s backup row (delay compensation on)."""
+        return None if self.bak is None else self.bak[self._bak_row[worker]]
+
+    def _ps_apply(self, delta: torch.Tensor, atomic: bool = False, factor=None, sender=None,
+                  shard: torch.Tensor | None = None):
+        """``shard += delta_scale [* factor] * delta`` on the current stream; the
+        delay-compensated delta once ``sender`` holds a backup."""
+        shard = self.shard if shard is None else shard
+        codec = wire.codec(delta)
+        comp = self.bak is not None and self.has_backup.get(sender, False)
+        if comp:
+            codec.apply_dc(shard, self._backup(sender), delta, self.delta_scale,
+                           self.delay_comp, atomic, factor)
+        elif factor is None or shard.is_cuda:
+            codec.apply(shard, delta, self.delta_scale, atomic, factor)
+        else:
+            codec.apply(shard, delta, self.delta_scale * factor)      # CPU, policy "damp"
+        if self.bak is not None:
+            self.dc_log.append(("push", sender, comp))
+            self.compensated += comp
+            self.uncompensated += not comp
 
     def _warm_kernels(self):
         """Launch every kernel of the apply / reply path once, before any transfer
         (:func:`.wire.warm_applies`)."""
         with torch.cuda.stream(self.stream):
             wire.warm_applies(self.shard, self._codecs(), self.delta_scale,
-                              with_factor=self.stale_dev is not None, atomic_only=False)
+                              with_factor=self.stale_dev is not None, atomic_only=False,
+                              bak=None if self.bak is None else self.bak[0],
+                              dc=self.delay_comp)
+            if self.bak is not None:
+                # overwritten by the worker's first reply before it is ever read
+                self._native.ps_snapshot(self.shard, None, None, self.bak[0])
             if self.stale_dev is not None:
                 # a log of its own: the warm-up launch is no apply
                 warm = DeviceStaleLog(self.device, self._native, self.applied, 0)
@@ -237,10 +287,19 @@ class ParameterServer:
         (:class:`.links.AppliedCount`: stamped on the device before the copy) --
         so the worker can report its staleness on its next push."""
         n = self.numel
+        # delay compensation: dst's backup and the payload come from ONE read of the
+        # shard, so the fp32 payload bit-equals the backup while other links add
+        bak = self._backup(dst)
+        if bak is not None:
+            self.has_backup[dst] = True
+            self.dc_log.append(("reply", dst))
         if self.links is not None:
             def fill(buf):
                 self.applied.stamp(buf[n:])     # first: counts only landed applies
-                buf[:n].copy_(self.shard[:n])   # snapshot: later applies never tear it
+                if bak is not None:
+                    self._native.ps_snapshot(self.shard, buf[:n], None, bak)
+                else:
+                    buf[:n].copy_(self.shard[:n])   # snapshot: later applies never tear it
 
             # snapshot on dst's OWN link stream: behind dst's own applies (same
             # stream) and the last initialisation, never behind another worker's
@@ -255,11 +314,16 @@ class ParameterServer:
             if self.stream is not None:
                 # a device shard behind gloo payloads: the applies run on the apply
                 # stream; once it has drained the host count is what has landed
+                if bak is not None:
+                    with torch.cuda.stream(self.stream):
+                        self._native.ps_snapshot(self.shard, None, None, bak)
                 self.stream.synchronize()
                 snap[n] = float(self.applied.host)
             else:
                 self.applied.stamp(snap[n:])     # gloo: applies are synchronous
-            snap[:n].copy_(self.shard[:n])
+                if bak is not None:
+                    bak.copy_(self.shard)
+            snap[:n].copy_(self.shard[:n] if bak is None else bak[:n])
             w = dist.isend(snap, dst, group=self.ctrl, tag=M.TAG_REPLY)
             self._tracker.add(w, snap)
         self.bytes_out += (n + 1) * 4
@@ -283,7 +347,7 @@ class ParameterServer:
             with torch.cuda.stream(s):
                 wait_on(s, ready)
                 wait_on(s, self._init_ev)
-                self._ps_apply(delta, True)
+                self._ps_apply(delta, True, sender=sender)
                 self.applied.bump()            # counted once this apply has landed
                 if slot is not None:
                     self.links.release(slot, s)
@@ -291,13 +355,13 @@ class ParameterServer:
         elif self._native is not None:
             with torch.cuda.stream(self.stream):
                 wait_on(self.stream, ready)
-                self._ps_apply(delta)
+                self._ps_apply(delta, sender=sender)
                 self.applied.bump()
                 if slot is not None:
                     self.links.release(slot, self.stream)
         else:
             f = self.gate.note_push(sender, tau) if base is not None else 1.0
-            wire.codec(delta).apply(self.shard[: self.numel], delta, self.delta_scale * f)
+            self._ps_apply(delta, factor=f, sender=sender, shard=self.shard[: self.numel])
             self.applied.bump()
         self.version += 1
 
@@ -312,7 +376,7 @@ class ParameterServer:
             if links:
                 wait_on(s, self._init_ev)
             fac = self.stale_dev.factor(sender if links else None, base, cap=self.version)
-            self._ps_apply(delta, links, fac)
+            self._ps_apply(delta, links, fac, sender=sender)
             self.applied.bump()
             if slot is not None:
                 self.links.release(slot, s)
@@ -322,6 +386,9 @@ class ParameterServer:
         self.version += 1
 
     def _set(self, params: torch.Tensor, ready=None, slot=None, version: int | None = None):
+        # the backups describe the shard that is being replaced: every worker's pushes
+        # are uncompensated again until its next reply
+        self.has_backup = dict.fromkeys(self.has_backup, False)
         with torch.cuda.stream(self.stream) if self.stream is not None else _null():
             wait_on(self.stream, ready)
             # an overwrite orders against every apply AND reply snapshot already
@@ -506,6 +573,9 @@ class ParameterServer:
             "staleness_mean": (sum(st) / len(st)) if st else 0.0,
             "staleness_max": max(st) if st else 0,
             "dropped": list(self.dropped),
+            "delay_comp": self.delay_comp,
+            "compensated": self.compensated,
+            "uncompensated": self.uncompensated,
         }
 
     def save_checkpoint(self, path: str | None = None):

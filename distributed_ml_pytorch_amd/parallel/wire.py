@@ -3,7 +3,7 @@
 Every client and server asks a codec how a push accumulator becomes a payload
 (``handoff``), how large the payload of ``n`` elements is and what its header
 says (``payload_shape``, ``header``), and how a payload lands in an fp32 master
-(``apply``).  On the GPU these are the native kernels (``csrc/optim.hip``: one
+(``apply``; ``apply_dc`` with delay compensation, :func:`dc_delta`).  On the GPU these are the native kernels (``csrc/optim.hip``: one
 wire reader per format); on the CPU the torch expressions below, which the
 kernels match bit for bit (``tests/test_wire_codec_gpu.py``).  The codecs hold
 no state: :data:`FP32`, :data:`BF16` and :data:`MX8` are shared by everyone.
@@ -20,6 +20,42 @@ def _native():
     from ..ops._ext import native
 
     return native()
+
+
+def _f32(x) -> torch.Tensor:
+    """``x`` rounded to fp32 once, as a 0-dim CPU tensor (nothing below depends on
+    how torch promotes a Python scalar)."""
+    if torch.is_tensor(x):
+        return x.reshape(-1)[0].to(device="cpu", dtype=torch.float32)
+    return torch.tensor(x, dtype=torch.float32)
+
+
+def dc_delta(d: torch.Tensor, master: torch.Tensor, bak: torch.Tensor, c) -> torch.Tensor:
+    """The delay-compensated delta of DC-ASGD (Zheng et al., ICML 2017), the
+    specification of the ``ps_apply_dc`` kernels::
+
+        e = d - c * d*d * (master - bak)
+
+    ``bak``: the parameters the pushing worker computed ``d`` from; ``c`` =
+    ``lambda / (lr * n_push)``.  All fp32, one separately rounded torch operation
+    per line; the kernels run the same operations in the same order with
+    contraction off and give the same bits."""
+    c = _f32(c)
+    t = master - bak
+    q = d * d
+    r = q * t
+    u = c * r
+    return d - u
+
+
+def _apply_dc_cpu(master: torch.Tensor, bak: torch.Tensor, d: torch.Tensor, scale, c, factor):
+    """``master += sc * dc_delta(d)`` as two more separately rounded operations;
+    ``sc = fp32(scale) * fp32(factor)``.  No ``add_(alpha=)``: that is free to fuse."""
+    sc = _f32(scale)
+    if factor is not None:
+        sc = sc * _f32(factor)
+    p = sc * dc_delta(d, master, bak[: master.numel()], c)
+    master.copy_(master + p)
 
 
 class _Dense:
@@ -56,6 +92,16 @@ class _Dense:
             _native().ps_apply(master, payload, None, scale, atomic, factor)
         else:
             master.add_(self.decode(payload, master.numel()), alpha=scale)
+
+    def apply_dc(self, master: torch.Tensor, bak: torch.Tensor, payload: torch.Tensor,
+                 scale: float, c: float, atomic: bool = False, factor=None):
+        """The delay-compensated apply: ``master += scale [* factor] *
+        dc_delta(payload, master, bak, c)``.  GPU: ``ps_apply_dc`` (``factor`` a
+        device slot); CPU: ``decode`` plus the specification (``factor`` a number)."""
+        if master.is_cuda:
+            _native().ps_apply_dc(master, payload, bak, None, scale, c, atomic, factor)
+        else:
+            _apply_dc_cpu(master, bak, self.decode(payload, master.numel()), scale, c, factor)
 
 
 class _MX8:
@@ -97,6 +143,13 @@ class _MX8:
         else:
             master.add_(self.decode(payload, master.numel()), alpha=scale)
 
+    def apply_dc(self, master: torch.Tensor, bak: torch.Tensor, payload: torch.Tensor,
+                 scale: float, c: float, atomic: bool = False, factor=None):
+        if master.is_cuda:
+            _native().ps_apply_dc_mx8(master, payload, bak, None, scale, c, atomic, factor)
+        else:
+            _apply_dc_cpu(master, bak, self.decode(payload, master.numel()), scale, c, factor)
+
 
 FP32, BF16, MX8 = _Dense(torch.float32), _Dense(torch.bfloat16), _MX8()
 _CODECS = {torch.float32: FP32, torch.bfloat16: BF16, M.MX8: MX8, torch.uint8: MX8}
@@ -117,13 +170,17 @@ def copy_as(master: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 
 
 def warm_applies(master: torch.Tensor, codecs, scale: float, with_factor: bool,
-                 atomic_only: bool):
+                 atomic_only: bool, bak: torch.Tensor | None = None, dc: float = 0.0):
     """Launch every apply kernel a server may need once, on the current stream,
     before any transfer.  HIP loads a kernel's code object at its first launch,
     and that load waited for the work in flight: the first apply stalled every
     other link until the first receive had landed (tests/test_links_gpu.py).
     An all-zero payload leaves the master unchanged (MX8: codes 0 at scale
-    2^-127 add +0).  ``with_factor``: the damped forms too (policy "damp")."""
+    2^-127 add +0).  ``with_factor``: the damped forms too (policy "damp").
+    ``bak`` (one worker's backup) and ``dc``: the server compensates delays, so
+    the compensated forms are launched as well, for the same reason -- their
+    first launch must not happen during a transfer either (a zero delta gives a
+    zero compensated delta whatever the backup holds)."""
     factors = (None, torch.ones(2, device=master.device)) if with_factor else (None,)
     for c in codecs:
         _, alloc, dtype = c.payload_shape(master.numel())
@@ -131,3 +188,5 @@ def warm_applies(master: torch.Tensor, codecs, scale: float, with_factor: bool,
         for factor in factors:
             for atomic in ((True,) if atomic_only else (False, True)):
                 c.apply(master, z, scale, atomic, factor)
+                if bak is not None:
+                    c.apply_dc(master, bak, z, scale, dc, atomic, factor)

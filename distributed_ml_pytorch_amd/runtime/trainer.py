@@ -36,7 +36,7 @@ from ..parallel.arena import attach_arena
 from ..parallel.asgd import Asynchronous
 from ..parallel.async_sharded import AsyncShardedPSClient
 from ..parallel.clients import (MX8_FLAVOURS, GlooPSClient, LocalPSClient, RcclPSClient,
-                                ShardedPSClient, check_push_wire)
+                                ShardedPSClient, SharedPSClient, check_push_wire)
 from ..parallel.ddp import BucketedAllReduce, FusedAdamW, FusedSGD
 from ..parallel.fused_optim import Schedule
 from ..parallel.server import ParameterServer, make_ps_groups
@@ -102,6 +102,7 @@ class TrainConfig:
     ps_worker_timeout: float = 0.0    # central PS: drop a worker silent this long (0 = never)
     stale_bound: int = 0              # S of the version-based staleness bound (parallel/staleness.py)
     stale_policy: str = "off"         # off | damp | block (central and sharded_async PS only)
+    delay_comp: float = 0.0           # lambda of delay compensation (DC-ASGD); 0 = off
     bucket_mb: float = 0.0            # sync-DP all-reduce bucket; <= 0: measured (ddp.py)
     label_smoothing: float = 0.0
     divergence_check: bool = True     # halt on non-finite parameters at each log interval
@@ -125,6 +126,7 @@ class Worker:
         self.info = info
         check_stale_config(cfg, info)
         check_push_wire_config(cfg, client)
+        check_delay_comp_config(cfg, info, client)
         if cfg.deterministic:
             cfg = self.cfg = enable_determinism(cfg)
         torch.manual_seed(cfg.seed + info.rank)
@@ -454,6 +456,47 @@ def check_stale_config(cfg: TrainConfig, info: DistInfo):
             "(the local PS has one worker, the collective sharded PS is lock-step)")
 
 
+def delay_comp_coefficient(cfg: TrainConfig) -> float:
+    """``c = lambda / (lr * n_push)``: what the servers take.  A push carries
+    ``d = -lr * sum(g_i)`` of ``n_push`` steps; DC-ASGD's ``lambda * g*g`` becomes
+    ``c * d*d`` per unit of ``d`` (``(sum g)^2 ~ n^2 gbar^2`` against ``sum(g^2) ~
+    n gbar^2``).  Formed once from the base learning rate: under a decaying
+    schedule the compensation shrinks with ``lr_t / lr_0``."""
+    return cfg.delay_comp / (cfg.lr * cfg.n_push) if cfg.delay_comp else 0.0
+
+
+def check_delay_comp_config(cfg: TrainConfig, info: DistInfo, client=None):
+    """Delay compensation corrects a stale push at a PS that hands every worker
+    its own snapshot: the central PS, and the shared PS of the virtual workers
+    (``client``).  Anywhere else, and with an update that is not proportional to
+    the gradient (AdamW), asking for it is an error at start-up.  SGD with
+    momentum passes: its delta is a running mean of gradients, for which
+    ``lambda * g*g`` is an approximation."""
+    lam = cfg.delay_comp
+    if not (0.0 <= lam < float("inf")):
+        raise ValueError(f"--delay-comp must be finite and >= 0, got {lam!r}")
+    if lam == 0:
+        return
+    what = None
+    if cfg.mode != "asgd":
+        what = (f"--mode {cfg.mode}", "there is no parameter server and no stale push")
+    elif cfg.optimizer == "adamw":
+        what = ("--optimizer adamw", "its update is not proportional to the gradient, so "
+                "lambda * g*g is no stand-in for the curvature seen by the pushed delta")
+    elif client is not None and not isinstance(client, SharedPSClient):
+        what = (type(client).__name__, "this client's server keeps no per-worker backup")
+    elif client is None and (cfg.ps != "central" or not info.is_distributed):
+        flavour = f"--ps {cfg.ps}" if info.is_distributed else \
+            "--ps local (a single-process run)"
+        what = (flavour, "a single worker or a lock-step collective has no stale push to "
+                "correct, and the sharded_async shard servers do not compensate")
+    if what:
+        raise ValueError(f"--delay-comp {lam} is not supported with {what[0]}: {what[1]} "
+                         "(delay compensation runs on the central PS and the virtual workers)")
+    if not cfg.lr > 0 or cfg.n_push < 1:
+        raise ValueError("--delay-comp needs lr > 0 and n_push >= 1 (c = lambda / (lr n_push))")
+
+
 def check_push_wire_config(cfg: TrainConfig, client=None):
     """The 8-bit push wire exists where one worker's push reaches one server:
     the local PS and the central PS.  Anywhere else it is an error at start-up."""
@@ -489,7 +532,8 @@ def run_server(cfg: TrainConfig, info: DistInfo, ps_groups):
                              checkpoint_every=cfg.checkpoint_every,
                              worker_timeout=cfg.ps_worker_timeout or None,
                              delta_scale=cfg.delta_scale, stale_bound=cfg.stale_bound,
-                             stale_policy=cfg.stale_policy)
+                             stale_policy=cfg.stale_policy,
+                             delay_comp=delay_comp_coefficient(cfg))
     ps_path = _ps_resume_path(cfg)
     if ps_path:
         server.load_checkpoint(ps_path)
@@ -505,6 +549,7 @@ def run_training(cfg: TrainConfig, info: DistInfo):
     """Entry point for every rank. Returns a result dict (worker) or PS stats."""
     check_stale_config(cfg, info)
     check_push_wire_config(cfg)
+    check_delay_comp_config(cfg, info)
     ps_groups = None
     central = cfg.mode == "asgd" and cfg.ps == "central" and info.is_distributed
     if central:

@@ -20,7 +20,7 @@ import torch
 
 from ..parallel.clients import SharedPS, SharedPSClient
 from .dist import DistInfo
-from .trainer import TrainConfig, Worker, _dtype
+from .trainer import TrainConfig, Worker, _dtype, delay_comp_coefficient
 
 
 class VirtualWorkers:
@@ -33,7 +33,9 @@ class VirtualWorkers:
                             else torch.device("cpu"))
         self.device = device
         self.cuda = device.type == "cuda"
-        self.shared = SharedPS()
+        # delay compensation (cfg.delay_comp = lambda): the shared PS takes c and keeps
+        # one backup per worker index
+        self.shared = SharedPS(delay_comp=delay_comp_coefficient(cfg))
         self.workers: list[Worker] = []
         self.streams = [torch.cuda.Stream(device) if self.cuda else None for _ in range(k)]
         kw = dict(staleness=cfg.staleness, pull_mode=cfg.pull_mode,
@@ -41,7 +43,7 @@ class VirtualWorkers:
         for i in range(k):
             with self._on(i):
                 w = Worker(replace(cfg, seed=cfg.seed + i), DistInfo(device=device),
-                           client=SharedPSClient(self.shared, **kw))
+                           client=SharedPSClient(self.shared, worker=i, **kw))
             self.workers.append(w)
 
     def _on(self, i: int):
@@ -78,3 +80,7 @@ class VirtualWorkers:
 
     def stats(self) -> list[dict]:
         return [w.opt.stats() for w in self.workers]
+
+    def ps_stats(self) -> dict:
+        """The shared PS's counters (version, compensated / uncompensated pushes)."""
+        return self.shared.stats()
