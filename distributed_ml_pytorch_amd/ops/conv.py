@@ -31,9 +31,11 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from ._ext import native
+from ._grads import GradSink
 from ._policy import stock_gpu
-from .functional import (DEFER_RES_STATS, apply_bitmask, deferred_mask, is_relu_masked,
-                         resolve_deferred, set_nonneg)
+from .functional import (DEFER_RES_STATS, apply_bitmask, clean_slots, deferred_mask,
+                         is_relu_masked, resolve_deferred, set_nonneg)
+from .linear import bias_grad_acc, gemm, weight_grads
 from .tuner import TUNER
 
 _NATIVE_ENABLED = True
@@ -93,6 +95,25 @@ def set_native_conv(enabled: bool):
 
 def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def _shadow16(master):
+    """The arena's channels-last bf16 shadow of ``master``, else a one-off cast."""
+    w16 = getattr(master, "_dmp_w16", None)
+    if w16 is None or not w16.is_contiguous(memory_format=torch.channels_last):
+        w16 = master.detach().to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+    return w16
+
+
+def _shadow_arena(master, w16):
+    """The arena of ``master`` if ``w16`` is its own shadow there (so the arena's
+    batched images of that shadow apply), else None."""
+    ref = getattr(master, "_dmp_arena_ref", None)
+    arena = ref() if ref is not None else None
+    shadow = getattr(master, "_dmp_w16", None)
+    if arena is not None and shadow is not None and shadow.data_ptr() == w16.data_ptr():
+        return arena
+    return None
 
 
 def _configs():
@@ -168,8 +189,6 @@ def _rows_nhwc(t):
 
 
 def _gemm1x1_fwd(x, w16, part=None, relu=False):
-    from .linear import gemm
-
     B, CI, H, W = x.shape
     CO = w16.shape[0]
     y2 = torch.empty(B * H * W, CO, dtype=x.dtype, device=x.device)
@@ -178,8 +197,6 @@ def _gemm1x1_fwd(x, w16, part=None, relu=False):
 
 
 def _gemm1x1_dgrad(dy, w16, addend=None, addend_mask=None):
-    from .linear import gemm
-
     B, CO, H, W = dy.shape
     CI = w16.shape[1]
     dx2 = torch.empty(B * H * W, CI, dtype=dy.dtype, device=dy.device)
@@ -191,8 +208,6 @@ def _gemm1x1_dgrad(dy, w16, addend=None, addend_mask=None):
 
 def _gemm1x1_wgrad(dy, x, g):
     """g: fp32 [CO, CI, 1, 1] (channels_last) accumulated in place."""
-    from .linear import gemm
-
     gemm(2, 3, _rows_nhwc(dy), _rows_nhwc(x), g.reshape(g.shape[0], g.shape[1]))
 
 
@@ -223,8 +238,6 @@ def _im2col_wgrad_ok(x, shape, stride, pad) -> bool:
 
 def _im2col_wgrad(dy, x, g, stride, pad):
     """g: fp32 [CO, CI, R, S] channels_last, accumulated in place."""
-    from .linear import gemm
-
     CO, CI, R, S = g.shape
     K = R * S * CI
     cols = native().im2col(x.contiguous(memory_format=torch.channels_last), R, S, stride, pad, K)
@@ -382,91 +395,52 @@ class _NativeConv(Function):
             DEFER_RES_STATS["native"] += 1
         sub = ctx.alias_sub and dxa is not None
         sub_after = None          # subsampled alias gradient added after the dgrad
+        dcfg = _dgrad_cfg(dy, w16, H, W, stride, pad) if ctx.needs_input_grad[0] else None
         if sub and not ctx.needs_input_grad[0]:
             dx = torch.zeros(x.shape, dtype=dxa.dtype, device=dxa.device).contiguous(
                 memory_format=torch.channels_last)
             dx[:, :, ::2, ::2] = dxa
             dxa = None
-        elif sub and (stride != 2 or _dgrad_cfg(dy, w16, H, W, stride, pad) == _GEMM_ROUTE):
+        elif sub and (stride != 2 or dcfg == _GEMM_ROUTE):
             sub_after, dxa, sub = dxa.contiguous(memory_format=torch.channels_last), None, False
-        if ctx.needs_input_grad[0] and _dgrad_cfg(dy, w16, H, W, stride, pad) == _GEMM_ROUTE:
+        if dcfg == _GEMM_ROUTE:
             dx = _gemm1x1_dgrad(dy, w16, dxa, amask)
         elif ctx.needs_input_grad[0]:
-            cfg = _dgrad_cfg(dy, w16, H, W, stride, pad)
-            wt = None
-            ref = getattr(master, "_dmp_arena_ref", None)
-            arena = ref() if ref is not None else None
-            shadow = getattr(master, "_dmp_w16", None)
-            if arena is not None and shadow is not None and shadow.data_ptr() == w16.data_ptr():
-                wt = arena.transposed_conv_shadow(master)
-            dx = native().conv_dgrad(dy, w16, H, W, stride, pad, cfg, wt, dxa,
+            arena = _shadow_arena(master, w16)
+            wt = arena.transposed_conv_shadow(master) if arena is not None else None
+            dx = native().conv_dgrad(dy, w16, H, W, stride, pad, dcfg, wt, dxa,
                                      addend_sub=sub, addend_mask=amask)
         elif dxa is not None:
             dx = dxa
         if sub_after is not None:
             dx = dx.contiguous(memory_format=torch.channels_last)
             native().add_subsampled2(dx, sub_after)
-        gw = None
         bias = ctx.bias
+        sw = GradSink(master, master is not None and master.requires_grad, "cl")
+        sb = GradSink(bias, bias is not None and bias.requires_grad)
         # a conv bias gradient (AlexNet) summed by the gather wgrad kernel from the
         # dY tiles it already stages (no separate column-sum launches)
         bias_in_wgrad = False
-        if master is not None and master.requires_grad:
+        if sw.buf is not None:
+            g = sw.buf
             wcfg = _wgrad_cfg(dy, x, tuple(master.shape), stride, pad)
-            g = master.grad if getattr(master, "_dmp_arena", False) else None
-            bias_in_wgrad = (bias is not None and bias.requires_grad and wcfg < _WH_BASE
-                             and getattr(bias, "_dmp_arena", False)
-                             and bias.grad is not None and bias.grad.is_contiguous()
-                             and bias.grad.dtype == torch.float32
-                             and g is not None and g.is_contiguous(
-                                 memory_format=torch.channels_last)
-                             and getattr(master, "_dmp_grad_ready", None) is None)
-            if wcfg in (_GEMM_ROUTE, _IM2COL_ROUTE):
-                gg = g if g is not None and g.is_contiguous(
-                    memory_format=torch.channels_last) else None
-                if gg is None:
-                    gw = torch.zeros(tuple(master.shape), dtype=torch.float32, device=x.device)
-                    gw = gw.contiguous(memory_format=torch.channels_last)
-                    _gemm_route_wgrad(wcfg, dy, x, gw, stride, pad)
-                    gw = gw.to(master.dtype)
-                else:
-                    cb = getattr(master, "_dmp_grad_ready", None)
-                    if cb is None and _WG_STREAM_ENABLED:
-                        _side_wgrad(x.device,
-                                    lambda: _gemm_route_wgrad(wcfg, dy, x, gg, stride, pad), dy, x)
-                    else:
-                        _gemm_route_wgrad(wcfg, dy, x, gg, stride, pad)
-                        if cb is not None:
-                            cb(master)
-            elif bias_in_wgrad:
-                native().conv_wgrad(dy, x, g, stride, pad, wcfg, bias.grad)
-            elif g is not None and g.is_contiguous(memory_format=torch.channels_last):
-                cb = getattr(master, "_dmp_grad_ready", None)
-                if cb is None and _WG_STREAM_ENABLED:
-                    _side_wgrad(x.device, lambda: native().conv_wgrad(dy, x, g, stride, pad, wcfg),
-                                dy, x)
+            bias_in_wgrad = (wcfg < _WH_BASE and sb.arena and sb.buf.is_contiguous()
+                             and sb.buf.dtype == torch.float32 and sw.arena and not sw.hooked)
+
+            def wgrad():
+                if wcfg in (_GEMM_ROUTE, _IM2COL_ROUTE):
+                    _gemm_route_wgrad(wcfg, dy, x, g, stride, pad)
                 else:
                     native().conv_wgrad(dy, x, g, stride, pad, wcfg)
-                    if cb is not None:
-                        cb(master)
+            if bias_in_wgrad:
+                native().conv_wgrad(dy, x, g, stride, pad, wcfg, sb.buf)
+            elif _WG_STREAM_ENABLED and sw.arena and not sw.hooked:
+                _side_wgrad(x.device, wgrad, dy, x)
             else:
-                gw = torch.zeros(tuple(master.shape), dtype=torch.float32, device=x.device)
-                gw = gw.contiguous(memory_format=torch.channels_last)
-                native().conv_wgrad(dy, x, gw, stride, pad, wcfg)
-                gw = gw.to(master.dtype)
-        gb = None
-        if bias is not None and bias.requires_grad and not bias_in_wgrad:
-            if (getattr(bias, "_dmp_arena", False) and bias.grad is not None
-                    and dy.shape[1] % 8 == 0):
-                from .linear import bias_grad_acc
-
-                bias_grad_acc(dy, bias.grad)
-                cb = getattr(bias, "_dmp_grad_ready", None)
-                if cb is not None:
-                    cb(bias)
-            else:
-                gb = dy.sum(dim=(0, 2, 3), dtype=torch.float32).to(bias.dtype)
-        return dx, None, gw, None, None, None, None, gb, None, None
+                wgrad()
+        if sb.buf is not None and not bias_in_wgrad:
+            bias_grad_acc(dy, sb.buf)
+        return dx, None, sw.done(), None, None, None, None, sb.done(), None, None
 
 
 def _ceil8(v: int) -> int:
@@ -484,8 +458,6 @@ class _Im2colConv(Function):
 
     @staticmethod
     def forward(ctx, x, w16, master, b16, bias, stride, pad, relu):
-        from .linear import gemm
-
         B, CI, H, W = x.shape
         CO, _, R, S = master.shape
         K = R * S * CI
@@ -496,12 +468,8 @@ class _Im2colConv(Function):
         if Kp != K:
             # the arena's batched padded-row image (one launch per step for every
             # such layer), else a one-off padded copy
-            ref = getattr(master, "_dmp_arena_ref", None)
-            arena = ref() if ref is not None else None
-            shadow = getattr(master, "_dmp_w16", None)
-            wp = None
-            if arena is not None and shadow is not None and shadow.data_ptr() == w16.data_ptr():
-                wp = arena.padded_rows_shadow(master, Kp)
+            arena = _shadow_arena(master, w16)
+            wp = arena.padded_rows_shadow(master, Kp) if arena is not None else None
             if wp is None:
                 wp = torch.zeros(CO, Kp, dtype=w16.dtype, device=w16.device)
                 wp[:, :K] = wmat
@@ -516,9 +484,6 @@ class _Im2colConv(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        from .linear import _arena_grad, gemm
-        from .functional import _notify
-
         cols, wp, y2 = ctx.saved_tensors
         master, bias = ctx.params
         B, CI, H, W, R, S, K, stride, pad = ctx.geom
@@ -527,33 +492,22 @@ class _Im2colConv(Function):
         dy2 = dy.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1).reshape(-1, CO)
         if y2 is not None and not masked:
             dy2 = native().relu_bwd(dy2, y2)
-        gw = gb = None
-        wants_w = master is not None and master.requires_grad
-        wants_b = bias is not None and bias.requires_grad
-        g = _arena_grad(master) if wants_w else None
-        gbias = _arena_grad(bias) if wants_b else None
-        tmp_w = wants_w and g is None
-        tmp_b = wants_b and gbias is None
-        if wants_w or wants_b:
-            gmat = (torch.zeros(CO, K, dtype=torch.float32, device=dy.device) if g is None
-                    else g)                                   # [CO, K] view of the arena grad
-            if tmp_b:
-                gbias = torch.zeros(CO, dtype=torch.float32, device=dy.device)
-            gemm(2, 3, dy2, cols[:, :K], gmat, dbias=gbias)
-            if tmp_w:
-                gw = gmat.view(CO, R, S, CI).permute(0, 3, 1, 2).to(master.dtype)
-            elif wants_w:
-                _notify(master)
-            if tmp_b:
-                gb = gbias.to(bias.dtype)
-            elif wants_b:
-                _notify(bias)
+        gw, gb = weight_grads(dy2, cols[:, :K], master, bias)
         dx = None
         if ctx.needs_input_grad[0]:
             dcols = torch.empty(dy2.shape[0], wp.shape[1], dtype=dy2.dtype, device=dy2.device)
             gemm(1, 0, dy2, wp, dcols)
             dx = native().col2im(dcols, B, CI, H, W, R, S, stride, pad)
         return dx, None, gw, None, gb, None, None, None
+
+
+def _wgrad_only(master, launch):
+    """The backward of a conv over data (no input gradient): ``launch(g)``
+    accumulates the weight gradient into the fp32 channels-last ``g``."""
+    sink = GradSink(master, master is not None and master.requires_grad, "cl")
+    if sink.buf is not None:
+        launch(sink.buf)
+    return sink.done()
 
 
 class _SmallConv(Function):
@@ -576,21 +530,7 @@ class _SmallConv(Function):
         if dy is None:
             return None, None, None, None, None, None, None
         (x,) = ctx.saved_tensors
-        stride, pad = ctx.geom
-        master = ctx.master
-        gw = None
-        if master is not None and master.requires_grad:
-            g = master.grad if getattr(master, "_dmp_arena", False) else None
-            if g is not None and g.is_contiguous(memory_format=torch.channels_last):
-                native().conv_small_wgrad(dy, x, g, stride, pad)
-                cb = getattr(master, "_dmp_grad_ready", None)
-                if cb is not None:
-                    cb(master)
-            else:
-                gw = torch.empty(tuple(master.shape), dtype=torch.float32, device=x.device,
-                                 memory_format=torch.channels_last).zero_()
-                native().conv_small_wgrad(dy, x, gw, stride, pad)
-                gw = gw.to(master.dtype)
+        gw = _wgrad_only(ctx.master, lambda g: native().conv_small_wgrad(dy, x, g, *ctx.geom))
         return None, None, gw, None, None, None, None
 
 
@@ -619,30 +559,25 @@ class _StemConv(Function):
         if dy is None:
             return None, None, None, None, None
         (xs,) = ctx.saved_tensors
-        master = ctx.master
-        gw = None
-        if master is not None and master.requires_grad:
-            g = master.grad if getattr(master, "_dmp_arena", False) else None
-            if g is not None and g.is_contiguous(memory_format=torch.channels_last):
-                native().stem_wgrad(dy, xs, g)
-                cb = getattr(master, "_dmp_grad_ready", None)
-                if cb is not None:
-                    cb(master)
-            else:
-                gw = torch.empty(tuple(master.shape), dtype=torch.float32, device=xs.device,
-                                 memory_format=torch.channels_last).zero_()
-                native().stem_wgrad(dy, xs, gw)
-                gw = gw.to(master.dtype)
+        gw = _wgrad_only(ctx.master, lambda g: native().stem_wgrad(dy, xs, g))
         return None, None, gw, None, None
 
 
+def _conv_route_ok(x, stride, padding, dilation, groups) -> bool:
+    """What every native conv route needs: a bf16 GPU NCHW input, one group, no
+    dilation, square integer stride / padding."""
+    if not (_NATIVE_ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
+        return False
+    if groups != 1 or _pair(dilation) != (1, 1):
+        return False
+    st, pd = _pair(stride), _pair(padding)
+    return st[0] == st[1] and pd[0] == pd[1] and isinstance(pd[0], int)
+
+
 def stem_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
-    if not (_NATIVE_ENABLED and _STEM != "im2col" and x.is_cuda and x.dtype == torch.bfloat16
-            and x.dim() == 4):
+    if not _conv_route_ok(x, stride, padding, dilation, groups) or _STEM == "im2col":
         return False
-    if x.requires_grad or groups != 1 or _pair(dilation) != (1, 1):
-        return False
-    if _pair(stride) != (2, 2) or _pair(padding) != (3, 3):
+    if x.requires_grad or _pair(stride) != (2, 2) or _pair(padding) != (3, 3):
         return False
     if tuple(weight.shape) != (64, 3, 7, 7):
         return False
@@ -650,12 +585,7 @@ def stem_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
 
 
 def small_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
-    if not (_NATIVE_ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
-        return False
-    if x.requires_grad or groups != 1 or _pair(dilation) != (1, 1):
-        return False
-    st, pd = _pair(stride), _pair(padding)
-    if st[0] != st[1] or pd[0] != pd[1] or not isinstance(pd[0], int):
+    if not _conv_route_ok(x, stride, padding, dilation, groups) or x.requires_grad:
         return False
     co, ci, r, s = weight.shape
     # VALU kernels: the pick only while K = R*S*CI is tiny (CIFAR-style 3x3x3
@@ -679,32 +609,18 @@ def bn_slot_buffer(owner, attr: str, channels: int, device, fresh: bool = True):
         buf = torch.zeros(n, dtype=torch.float32, device=device)
         object.__setattr__(owner, attr, buf)
     elif fresh:
-        from .functional import clean_slots
-
         clean_slots(buf)
     return buf
 
 
 def native_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
-    if not (_NATIVE_ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
-        return False
-    if groups != 1 or _pair(dilation) != (1, 1):
-        return False
-    st, pd = _pair(stride), _pair(padding)
-    if st[0] != st[1] or pd[0] != pd[1] or not isinstance(pd[0], int):
-        return False
-    co, ci = weight.shape[0], weight.shape[1]
-    return ci % 64 == 0 and co % 64 == 0
+    return (_conv_route_ok(x, stride, padding, dilation, groups)
+            and weight.shape[0] % 64 == 0 and weight.shape[1] % 64 == 0)
 
 
 def im2col_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
     """Any other conv with a bf16 GPU input: patch matrix + native GEMM."""
-    if not (_NATIVE_ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
-        return False
-    if groups != 1 or _pair(dilation) != (1, 1):
-        return False
-    st, pd = _pair(stride), _pair(padding)
-    return st[0] == st[1] and pd[0] == pd[1] and isinstance(pd[0], int)
+    return _conv_route_ok(x, stride, padding, dilation, groups)
 
 
 def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=False,
@@ -722,10 +638,7 @@ def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=F
         x = x.contiguous(memory_format=torch.channels_last)
         if master is not None and native_conv_supported(
                 x, master, stride, padding, dilation, groups):
-            w16 = getattr(master, "_dmp_w16", None)
-            if w16 is None or not w16.is_contiguous(memory_format=torch.channels_last):
-                w16 = master.detach().to(torch.bfloat16).contiguous(
-                    memory_format=torch.channels_last)
+            w16 = _shadow16(master)
             y, part, xa = _NativeConv.apply(x, w16, master, _pair(stride)[0], _pair(padding)[0],
                                             bool(want_stats and not relu),
                                             slots if want_stats and not relu else None, b,
@@ -740,10 +653,7 @@ def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=F
             return (y, xa) if alias else y
         if master is not None and b is None and not relu and _STEM != "im2col" and \
                 small_conv_supported(x, master, stride, padding, dilation, groups):
-            w16 = getattr(master, "_dmp_w16", None)
-            if w16 is None or not w16.is_contiguous(memory_format=torch.channels_last):
-                w16 = master.detach().to(torch.bfloat16).contiguous(
-                    memory_format=torch.channels_last)
+            w16 = _shadow16(master)
             y, part = _SmallConv.apply(x, w16, master, _pair(stride)[0], _pair(padding)[0],
                                        bool(want_stats), slots if want_stats else None)
             if part is not None:
@@ -751,10 +661,7 @@ def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=F
             return (y, x) if alias else y
         if master is not None and b is None and not relu and \
                 stem_conv_supported(x, master, stride, padding, dilation, groups):
-            w16 = getattr(master, "_dmp_w16", None)
-            if w16 is None or not w16.is_contiguous(memory_format=torch.channels_last):
-                w16 = master.detach().to(torch.bfloat16).contiguous(
-                    memory_format=torch.channels_last)
+            w16 = _shadow16(master)
             y, part = _StemConv.apply(x, w16, master, bool(want_stats),
                                       slots if want_stats else None)
             if part is not None:
@@ -762,10 +669,7 @@ def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=F
             return (y, x) if alias else y
         if master is not None and im2col_conv_supported(x, master, stride, padding, dilation,
                                                         groups):
-            w16 = getattr(master, "_dmp_w16", None)
-            if w16 is None or not w16.is_contiguous(memory_format=torch.channels_last):
-                w16 = master.detach().to(torch.bfloat16).contiguous(
-                    memory_format=torch.channels_last)
+            w16 = _shadow16(master)
             b16 = None
             if b is not None:
                 b16 = getattr(b, "_dmp_w16", None)

@@ -3,13 +3,8 @@
 GPU tensors run the hand-written HIP kernels (``_native``); CPU tensors run
 the PyTorch formulation of the same math, which doubles as the test oracle.
 
-Gradient plumbing for parameters that live in a :class:`FlatArena`
-(``p._dmp_arena`` set): the native backward writes/accumulates the fp32
-parameter gradient straight into ``p.grad`` (a view of the arena's flat grad
-buffer) and returns ``None`` for that input, so autograd never materialises a
-per-parameter grad tensor nor runs an AccumulateGrad copy.  The arena is told
-the gradient is ready through ``p._dmp_grad_ready`` (drives bucketed
-all-reduce overlap in sync-DP mode).
+Where each backward puts its parameter gradients (the arena's flat grad buffer
+or a returned tensor) is decided by :class:`._grads.GradSink`.
 """
 from __future__ import annotations
 
@@ -20,23 +15,10 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from ._ext import native
+from ._grads import GradSink, notify
 from ._policy import stock_gpu
 
 CL = torch.channels_last
-
-
-def _arena_grad(p):
-    """fp32 grad view for an arena-managed parameter, else None."""
-    if p is None or not getattr(p, "_dmp_arena", False):
-        return None
-    return p.grad
-
-
-def _notify(*ps):
-    for p in ps:
-        cb = getattr(p, "_dmp_grad_ready", None) if p is not None else None
-        if cb is not None:
-            cb(p)
 
 
 # ----------------------------------------------------- ReLU-mask hand-offs
@@ -158,7 +140,7 @@ class _ShadowWeight(Function):
         if p.grad is None:
             return g.to(p.dtype), None
         p.grad.add_(g)
-        _notify(p)
+        notify(p)
         return None, None
 
 
@@ -340,13 +322,9 @@ class _BNAct(Function):
         in_mask = deferred_mask(dy)
         if in_mask is not None and not (ctx.fold and not ctx.relu and not ctx.has_res):
             dy, in_mask = apply_bitmask(dy, in_mask), None
-        dg_arena, db_arena = _arena_grad(gamma), _arena_grad(beta)
-        need_g = gamma is not None and ctx.needs_input_grad[1]
-        need_b = beta is not None and ctx.needs_input_grad[2]
-        dg = dg_arena if dg_arena is not None else (
-            torch.zeros_like(gamma) if need_g else None)
-        db = db_arena if db_arena is not None else (
-            torch.zeros_like(beta) if need_b else None)
+        sg = GradSink(gamma, ctx.needs_input_grad[1], dtype=None)
+        sb = GradSink(beta, ctx.needs_input_grad[2], dtype=None)
+        dg, db = sg.buf, sb.buf
         if ctx.fold:
             if x.dim() == 4:
                 dy = dy.contiguous(memory_format=CL)
@@ -374,12 +352,8 @@ class _BNAct(Function):
                 dy = dy.contiguous()
             dx, dres = native().bn_bwd(x, dy, y, gamma, stats, dg, db, ctx.relu, ctx.has_res,
                                        ctx.bslots, mask)
-        if dg_arena is not None or db_arena is not None:
-            _notify(gamma, beta)
-        ret_g = None if (dg_arena is not None or not need_g) else dg
-        ret_b = None if (db_arena is not None or not need_b) else db
-        return (dx, ret_g, ret_b, (dres if ctx.has_res else None), None, None, None, None, None,
-                None, None, None)
+        return (dx, sg.done(), sb.done(), (dres if ctx.has_res else None), None, None, None, None,
+                None, None, None, None)
 
 
 def batch_norm_act(x, weight, bias, running_mean, running_var, training: bool, momentum: float,
@@ -502,22 +476,16 @@ class _BNReLUPool(Function):
     def backward(ctx, dp):
         x, idx, stats, xm = ctx.saved_tensors
         gamma, beta = ctx.gamma, ctx.beta
-        dg_arena, db_arena = _arena_grad(gamma), _arena_grad(beta)
-        need_g = gamma is not None and ctx.needs_input_grad[1]
-        need_b = beta is not None and ctx.needs_input_grad[2]
-        dg = dg_arena if dg_arena is not None else (torch.zeros_like(gamma) if need_g else None)
-        db = db_arena if db_arena is not None else (torch.zeros_like(beta) if need_b else None)
+        sg = GradSink(gamma, ctx.needs_input_grad[1], dtype=None)
+        sb = GradSink(beta, ctx.needs_input_grad[2], dtype=None)
         bs = _fresh_slots(ctx.bslots, x.shape[1], x.device)
         k, s, p = ctx.meta
-        dx = native().maxpool_bn_bwd(x, dp, idx, xm, gamma, stats, dg, db, bs, ctx.fpart, k, s, p)
+        dx = native().maxpool_bn_bwd(x, dp, idx, xm, gamma, stats, sg.buf, sb.buf, bs, ctx.fpart,
+                                     k, s, p)
         mark_slots(bs, True)
         mark_slots(ctx.fpart, False)
         ctx.fpart = None
-        if dg_arena is not None or db_arena is not None:
-            _notify(gamma, beta)
-        ret_g = None if (dg_arena is not None or not need_g) else dg
-        ret_b = None if (db_arena is not None or not need_b) else db
-        return dx, ret_g, ret_b, None, None, None, None, None, None, None, None, None
+        return dx, sg.done(), sb.done(), None, None, None, None, None, None, None, None, None
 
 
 def bn_relu_maxpool_ok(x, bn, k: int, s: int, p: int) -> bool:
@@ -611,6 +579,21 @@ def dropout(x, p: float, training: bool, channelwise: bool = False, state=None, 
 
 
 # ----------------------------------------------------------------- layernorm
+def _ln_backward(ctx, dy, dh, gi):
+    """``(dx, dgamma, dbeta)`` of the three LayerNorm Functions: ``dh`` is the
+    residual stream's own gradient (added inside the kernel), ``gi`` gamma's
+    position among the forward inputs (beta follows it)."""
+    x, mean, rstd = ctx.saved_tensors
+    gamma = ctx.gamma
+    sg = GradSink(gamma, ctx.needs_input_grad[gi])
+    sb = GradSink(ctx.beta, ctx.needs_input_grad[gi + 1])
+    g32 = gamma.detach() if gamma is not None else None
+    if dh is not None and dh.dtype != x.dtype:
+        dh = dh.to(x.dtype)
+    dx = native().layernorm_bwd(x, dy.to(x.dtype), g32, mean, rstd, sg.buf, sb.buf, ctx.slots, dh)
+    return dx, sg.done(), sb.done()
+
+
 class _LayerNorm(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, slots=None):
@@ -624,22 +607,7 @@ class _LayerNorm(Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, mean, rstd = ctx.saved_tensors
-        gamma, beta = ctx.gamma, ctx.beta
-        dg_arena, db_arena = _arena_grad(gamma), _arena_grad(beta)
-        need_g = gamma is not None and ctx.needs_input_grad[1]
-        need_b = beta is not None and ctx.needs_input_grad[2]
-        dg = dg_arena if dg_arena is not None else (
-            torch.zeros_like(gamma, dtype=torch.float32) if need_g else None)
-        db = db_arena if db_arena is not None else (
-            torch.zeros_like(beta, dtype=torch.float32) if need_b else None)
-        g32 = gamma.detach() if gamma is not None else None
-        dx = native().layernorm_bwd(x, dy, g32, mean, rstd, dg, db, ctx.slots)
-        if dg_arena is not None or db_arena is not None:
-            _notify(gamma, beta)
-        ret_g = None if (dg_arena is not None or not need_g) else dg.to(gamma.dtype)
-        ret_b = None if (db_arena is not None or not need_b) else db.to(beta.dtype)
-        return dx, ret_g, ret_b, None, None
+        return (*_ln_backward(ctx, dy, None, 1), None, None)
 
 
 class _AddLayerNorm(Function):
@@ -662,24 +630,8 @@ class _AddLayerNorm(Function):
     def backward(ctx, dh, dy):
         if dy is None:
             return dh, dh, None, None, None, None
-        h, mean, rstd = ctx.saved_tensors
-        gamma, beta = ctx.gamma, ctx.beta
-        dg_arena, db_arena = _arena_grad(gamma), _arena_grad(beta)
-        need_g = gamma is not None and ctx.needs_input_grad[2]
-        need_b = beta is not None and ctx.needs_input_grad[3]
-        dg = dg_arena if dg_arena is not None else (
-            torch.zeros_like(gamma, dtype=torch.float32) if need_g else None)
-        db = db_arena if db_arena is not None else (
-            torch.zeros_like(beta, dtype=torch.float32) if need_b else None)
-        g32 = gamma.detach() if gamma is not None else None
-        if dh is not None and dh.dtype != h.dtype:
-            dh = dh.to(h.dtype)
-        dx = native().layernorm_bwd(h, dy.to(h.dtype), g32, mean, rstd, dg, db, ctx.slots, dh)
-        if dg_arena is not None or db_arena is not None:
-            _notify(gamma, beta)
-        ret_g = None if (dg_arena is not None or not need_g) else dg.to(gamma.dtype)
-        ret_b = None if (db_arena is not None or not need_b) else db.to(beta.dtype)
-        return dx, dx, ret_g, ret_b, None, None
+        dx, dg, db = _ln_backward(ctx, dy, dh, 2)
+        return dx, dx, dg, db, None, None
 
 
 class _LayerNormStream(Function):
@@ -704,24 +656,7 @@ class _LayerNormStream(Function):
     def backward(ctx, dh, dy):
         if dy is None:
             return dh, None, None, None, None
-        x, mean, rstd = ctx.saved_tensors
-        gamma, beta = ctx.gamma, ctx.beta
-        dg_arena, db_arena = _arena_grad(gamma), _arena_grad(beta)
-        need_g = gamma is not None and ctx.needs_input_grad[1]
-        need_b = beta is not None and ctx.needs_input_grad[2]
-        dg = dg_arena if dg_arena is not None else (
-            torch.zeros_like(gamma, dtype=torch.float32) if need_g else None)
-        db = db_arena if db_arena is not None else (
-            torch.zeros_like(beta, dtype=torch.float32) if need_b else None)
-        g32 = gamma.detach() if gamma is not None else None
-        if dh is not None and dh.dtype != x.dtype:
-            dh = dh.to(x.dtype)
-        dx = native().layernorm_bwd(x, dy.to(x.dtype), g32, mean, rstd, dg, db, ctx.slots, dh)
-        if dg_arena is not None or db_arena is not None:
-            _notify(gamma, beta)
-        ret_g = None if (dg_arena is not None or not need_g) else dg.to(gamma.dtype)
-        ret_b = None if (db_arena is not None or not need_b) else db.to(beta.dtype)
-        return dx, ret_g, ret_b, None, None
+        return (*_ln_backward(ctx, dy, dh, 1), None, None)
 
 
 def stream_layer_norm(x, weight, bias, eps: float, slots=None):
@@ -840,21 +775,10 @@ class _VitEmbed(Function):
     @staticmethod
     def backward(ctx, dh):
         cls, pos = ctx.params
-        gc, gp = _arena_grad(cls), _arena_grad(pos)
-        tmp_c = gc is None and ctx.needs_input_grad[1]
-        tmp_p = gp is None and ctx.needs_input_grad[2]
-        if tmp_c:
-            gc = torch.zeros(cls.shape, dtype=torch.float32, device=dh.device)
-        if tmp_p:
-            gp = torch.zeros(pos.shape, dtype=torch.float32, device=dh.device)
-        dtok = native().vit_embed_bwd(dh, gp if ctx.needs_input_grad[2] else None,
-                                      gc if ctx.needs_input_grad[1] else None, ctx.tok_grad)
-        if not tmp_c and ctx.needs_input_grad[1]:
-            _notify(cls)
-        if not tmp_p and ctx.needs_input_grad[2]:
-            _notify(pos)
-        return (dtok if ctx.tok_grad else None, gc.to(cls.dtype) if tmp_c else None,
-                gp.to(pos.dtype) if tmp_p else None, None, None)
+        sc = GradSink(cls, ctx.needs_input_grad[1])
+        sp = GradSink(pos, ctx.needs_input_grad[2])
+        dtok = native().vit_embed_bwd(dh, sp.buf, sc.buf, ctx.tok_grad)
+        return dtok if ctx.tok_grad else None, sc.done(), sp.done(), None, None
 
 
 def vit_embed(tok, cls, pos):

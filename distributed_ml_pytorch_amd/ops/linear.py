@@ -33,7 +33,8 @@ import torch.nn.functional as F
 from torch.autograd import Function
 
 from ._ext import native
-from .functional import _notify, is_relu_masked, mark_relu_masked, nonneg, set_nonneg
+from ._grads import GradSink
+from .functional import is_relu_masked, mark_relu_masked, nonneg, set_nonneg
 from .tuner import TUNER
 
 _SMALL = -1            # any-shape fallback kernel
@@ -239,44 +240,19 @@ def _rows(t, k):
 
 
 # ------------------------------------------------------------ arena plumbing
-def _arena_grad(p):
-    if p is None or not p.requires_grad or not getattr(p, "_dmp_arena", False):
-        return None
-    g = p.grad
-    if g is None:
-        return None
-    if g.dim() == 4 and g.is_contiguous(memory_format=torch.channels_last):
-        # conv weight used as a GEMM (patch embedding): [Cout, kh*kw*Cin] view
-        return g.permute(0, 2, 3, 1).reshape(g.shape[0], -1)
-    return g if g.is_contiguous() else None
-
-
-def _weight_grads(dy2, x2, w, b):
+def weight_grads(dy2, x2, w, b):
     """dW (+ db) of ``y = x W^T + b``: accumulated into the fp32 arena views
-    when the parameters live in one (grad-ready hooks fired), else returned."""
-    N, K = dy2.shape[1], x2.shape[1]
-    gw = gb = None
-    g = _arena_grad(w) if w is not None and w.requires_grad else None
-    gbias = _arena_grad(b) if b is not None and b.requires_grad else None
-    tmp_w = g is None and w is not None and w.requires_grad
-    tmp_b = gbias is None and b is not None and b.requires_grad
-    if g is None and (tmp_w or tmp_b or gbias is not None):
-        g = torch.zeros(N, K, dtype=torch.float32, device=dy2.device)
-    if tmp_b:
-        gbias = torch.zeros(N, dtype=torch.float32, device=dy2.device)
+    when the parameters live in one (grad-ready hooks fired), else returned.
+    ``w`` may be a conv weight used as a GEMM (patch embedding, im2col conv):
+    its channels-last gradient is the [Cout, kh*kw*Cin] output."""
+    sw = GradSink(w, w is not None and w.requires_grad, "rows")
+    sb = GradSink(b, b is not None and b.requires_grad)
+    g = sw.buf
+    if g is None and sb.buf is not None:      # bias only: the GEMM still needs its C operand
+        g = torch.zeros(dy2.shape[1], x2.shape[1], dtype=torch.float32, device=dy2.device)
     if g is not None:
-        gemm(2, 3, dy2, x2, g, dbias=gbias)
-    if tmp_w:
-        gw = g.to(w.dtype)
-        if w.dim() == 4:                     # patch embedding: (kh, kw, Cin) columns
-            gw = gw.view(w.shape[0], w.shape[2], w.shape[3], w.shape[1]).permute(0, 3, 1, 2)
-    elif w is not None and w.requires_grad:
-        _notify(w)
-    if tmp_b:
-        gb = gbias.to(b.dtype)
-    elif b is not None and b.requires_grad:
-        _notify(b)
-    return gw, gb
+        gemm(2, 3, dy2, x2, g, dbias=sb.buf)
+    return sw.done(), sb.done()
 
 
 class _ArenaLinear(Function):
@@ -313,7 +289,7 @@ class _ArenaLinear(Function):
             dx = dx.view(ctx.xshape)
             if ctx.x_nonneg:
                 mark_relu_masked(dx)
-        gw, gb = _weight_grads(dy2, x2, w, b)
+        gw, gb = weight_grads(dy2, x2, w, b)
         return dx, None, None, gw, gb, None
 
 
@@ -339,27 +315,13 @@ class _GapLinear(Function):
         f, w16 = ctx.saved_tensors
         w, b = ctx.params
         N, C = w16.shape
-        gw = _arena_grad(w) if w.requires_grad else None
-        gb = _arena_grad(b) if b is not None and b.requires_grad else None
-        tmp_w = gw is None
-        tmp_b = gb is None and b is not None and b.requires_grad
-        if tmp_w:
+        sw = GradSink(w, w.requires_grad, "rows")
+        sb = GradSink(b, b is not None and b.requires_grad)
+        gw = sw.buf                          # the kernel always writes a weight gradient
+        if gw is None:
             gw = torch.zeros(N, C, dtype=torch.float32, device=dy.device)
-        if tmp_b:
-            gb = torch.zeros(N, dtype=torch.float32, device=dy.device)
-        dx = native().gap_linear_bwd(dy, f, w16, gw, gb, ctx.hw[0], ctx.hw[1])
-        gw_out = gb_out = None
-        if w.requires_grad:
-            if tmp_w:
-                gw_out = gw.to(w.dtype)
-            else:
-                _notify(w)
-        if b is not None and b.requires_grad:
-            if tmp_b:
-                gb_out = gb.to(b.dtype)
-            else:
-                _notify(b)
-        return dx, None, None, gw_out, gb_out
+        dx = native().gap_linear_bwd(dy, f, w16, gw, sb.buf, ctx.hw[0], ctx.hw[1])
+        return dx, None, None, sw.done(), sb.done()
 
 
 def gap_linear_ok(x, linear) -> bool:
@@ -450,10 +412,10 @@ class _ArenaMLP(Function):
         x2, h, g, w1_16, w2_16 = ctx.saved_tensors
         w1, b1, w2, b2 = ctx.params
         dy2 = _rows(dy, w2_16.shape[0])
-        gw2, gb2 = _weight_grads(dy2, g, w2, b2)
+        gw2, gb2 = weight_grads(dy2, g, w2, b2)
         dh = torch.empty_like(h)
         gemm(1, 2, dy2, w2_16, dh, aux=h)          # (dY W2) * gelu'(h)
-        gw1, gb1 = _weight_grads(dh, x2, w1, b1)
+        gw1, gb1 = weight_grads(dh, x2, w1, b1)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x2)
