@@ -282,16 +282,27 @@ std::vector<Tensor> dropout_fwd(Tensor x, double p, int64_t seed, Tensor offset,
   return {y, mask};
 }
 
-Tensor dropout_bwd(Tensor dy, Tensor mask, double p, int64_t mode) {
+// `channels_last`: the dense format the forward drew the mask in (its input's).
+// dy is brought to it (a copy only on a mismatch) and dx comes back in it: the
+// element-wise mask is indexed in memory order, so the format is the forward's
+// to state, never a guess from how the gradient happens to arrive.
+Tensor dropout_bwd(Tensor dy, Tensor mask, double p, int64_t mode, bool channels_last) {
   check_gpu(dy, "dy");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "dropout_bwd: bad mode");
+  TORCH_CHECK(mode == 0 || channels_last == (mode == 2),
+              "dropout_bwd: mode 1 masks NCHW planes, mode 2 channels_last ones");
+  TORCH_CHECK(!channels_last || dy.dim() == 4, "dropout_bwd: channels_last needs [N, C, H, W]");
+  TORCH_CHECK(mode == 0 || dy.dim() >= 3, "channel dropout needs [N, C, ...]");
   long long inner = 1;
   int C = 1;
-  if (mode == 2) dy = dy.contiguous(kCL);
-  else if (!(mode == 0 && dy.is_contiguous(kCL))) dy = dy.contiguous();
+  dy = channels_last ? dy.contiguous(kCL) : dy.contiguous();
   if (mode != 0) {
     C = (int)dy.size(1);
     inner = dy.numel() / (dy.size(0) * C);
   }
+  TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == at::kByte && mask.is_contiguous() &&
+                  mask.numel() == (mode == 0 ? dy.numel() : dy.size(0) * (int64_t)C),
+              "dropout_bwd: mask must be the forward's uint8 keep mask");
   auto dx = at::empty_like(dy);
   const float scale = (float)(1.0 / (1.0 - p));
   if (dy.scalar_type() == at::kBFloat16)

@@ -123,9 +123,12 @@ __global__ void __launch_bounds__(1024) softmax_xent_kernel(
     sx = wave_sum(sx);
     const float lse = m + __logf(s);
     const float xy = valid ? ld(x, y) : 0.f;
-    // loss = (1-eps) * (lse - x_y) + eps * (lse - mean(x))
+    // loss = (1-eps) * (lse - x_y) + eps * (lse - mean(x)); the smoothing term
+    // is not formed at eps = 0: a -inf logit makes mean(x) -inf, and 0 * inf
+    // would turn a finite loss into NaN
     const float eps = label_smoothing;
-    const float loss = valid ? ((1.f - eps) * (lse - xy) + eps * (lse - sx / (float)C)) : 0.f;
+    const float smooth_loss = eps > 0.f ? eps * (lse - sx / (float)C) : 0.f;
+    const float loss = valid ? ((1.f - eps) * (lse - xy) + smooth_loss) : 0.f;
     // pass 3: gradient
     if (dlogits) {
       T* d = dlogits + (long long)r * C;
@@ -217,7 +220,9 @@ __global__ void __launch_bounds__(1024) softmax_xent_narrow_kernel(
       }
     }
     const float lse = __logf(se);   // shifted by m, like xy and sx
-    const float loss = valid ? ((1.f - eps) * (lse - xy) + eps * (lse - sx / (float)C)) : 0.f;
+    // no smoothing term at eps = 0 (0 * inf = NaN when a logit is -inf)
+    const float smooth_loss = eps > 0.f ? eps * (lse - sx / (float)C) : 0.f;
+    const float loss = valid ? ((1.f - eps) * (lse - xy) + smooth_loss) : 0.f;
     if (dlogits) {
       T* d = dlogits + (long long)r * C;
       const float inv = 1.f / se;

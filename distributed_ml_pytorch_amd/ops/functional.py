@@ -542,12 +542,15 @@ class _Dropout(Function):
         y, mask = native().dropout_fwd(x, float(p), int(seed), offset, int(mode))
         ctx.save_for_backward(mask)
         ctx.p, ctx.mode = p, mode
+        # the dense format the mask was drawn in (element-wise: memory order);
+        # the backward brings dy to it, however the gradient arrives
+        ctx.cl = x.dim() == 4 and x.is_contiguous(memory_format=CL) and not x.is_contiguous()
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (mask,) = ctx.saved_tensors
-        dx = native().dropout_bwd(dy, mask, float(ctx.p), int(ctx.mode))
+        dx = native().dropout_bwd(dy, mask, float(ctx.p), int(ctx.mode), ctx.cl)
         if is_relu_masked(dy):
             mark_relu_masked(dx)       # a positive scaling keeps the mask valid
         return dx, None, None, None, None
