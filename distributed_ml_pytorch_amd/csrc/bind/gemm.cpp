@@ -81,6 +81,9 @@ void gemm(int64_t mode, int64_t epi, int64_t cfg, Tensor a, Tensor b, Tensor c,
               "gemm: epilogue ", epi, " not available in mode ", mode);
   TORCH_CHECK(dmp::gemm_config_ok((int)mode, (int)cfg), "gemm: config ", cfg,
               " is not available in mode ", mode);
+  TORCH_CHECK(splits <= 1 || mode == 2,
+              "gemm: split-K only in the weight-gradient mode, got splits ", splits, " in mode ",
+              mode);
   const int64_t M = c.size(0), N = c.size(1);
   const int64_t K = mode == 2 ? a.size(0) : a.size(1);
   const int64_t lda = mat_ld(a, at::kBFloat16, mode == 2 ? K : M, mode == 2 ? M : K, "a");
@@ -155,23 +158,11 @@ void gemm(int64_t mode, int64_t epi, int64_t cfg, Tensor a, Tensor b, Tensor c,
     const int sp = dmp::gemm_effective_splits((int)K, (int)std::max<int64_t>(1, splits));
     if (sp > 1) ws = at::empty({(int64_t)sp * M * N}, c.options().dtype(at::kFloat));
   }
-  // fwd / dgrad remainder split-K: per-call fp32 piece workspace + zeroed tickets
-  // (caching-allocator memory: safe inside a captured graph)
-  Tensor skw, skc;
-  if (mode != 2 && cfg >= 0 && splits > 1) {
-    long long wf = 0;
-    int nc = 0;
-    dmp::gemm_sk_sizes((int)cfg, (int)M, (int)N, (int)K, (int)splits, &wf, &nc);
-    if (wf > 0 && nc > 0) {
-      skw = at::empty({(int64_t)wf}, c.options().dtype(at::kFloat));
-      skc = at::zeros({(int64_t)nc}, c.options().dtype(at::kInt));
-    }
-  }
   dmp::launch_gemm((int)mode, (int)epi, (int)cfg, bf16(a), (int)lda, bf16(b), (int)ldb,
                    c.data_ptr(), (int)ldc, c2p, bf16_or_null(bias), auxp,
                    ptr_or_null<float>(dbias), (int)M, (int)N, (int)K,
                    (int)std::max<int64_t>(1, splits), cur_stream(), relu, partp,
-                   ptr_or_null<float>(ws), ptr_or_null<float>(skw), ptr_or_null<int>(skc), amp);
+                   ptr_or_null<float>(ws), amp);
 }
 
 std::vector<std::vector<int64_t>> gemm_configs() {
@@ -182,14 +173,6 @@ std::vector<std::vector<int64_t>> gemm_configs() {
 
 void bind_gemm(pybind11::module_& m) {
   m.def("pad_rows_batched", &pad_rows_batched, "padded-row copies of im2col conv weights");
-  m.def("gemm_sk_pieces",
-        [](int64_t cfg, int64_t M, int64_t N, int64_t K, int64_t splits) {
-          long long wf = 0;
-          int nc = 0;
-          dmp::gemm_sk_sizes((int)cfg, (int)M, (int)N, (int)K, (int)splits, &wf, &nc);
-          return nc > 0 ? wf / std::max<long long>(1, nc) : 0LL;
-        },
-        "fwd / dgrad remainder split-K: fp32 workspace floats per split tile (0 = no split)");
   m.def("colsum_acc", &colsum_acc, "bias gradient: out[n] += sum_m dy[m][n] (bf16 -> fp32)",
         py::arg("dy"), py::arg("out"), py::arg("slots") = py::none());
   m.def("colsum_num_slots", &dmp::colsum_num_slots, "slot rows of the colsum scratch");

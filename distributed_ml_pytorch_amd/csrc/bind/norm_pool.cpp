@@ -160,13 +160,10 @@ std::vector<Tensor> bn_bwd_fold(Tensor x, Tensor dy, optional<Tensor> y, optiona
   auto b = bn_bwd_front(x, dy, y, gamma, stats, dgamma, dbeta, relu, want_dres, mask);
   auto part = bn_slots(slots, b.C, b.fopt);
   float* zb = other_slots(zero_buf, b.C, b.fopt, part);
-  // [3][C] coefficient hand-off of the one-pass kernel (bn.hip bn_bwd_onepass_kernel)
-  auto coef = at::empty({3 * b.C}, b.fopt);
   dmp::launch_bn_bwd_fold(bf16(x), bf16(dy), b.y, ptr_or_null<float>(gamma),
                           stats.data_ptr<float>(), ptr_or_null<float>(dgamma),
                           ptr_or_null<float>(dbeta), part.data_ptr<float>(), zb, bf16(b.dx),
-                          bf16_or_null(b.dres), b.M, (int)b.C, relu, cur_stream(), b.mask,
-                          coef.data_ptr<float>());
+                          bf16_or_null(b.dres), b.M, (int)b.C, relu, cur_stream(), b.mask);
   return b.result();
 }
 

@@ -91,8 +91,7 @@ void launch_bn_fwd_fold(const uint16_t* x, const uint16_t* res, uint16_t* y, con
 void launch_bn_bwd_fold(const uint16_t* x, const uint16_t* dy, const uint16_t* y,
                         const float* gamma, const float* stats, float* dgamma, float* dbeta,
                         float* part, float* zero_buf, uint16_t* dx, uint16_t* dres, long long M,
-                        int C, bool relu, hipStream_t s, const uint8_t* mask,
-                        float* coef = nullptr);   // [3][C] scratch: one-pass kernel (bn.hip)
+                        int C, bool relu, hipStream_t s, const uint8_t* mask);
 // BN + ReLU + max pool 3x3/s2/p1 fused (ImageNet ResNet stem), folded finalize
 bool bn_maxpool_supported(int C, int K, int S, int P);
 void launch_bn_relu_maxpool_fold(const uint16_t* x, uint16_t* y, uint8_t* idx, uint16_t* xm,
@@ -264,11 +263,7 @@ void launch_gemm(int mode, int epi, int cfg, const uint16_t* a, int lda, const u
                  int ldb, void* c, int ldc, uint16_t* c2, const uint16_t* bias,
                  const uint16_t* aux, float* dbias, int M, int N, int K, int splits,
                  hipStream_t s, bool relu = false, float* part = nullptr,
-                 float* slab = nullptr, float* sk_ws = nullptr, int* sk_cnt = nullptr,
-                 const uint8_t* auxmask = nullptr);
-// remainder split-K of a fwd / dgrad launch_gemm (splits > 1): fp32 workspace
-// floats and ticket counters it needs for (cfg, M, N, K, splits); 0 = not split
-void gemm_sk_sizes(int cfg, int M, int N, int K, int splits, long long* ws_floats, int* counters);
+                 float* slab = nullptr, const uint8_t* auxmask = nullptr);
 // effective split-K count of launch_gemm (mode 2) for K and a requested count
 int gemm_effective_splits(int K, int splits);
 

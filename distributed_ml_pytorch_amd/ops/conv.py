@@ -45,49 +45,6 @@ _SMALL_MAX_K = 32
 # statistics in the epilogue), "im2col" = patch matrix + MFMA GEMM
 _STEM = os.environ.get("DMP_STEM", "small")
 
-# Weight gradients on a side HIP stream.  A layer's wgrad depends only on its
-# dY and X, and nothing in the rest of the backward depends on it (it lands in
-# the fp32 grad arena), so it runs concurrently with the dgrad -> BN-backward
-# chain of the layers below: the MFMA-bound wgrad fills the CUs that the
-# latency-bound BN reductions / finalizes and the small-grid layer-4 convs
-# leave idle.  The side stream is joined back (current stream waits on it) by
-# an autograd end-of-backward callback, so callers -- including hipGraph
-# capture -- see an ordinary single-stream backward.  Disabled for parameters
-# with a grad-ready hook (sync-DP bucket all-reduce orders on the current
-# stream).  Opt-in (DMP_WGRAD_STREAM=1): measured on ResNet-18/CIFAR bs256 the
-# concurrent wgrad grids delay the single-block BN finalize kernels on the
-# critical path (bwd finalize 96 -> 244 us/step) and the step got 3.6% slower
-# (profiles/bench_steady_state_wgrad_stream_r1.txt); round 2 at bs512 (GEMM-route
-# 1x1 wgrads included): ResNet-18 -4 %, ResNet-50 +0.7 % (noise), and replaying
-# the graph on a high-priority stream -30 % (profiles/wgrad_stream_ab_r2.txt).
-_WG_STREAM_ENABLED = os.environ.get("DMP_WGRAD_STREAM", "0") == "1"
-_WG_STREAMS: dict = {}
-_WG_KEEP: list = []          # operands kept alive until the join
-_WG_JOIN_QUEUED = [False]
-
-
-def _wg_join():
-    _WG_JOIN_QUEUED[0] = False
-    cur = torch.cuda.current_stream()
-    for side in _WG_STREAMS.values():
-        cur.wait_stream(side)
-    _WG_KEEP.clear()
-
-
-def _side_wgrad(dev, fn, *keep):
-    """Run ``fn()`` on the device's wgrad stream (ordered after the current stream)."""
-    side = _WG_STREAMS.get(dev)
-    if side is None:
-        side = _WG_STREAMS[dev] = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        fn()
-    _WG_KEEP.append(keep)
-    if not _WG_JOIN_QUEUED[0]:
-        _WG_JOIN_QUEUED[0] = True
-        torch.autograd.Variable._execution_engine.queue_callback(_wg_join)
-
-
 def set_native_conv(enabled: bool):
     global _NATIVE_ENABLED
     _NATIVE_ENABLED = bool(enabled)
@@ -174,6 +131,9 @@ def _halo_candidates(H, W, C, R, S, stride, pad):
 # tuner candidate (_GEMM_ROUTE) next to the conv tiles for every such layer
 # (the ResNet-50 bottleneck's 1x1 convs).
 _GEMM_ROUTE = 30000
+# 30001 was a patch-matrix weight-gradient route (retired: it measured 2.2-6x slower,
+# profiles/im2col_wgrad_route_r6.txt); only a private tune cache can still hold it
+_RETIRED_PATCH_ROUTE = 30001
 _GEMM_1X1 = os.environ.get("DMP_CONV_GEMM1X1", "1") != "0"
 
 
@@ -209,46 +169,6 @@ def _gemm1x1_dgrad(dy, w16, addend=None, addend_mask=None):
 def _gemm1x1_wgrad(dy, x, g):
     """g: fp32 [CO, CI, 1, 1] (channels_last) accumulated in place."""
     gemm(2, 3, _rows_nhwc(dy), _rows_nhwc(x), g.reshape(g.shape[0], g.shape[1]))
-
-
-# ------------------------------------ weight gradient as patch matrix x GEMM
-# dW[co][(r, s, ci)] += sum_p dY[p][co] cols[p][(r, s, ci)]: the native patch
-# matrix (csrc/im2col.hip, 16-B taps when CI % 8 == 0) into the wgrad GEMM
-# (mode 2, split-K over the pixels, fp32 into the arena view -- the
-# channels_last [CO][R][S][CI] gradient IS the [CO][K] GEMM output).  A tuner
-# candidate for the small-map layers (ResNet-18 layer3 / layer4 at the
-# reference batch 64: 1024-4096 pixels, 256-512 channels), bounded by the patch
-# matrix size.  Opt-in (DMP_CONV_IM2COL_WGRAD=1): graph-replayed per-candidate
-# timing put it at 2.2-6x the gather / halo picks on every ResNet-18 bs64 3x3
-# key (45-61 vs 7-22 us: the patch-matrix write plus a short-K GEMM launch,
-# profiles/im2col_wgrad_route_r6.txt), so the tuner is not offered it by default.
-_IM2COL_ROUTE = 30001
-_IM2COL_WGRAD = os.environ.get("DMP_CONV_IM2COL_WGRAD", "0") == "1"
-_IM2COL_WGRAD_MAX_BYTES = 64 << 20
-
-
-def _im2col_wgrad_ok(x, shape, stride, pad) -> bool:
-    CO, CI, R, S = shape
-    if not _IM2COL_WGRAD or (R, S) == (1, 1) or CI % 8 or CO % 8:
-        return False
-    B, _, H, W = x.shape
-    OH, OW = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
-    return 2 * B * OH * OW * R * S * CI <= _IM2COL_WGRAD_MAX_BYTES
-
-
-def _im2col_wgrad(dy, x, g, stride, pad):
-    """g: fp32 [CO, CI, R, S] channels_last, accumulated in place."""
-    CO, CI, R, S = g.shape
-    K = R * S * CI
-    cols = native().im2col(x.contiguous(memory_format=torch.channels_last), R, S, stride, pad, K)
-    gemm(2, 3, _rows_nhwc(dy), cols, g.permute(0, 2, 3, 1).reshape(CO, K))
-
-
-def _gemm_route_wgrad(route, dy, x, g, stride, pad):
-    if route == _IM2COL_ROUTE:
-        _im2col_wgrad(dy, x, g, stride, pad)
-    else:
-        _gemm1x1_wgrad(dy, x, g)
 
 
 def _fwd_cfg(x, w16, stride, pad):
@@ -293,7 +213,11 @@ def _dgrad_cfg(dy, w16, H, W, stride, pad):
 def _wgrad_cfg(dy, x, shape, stride, pad):
     key = ("wgrad", *x.shape, *shape, stride, pad)
     if key in TUNER.cache or not TUNER.enabled:
-        return TUNER.cache.get(key, -1)
+        pick = TUNER.cache.get(key, -1)
+        if pick == _RETIRED_PATCH_ROUTE:
+            raise RuntimeError(f"conv: tune cache entry {pick} for {key} is the retired "
+                               "patch-matrix weight-gradient route; re-tune this key")
+        return pick
     scratch = torch.empty(shape, dtype=torch.float32, device=x.device,
                           memory_format=torch.channels_last).zero_()
     K = shape[1] * shape[2] * shape[3]
@@ -304,12 +228,10 @@ def _wgrad_cfg(dy, x, shape, stride, pad):
                                                        stride, pad))
     if _gemm1x1_ok(shape, stride, pad, shape[1], shape[0]):
         cands.append(_GEMM_ROUTE)
-    elif _im2col_wgrad_ok(x, shape, stride, pad):
-        cands.append(_IM2COL_ROUTE)
 
     def run(c):
-        if c in (_GEMM_ROUTE, _IM2COL_ROUTE):
-            _gemm_route_wgrad(c, dy, x, scratch, stride, pad)
+        if c == _GEMM_ROUTE:
+            _gemm1x1_wgrad(dy, x, scratch)
         else:
             native().conv_wgrad(dy, x, scratch, stride, pad, c)
     return TUNER.best(key, run, cands)
@@ -428,14 +350,12 @@ class _NativeConv(Function):
                              and sb.buf.dtype == torch.float32 and sw.arena and not sw.hooked)
 
             def wgrad():
-                if wcfg in (_GEMM_ROUTE, _IM2COL_ROUTE):
-                    _gemm_route_wgrad(wcfg, dy, x, g, stride, pad)
+                if wcfg == _GEMM_ROUTE:
+                    _gemm1x1_wgrad(dy, x, g)
                 else:
                     native().conv_wgrad(dy, x, g, stride, pad, wcfg)
             if bias_in_wgrad:
                 native().conv_wgrad(dy, x, g, stride, pad, wcfg, sb.buf)
-            elif _WG_STREAM_ENABLED and sw.arena and not sw.hooked:
-                _side_wgrad(x.device, wgrad, dy, x)
             else:
                 wgrad()
         if sb.buf is not None and not bias_in_wgrad:
@@ -594,7 +514,7 @@ def small_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
 
 
 BN_SLOTS = 64   # csrc/bn_slots.h kBnSlots
-BN_TAIL = 4     # csrc/bn_slots.h kBnTail (arrival ticket)
+BN_TAIL = 4     # csrc/bn_slots.h kBnTail (reserved words)
 
 
 def bn_slot_buffer(owner, attr: str, channels: int, device, fresh: bool = True):

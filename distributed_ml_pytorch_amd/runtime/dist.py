@@ -36,8 +36,8 @@ def _env(name, default=None):
 
 
 # Hardware queues per process for every multi-rank GPU process.  Each rank runs
-# several HIP streams at once (compute, the push/pull side stream, the wgrad
-# side stream, one link stream per peer on a PS, and RCCL's internal streams);
+# several HIP streams at once (compute, the push/pull side stream, one link
+# stream per peer on a PS, and RCCL's internal streams);
 # HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and
 # streams that share a queue run back to back (profiles/links_stream_creation_r4.txt,
 # profiles/hw_queue_policy_r5.txt).  The harness refuses values above 32.

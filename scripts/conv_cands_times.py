@@ -80,10 +80,8 @@ def main():
                 nat.conv_wgrad_halo_configs(B, H, W, CI, CO, R, S, st, pd))
             if C._gemm1x1_ok((CO, CI, R, S), st, pd, CI, CO):
                 cands.append(C._GEMM_ROUTE)
-            elif C._im2col_wgrad_ok(x, (CO, CI, R, S), st, pd):
-                cands.append(C._IM2COL_ROUTE)
-            run = lambda c: (C._gemm_route_wgrad(c, dy, x, dw, st, pd)   # noqa: E731
-                             if c in (C._GEMM_ROUTE, C._IM2COL_ROUTE)
+            run = lambda c: (C._gemm1x1_wgrad(dy, x, dw)   # noqa: E731
+                             if c == C._GEMM_ROUTE
                              else nat.conv_wgrad(dy, x, dw, st, pd, c))
         elif k[0] == "fwd":
             cands = C._igemm_candidates(CO) + C._halo_candidates(H, W, CI, R, S, st, pd)
@@ -109,7 +107,7 @@ def main():
             cand[ks] = best[0]
             flag = "  <- candidate"
         route = next((f"  route {c}:{res.get(c, float('nan')):6.1f}" for c in
-                      (C._GEMM_ROUTE, C._IM2COL_ROUTE) if c in cands), "")
+                      (C._GEMM_ROUTE,) if c in cands), "")
         print(f"{str(k):58s} pick {pick}:{pt:6.1f}  best {best[0]}:{best[1]:6.1f}{route}{flag}",
               flush=True)
     for kt, v in TUNER.cache.items():          # GEMM keys first tuned here

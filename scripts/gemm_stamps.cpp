@@ -48,7 +48,7 @@ int main(int argc, char** argv) {
   CK(hipStreamCreate(&st));
   auto run = [&]() {
     dmp::launch_gemm(0, 0, cfg, a, K, b, K, c, N, nullptr, bias, nullptr, nullptr, M, N, K, 1, st,
-                     false, nullptr, nullptr, nullptr, nullptr, nullptr);
+                     false, nullptr, nullptr, nullptr);
   };
   for (int i = 0; i < 5; ++i) run();
   hipEvent_t e0, e1;

@@ -633,12 +633,12 @@ def test_gap_linear_head_fused(B, C, H, N):
 
 @pytest.mark.parametrize("B,C,H,mode", [(64, 64, 32, 2), (32, 64, 32, 3), (64, 256, 8, 3),
                                         (16, 512, 4, 0), (3, 80, 7, 2)])
-def test_bn_bwd_onepass(B, C, H, mode):
-    """One-launch BatchNorm backward (bn.hip bn_bwd_onepass_kernel: reduce ->
-    last-arriver coefficient fold -> apply on the same rows) at ResNet-18 sizes,
-    ReLU mask from x (mode 2), from the 1-bit mask (mode 3) or none, vs fp32; the
-    slot buffer's hand-off words are re-armed (zero) after every call and the
-    bounded poll never gave up; dgamma / dbeta accumulate across calls."""
+def test_bn_bwd_fold_direct(B, C, H, mode):
+    """Folded BatchNorm backward called directly (bn.hip launch_bn_bwd_fold: the
+    reduce launch, then the apply that folds the finalize) at ResNet-18 sizes, ReLU
+    mask from x (mode 2), from the 1-bit mask (mode 3) or none (mode 0), vs fp32;
+    the slot buffer's reserved tail words stay zero after every call, the forward
+    slots are zeroed, and dgamma / dbeta accumulate across calls."""
     from distributed_ml_pytorch_amd.ops._ext import native
 
     nat = native()
