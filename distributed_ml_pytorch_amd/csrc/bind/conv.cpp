@@ -250,12 +250,18 @@ void stem_wgrad(Tensor dy, Tensor xs, Tensor dw) {
 
 // 3x3/s1/p1, CI <= 3, CO = 64 stems on MFMA (conv_small.hip stem3_*); DMP_STEM3=0
 // keeps the VALU kernels (A/B)
-bool stem3_applies(const ConvGeom& g, int64_t stride, int64_t pad) {
+bool stem3_route(int64_t CI, int64_t R, int64_t S, int64_t CO, int64_t stride, int64_t pad,
+                 int64_t W) {
   static const bool on = [] {
     const char* e = std::getenv("DMP_STEM3");
     return e == nullptr || std::atoi(e) != 0;
   }();
-  return on && dmp::stem3_supported(g.CI, g.R, g.S, g.CO, (int)stride, (int)pad, g.W);
+  return on && std::max({CI, R, S, CO, stride, pad, W}) < (int64_t(1) << 30) &&
+         dmp::stem3_supported((int)CI, (int)R, (int)S, (int)CO, (int)stride, (int)pad, (int)W);
+}
+
+bool stem3_applies(const ConvGeom& g, int64_t stride, int64_t pad) {
+  return stem3_route(g.CI, g.R, g.S, g.CO, stride, pad, g.W);
 }
 
 std::vector<Tensor> conv_small_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad,
@@ -303,6 +309,62 @@ void conv_small_wgrad(Tensor dy, Tensor x, Tensor dw, int64_t stride, int64_t pa
   dmp::launch_conv_small_wgrad(bf16(dy), bf16(x), xbytes, sb, sh, sw, sc, dw.data_ptr<float>(),
                                ws.data_ptr<float>(), g.B, g.H, g.W, g.CI, g.OH, g.OW, g.CO, g.R,
                                g.S, (int)stride, (int)pad, cur_stream());
+}
+
+// The CIFAR stem's BatchNorm + ReLU backward and conv weight gradient in one pass
+// (conv_small.hip stem3_bn_bwd_*).  dy, x0: channels_last bf16 [B, 64, H, W] (x0 =
+// the stem conv's stored output, the BN's input); x: the conv's bf16 input, any
+// dense layout; stats: the BN forward's [4, 64].  dgamma / dbeta (fp32 [64]) and
+// dw (fp32 channels_last [64, CI, 3, 3]) are accumulated; None = frozen.  scratch:
+// the layer's persistent zeroed fp32 buffer (left zeroed); zero_buf: the layer's
+// forward BN slot sums, zeroed here.
+void stem3_bn_bwd(Tensor dy, Tensor x0, Tensor x, Tensor stats, optional<Tensor> gamma,
+                  optional<Tensor> dgamma, optional<Tensor> dbeta, optional<Tensor> dw,
+                  Tensor scratch, optional<Tensor> zero_buf, int64_t blocks) {
+  check_nhwc_bf16(dy, "dy");
+  check_nhwc_bf16(x0, "x0");
+  TORCH_CHECK(dy.dim() == 4 && x0.dim() == 4, "stem3_bn_bwd: 4-D dy / x0 expected");
+  same_shape(dy, x0, "stem3_bn_bwd: dy / x0");
+  TORCH_CHECK(x.dim() == 4 && x.is_cuda() && x.scalar_type() == at::kBFloat16 &&
+                  (x.is_contiguous() || x.is_contiguous(kCL)),
+              "stem3_bn_bwd: x must be a dense 4-D bf16 GPU tensor");
+  TORCH_CHECK(dy.device() == x.device() && x0.device() == x.device() &&
+                  stats.device() == x.device() && scratch.device() == x.device(),
+              "stem3_bn_bwd: tensors on different devices");
+  const int64_t B = x.size(0), CI = x.size(1), H = x.size(2), W = x.size(3), C = dy.size(1);
+  TORCH_CHECK(dy.size(0) == B && dy.size(2) == H && dy.size(3) == W,
+              "stem3_bn_bwd: dy / x shape mismatch");
+  TORCH_CHECK(CI >= 1 && CI <= 3 && dmp::stem3_supported((int)CI, 3, 3, (int)C, 1, 1, (int)W),
+              "stem3_bn_bwd: needs a 3x3/s1/p1 stem with CI <= 3, CO = 64 and W % 8 == 0");
+  // 32-bit element offsets into dy | x0 and byte offsets into x
+  TORCH_CHECK(B > 0 && H > 0 && dmp::guard::small_conv_ok(B, H, W, 2 * C, x.numel()),
+              "stem3_bn_bwd: tensor too large for 32-bit indexing");
+  check_vec(stats, at::kFloat, 4 * C, "stem3_bn_bwd: stats [4, C]");
+  check_vecs({&gamma, &dgamma, &dbeta}, at::kFloat, C, "stem3_bn_bwd: gamma / dgamma / dbeta");
+  if (has(dw)) {
+    check_weight_cl(*dw, at::kFloat, "stem3_bn_bwd: dw");
+    TORCH_CHECK(dw->size(0) == C && dw->size(1) == CI && dw->size(2) == 3 && dw->size(3) == 3 &&
+                    dw->device() == x.device(),
+                "stem3_bn_bwd: dw must be [64, CI, 3, 3]");
+  }
+  TORCH_CHECK(scratch.is_cuda() && scratch.scalar_type() == at::kFloat &&
+                  scratch.is_contiguous() &&
+                  scratch.numel() >= dmp::stem3_bn_bwd_scratch_floats(),
+              "stem3_bn_bwd: scratch must be a contiguous fp32 GPU tensor of at least ",
+              dmp::stem3_bn_bwd_scratch_floats(), " elements");
+  float* zb = nullptr;
+  if (has(zero_buf)) {
+    zb = bn_slots(zero_buf, C, x.options()).data_ptr<float>();
+    TORCH_CHECK(zero_buf->device() == x.device(), "stem3_bn_bwd: zero_buf on another device");
+  }
+  TORCH_CHECK(blocks >= 0 && blocks <= (1 << 20), "stem3_bn_bwd: bad block target");
+  TORCH_CHECK(dmp::stem3_bn_bwd_steps(B * H * W, (int)blocks) > 0, "stem3_bn_bwd: bad grid");
+  dmp::launch_stem3_bn_bwd(bf16(dy), bf16(x0), bf16(x), (int)(2 * x.numel()), (int)x.stride(0),
+                           (int)x.stride(2), (int)x.stride(3), (int)x.stride(1),
+                           stats.data_ptr<float>(), ptr_or_null<float>(gamma),
+                           ptr_or_null<float>(dgamma), ptr_or_null<float>(dbeta),
+                           ptr_or_null<float>(dw), scratch.data_ptr<float>(), zb, (int)B, (int)H,
+                           (int)W, (int)CI, (int)blocks, cur_stream());
 }
 
 // ----------------------------------------------------------------- im2col
@@ -417,6 +479,17 @@ void bind_conv(pybind11::module_& m) {
         py::arg("slots") = py::none());
   m.def("conv_small_wgrad", &conv_small_wgrad, "few-input-channel conv weight gradient (fp32 +=)",
         py::arg("dy"), py::arg("x"), py::arg("dw"), py::arg("stride"), py::arg("pad"));
+  m.def("stem3_route", &stem3_route,
+        "conv_small_fwd / conv_small_wgrad run the MFMA stem kernels for this geometry",
+        py::arg("CI"), py::arg("R"), py::arg("S"), py::arg("CO"), py::arg("stride"),
+        py::arg("pad"), py::arg("W"));
+  m.def("stem3_bn_bwd_scratch_floats", [] { return (int64_t)dmp::stem3_bn_bwd_scratch_floats(); },
+        "fp32 elements of stem3_bn_bwd's persistent scratch");
+  m.def("stem3_bn_bwd", &stem3_bn_bwd,
+        "CIFAR stem: BN + ReLU backward and conv weight gradient in one pass (all +=)",
+        py::arg("dy"), py::arg("x0"), py::arg("x"), py::arg("stats"), py::arg("gamma"),
+        py::arg("dgamma"), py::arg("dbeta"), py::arg("dw"), py::arg("scratch"),
+        py::arg("zero_buf") = py::none(), py::arg("blocks") = 0);
   m.def("im2col", &im2col, "NHWC patch rows [B*OH*OW, Kp], k = (r, s, ci), zero-padded",
         py::arg("x"), py::arg("R"), py::arg("S"), py::arg("stride"), py::arg("pad"), py::arg("Kp"));
   m.def("col2im", &col2im, "gather-form inverse of im2col -> channels_last dX", py::arg("dcols"),

@@ -34,10 +34,6 @@ __device__ __forceinline__ void store8(u16* p, const float v[8]) {
 __device__ __forceinline__ bf16x8 bn_ldv(const u16* p) { return *reinterpret_cast<const bf16x8*>(p); }
 __device__ __forceinline__ void bn_stv(u16* p, const bf16x8& r) { *reinterpret_cast<bf16x8*>(p) = r; }
 
-// Pre-activation of the forward apply, shared by the forward and the backward's
-// ReLU-mask recomputation so both round identically (explicit fma).
-__device__ __forceinline__ float bn_pre(float x, float sc, float sh) { return __fmaf_rn(x, sc, sh); }
-
 // ReLU mask source of the backward: 0 = no ReLU, 1 = from the saved output y
 // (BN + residual + ReLU: the mask depends on the residual), 2 = recomputed from
 // x and the folded scale/shift in stats (no residual): one tensor read fewer in

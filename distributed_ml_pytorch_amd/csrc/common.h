@@ -52,6 +52,11 @@ __device__ __forceinline__ u16 f2bf(float f) {
   return __builtin_bit_cast(u16, static_cast<__bf16>(f));
 }
 
+// Pre-activation of the BatchNorm forward apply, shared by the forward and every
+// backward that recomputes the ReLU mask (bn.hip, conv_small.hip) so all of them
+// round identically (explicit fma).
+__device__ __forceinline__ float bn_pre(float x, float sc, float sh) { return __fmaf_rn(x, sc, sh); }
+
 // tanh(u) = 1 - 2 / (1 + e^{2u}): one v_exp_f32 + one v_rcp_f32 instead of
 // the ~30-instruction libm tanhf (the GELU pass was VALU-bound with it).
 __device__ __forceinline__ float fast_tanh(float u) {

@@ -676,6 +676,294 @@ __global__ void __launch_bounds__(256) stem3_wgrad_kernel(Stem3Args a) {
   }
 }
 
+// ------------------------------------------------------------------------------
+// Stem backward in one pass: BatchNorm(+ReLU) backward and the conv's weight
+// gradient together.  The stem's input is data, so the BN's dx exists only for
+// the weight gradient to read back, and it is affine per channel:
+//   dx = k1 dz + Cc x0 + Bc,   dz = dy [y > 0]   (k1, Cc, Bc: bn.hip fold_bwd_coefs)
+//   dW[co][k] = sum_p dx[p][co] patch[p][k] = k1 G1[co][k] + Cc G2[co][k] + Bc G3[k]
+//   G1 = sum_p dz patch,  G2 = sum_p x0 patch,  G3 = sum_p patch
+// G1, G2, G3 and the BN sums S1 = sum dz, S2 = sum dz xhat come from ONE pass over
+// dy and x0 (the conv's stored output); the coefficients, which need S1 and S2
+// complete, are applied afterwards to 64 x K numbers (stem3_bn_bwd_finalize_kernel,
+// one block).  dx is never written, x0 and dy are read once instead of twice, and
+// the bf16 rounding of dx is gone.
+//
+// The pass is stem3_wgrad_kernel with a double-width LDS image: toff<128> spreads
+// a row over all 128 columns already, so dz takes columns 0..63 and x0 columns
+// 64..127 of the same 8 KiB per wave, and the 8 extra MFMAs for G2 reuse the
+// gathered patch fragments.  A lane's four 16-B chunks per step always cover the
+// same 8 channels (lane & 7), so the mask parameters and S1 / S2 live in
+// registers.  Block end: the four waves' tiles are summed in LDS (over the image
+// storage) and flushed with one fp32 atomic per element into the layer's
+// persistent scratch, laid out as below; the finalize kernel re-zeroes it.
+constexpr int kS3KP = 32;                         // K padded to the MFMA k-step
+constexpr int kS3G1 = 0;                          // [64][kS3KP]
+constexpr int kS3G2 = kS3G1 + 64 * kS3KP;         // [64][kS3KP]
+constexpr int kS3G3 = kS3G2 + 64 * kS3KP;         // [kS3KP]
+constexpr int kS3S1 = kS3G3 + kS3KP;              // [64]
+constexpr int kS3S2 = kS3S1 + 64;                 // [64]
+constexpr int kS3Scratch = kS3S2 + 64;
+
+struct Stem3BnArgs {
+  const u16* x;       // the conv's input image (element strides below)
+  const u16* x0;      // [P][64] the conv's stored output = the BN's input
+  const u16* dy;      // [P][64] gradient of the BN + ReLU output
+  const float* stats; // [4][64] mean | invstd | scale | shift of the forward
+  float* scratch;     // [kS3Scratch] (+=)
+  int sb, sh, sw, sc, xbytes;
+  int H, W, CI, K;
+  long long P;
+  int groups;         // 128-pixel steps per block
+};
+
+__global__ void __launch_bounds__(256) stem3_bn_bwd_kernel(Stem3BnArgs a) {
+  // per wave [32 px][dz 64 | x0 64] transposed-read image; afterwards the same
+  // storage holds the block's G1 / G2 / G3 tiles
+  __shared__ __attribute__((aligned(16))) u16 img[4][32 * 128];
+  __shared__ float red[4][2][64];
+  __shared__ __attribute__((aligned(16))) float prm[3][64];   // mean | scale | shift
+  static_assert(sizeof(img) >= (2 * 64 * 33 + kS3KP) * sizeof(float), "tiles reuse the image");
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int kg = lane >> 4, col = lane & 15;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, a.xbytes, 0x00020000);
+  int tdr[2], tds[2], tci[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int k = 16 * t + col;
+    tdr[t] = k < a.K ? (k / a.CI) / 3 - 1 : 9;
+    tds[t] = (k / a.CI) % 3 - 1;
+    tci[t] = k % a.CI;
+  }
+  // this lane's 8 channels of every chunk it loads.  The mask parameters are read
+  // from LDS four channels at a time inside the loop: held in registers for the
+  // whole kernel (24 of them) they cost a wave per SIMD
+  const int c0 = (lane & 7) * 8;
+  if (tid < 192) prm[tid >> 6][tid & 63] = a.stats[(tid < 64 ? 0 : (tid >> 6) + 1) * 64 + (tid & 63)];
+  __syncthreads();
+  float s1[8], s2[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) { s1[i] = 0.f; s2[i] = 0.f; }
+  float g3[2] = {0.f, 0.f};
+  f32x4 acc1[4][2], acc2[4][2];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      acc1[j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      acc2[j][t] = acc1[j][t];
+    }
+  u16* im = img[wid];
+  const long long blk0 = (long long)blockIdx.x * a.groups * 128;
+  auto load_step = [&](int st, bf16x8 (&dv)[4], bf16x8 (&xv)[4], bf16x8 (&xf)[2]) {
+    const long long p0 = blk0 + (long long)st * 128 + wid * 32;   // this wave's 32 pixels
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long p = p0 + u * 8 + (lane >> 3);
+      if (p < a.P) {
+        dv[u] = *reinterpret_cast<const bf16x8*>(a.dy + p * 64 + c0);
+        xv[u] = *reinterpret_cast<const bf16x8*>(a.x0 + p * 64 + c0);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { dv[u].v[i] = 0; xv[u].v[i] = 0; }
+      }
+    }
+    // patch fragments: pixels p0 + 8kg + i (one image row: W % 8 == 0), taps 16t + col
+    {
+      const long long pb = p0 + 8 * kg;
+      const bool pv = pb < a.P;
+      const int p32 = pv ? (int)pb : 0;
+      const int ow0 = p32 % a.W, t0 = p32 / a.W;
+      const int oh = t0 % a.H, b = t0 / a.H;
+      const int boff = b * a.sb;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int ih = oh + tdr[t];
+        const bool rok = pv && (unsigned)ih < (unsigned)a.H;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int iw = ow0 + i + tds[t];
+          const bool ok = rok && (unsigned)iw < (unsigned)a.W && pb + i < a.P;
+          const int off = ok ? 2 * (boff + ih * a.sh + iw * a.sw + tci[t] * a.sc) : 0x7ffffff0;
+          xf[t].v[i] = __builtin_bit_cast(u16, __builtin_amdgcn_raw_buffer_load_b16(rs, off, 0, 0));
+        }
+      }
+    }
+  };
+  // dy / x0 chunks and patch taps of one step: loaded for step st + 1 as soon as
+  // step st's are staged to LDS, so the loads fly during the tr reads and MFMAs (a
+  // second register set for a full-step prefetch costs a wave per SIMD)
+  bf16x8 dv[4], xv[4], xn[2];
+  load_step(0, dv, xv, xn);
+  for (int st = 0; st < a.groups; ++st) {
+    int pofs = c0;
+    asm volatile("" : "+v"(pofs));        // keeps the parameter reads inside the loop
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) {      // four channels' parameters at a time
+      const float4 m4 = *reinterpret_cast<const float4*>(&prm[0][pofs + 4 * hf]);
+      const float4 c4 = *reinterpret_cast<const float4*>(&prm[1][pofs + 4 * hf]);
+      const float4 h4 = *reinterpret_cast<const float4*>(&prm[2][pofs + 4 * hf]);
+      const float mean[4] = {m4.x, m4.y, m4.z, m4.w}, msc[4] = {c4.x, c4.y, c4.z, c4.w},
+                  msh[4] = {h4.x, h4.y, h4.z, h4.w};
+#pragma unroll
+      for (int ii = 0; ii < 4; ++ii) {
+        const int i = 4 * hf + ii;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const float xx = bf2f(xv[u].v[i]);
+          // exactly bn.hip relu_mask_from_x: the y > 0 test on the stored bf16 y
+          const float yy = fmaxf(bn_pre(xx, msc[ii], msh[ii]), 0.f);
+          const bool keep = bf2f(f2bf(yy)) > 0.f;
+          dv[u].v[i] = keep ? dv[u].v[i] : (u16)0;   // dy -> dz in place
+          const float g = bf2f(dv[u].v[i]);
+          s1[i] += g;
+          s2[i] += g * (xx - mean[ii]);
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int row = u * 8 + (lane >> 3);
+      *reinterpret_cast<bf16x8*>(im + toff<128>(row, c0)) = dv[u];          // 8 cols stay in one granule
+      *reinterpret_cast<bf16x8*>(im + toff<128>(row, 64 + c0)) = xv[u];
+    }
+    bf16x8 xf[2];
+    xf[0] = xn[0];
+    xf[1] = xn[1];
+    if (st + 1 < a.groups) load_step(st + 1, dv, xv, xn);
+    // G3: this lane's patch values are pixels 8kg + i of taps 16t + col
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 8; ++i) g3[t] += bf2f(xf[t].v[i]);
+    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): this wave's LDS image writes landed
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int h = 0; h < 2; ++h)           // h = 0: dz -> G1, h = 1: x0 -> G2
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int li = lane & 15, qq = li >> 2, pp = li & 3;
+        const int row = 8 * kg + qq, cc = 64 * h + 16 * j + 4 * pp;
+        const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (__attribute__((address_space(3))) s16x4_t*)(im + toff<128>(row, cc)));
+        const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (__attribute__((address_space(3))) s16x4_t*)(im + toff<128>(row + 4, cc)));
+        const bf16x8 af = __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+        if (h == 0) {
+          acc1[j][0] = mfma16(af, xf[0], acc1[j][0]);
+          acc1[j][1] = mfma16(af, xf[1], acc1[j][1]);
+        } else {
+          acc2[j][0] = mfma16(af, xf[0], acc2[j][0]);
+          acc2[j][1] = mfma16(af, xf[1], acc2[j][1]);
+        }
+      }
+    __builtin_amdgcn_wave_barrier();
+  }
+  // S1 / S2: fold the 8 lanes (lane >> 3) that share a channel octet, then the waves
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    s2[i] *= a.stats[64 + c0 + i];        // xhat = (x0 - mean) * invstd
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1) {
+      s1[i] += __shfl_xor(s1[i], o, 64);
+      s2[i] += __shfl_xor(s2[i], o, 64);
+    }
+  }
+  if (lane < 8) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      red[wid][0][c0 + i] = s1[i];
+      red[wid][1][c0 + i] = s2[i];
+    }
+  }
+  // G3: fold the four pixel octets kg
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    g3[t] += __shfl_xor(g3[t], 16, 64);
+    g3[t] += __shfl_xor(g3[t], 32, 64);
+  }
+  __syncthreads();                        // every wave is done with its image
+  float (*t1)[33] = reinterpret_cast<float (*)[33]>(&img[0][0]);
+  float (*t2)[33] = t1 + 64;
+  float* t3 = &t2[64][0];
+  // sum the 4 waves' tiles.  D: lane holds rows co = 16j + 4kg + r, column k = 16t + col
+  for (int w = 0; w < 4; ++w) {
+    if (wid == w) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            float& d1 = t1[16 * j + 4 * kg + r][16 * t + col];
+            float& d2 = t2[16 * j + 4 * kg + r][16 * t + col];
+            d1 = (w == 0 ? 0.f : d1) + acc1[j][t][r];
+            d2 = (w == 0 ? 0.f : d2) + acc2[j][t][r];
+          }
+      if (kg == 0) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) t3[16 * t + col] = (w == 0 ? 0.f : t3[16 * t + col]) + g3[t];
+      }
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < 64 * kS3KP; e += 256) {
+    const int co = e / kS3KP, k = e % kS3KP;
+    if (k < a.K) {
+      atomicAdd(a.scratch + kS3G1 + e, t1[co][k]);
+      atomicAdd(a.scratch + kS3G2 + e, t2[co][k]);
+    }
+  }
+  if (tid < a.K) atomicAdd(a.scratch + kS3G3 + tid, t3[tid]);
+  if (tid >= 64 && tid < 192) {
+    const int h = (tid - 64) >> 6, c = tid & 63;
+    atomicAdd(a.scratch + (h == 0 ? kS3S1 : kS3S2) + c,
+              red[0][h][c] + red[1][h][c] + red[2][h][c] + red[3][h][c]);
+  }
+}
+
+// One block, launched right after stem3_bn_bwd_kernel (the kernel boundary makes
+// its atomics visible): the coefficients with fold_bwd_coefs' arithmetic, dgamma /
+// dbeta, dW += k1 G1 + Cc G2 + Bc G3; re-zeroes the scratch for the next call and
+// the layer's forward slot sums (as the backward apply's slice_zero does).  A null
+// dw / dgamma / dbeta is a frozen parameter: skipped.
+__global__ void __launch_bounds__(1024) stem3_bn_bwd_finalize_kernel(
+    float* __restrict__ scratch, const float* __restrict__ gamma, const float* __restrict__ stats,
+    float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dw,
+    float* __restrict__ zero_buf, long long M, int K) {
+  __shared__ float lk1[64], lbc[64], lcc[64], lg3[kS3KP];
+  const int t = threadIdx.x;
+  if (t < 64) {
+    const float db = scratch[kS3S1 + t];   // sum dz
+    const float dg = scratch[kS3S2 + t];   // sum dz * xhat
+    if (dgamma) dgamma[t] += dg;
+    if (dbeta) dbeta[t] += db;
+    const float mean = stats[t], inv = stats[64 + t];
+    const float k1 = (gamma ? gamma[t] : 1.f) * inv;
+    const float invM = 1.f / (float)M;
+    const float Cc = -k1 * inv * dg * invM;
+    lk1[t] = k1;
+    lbc[t] = -k1 * db * invM - Cc * mean;
+    lcc[t] = Cc;
+  } else if (t < 64 + kS3KP) {
+    lg3[t - 64] = scratch[kS3G3 + t - 64];
+  }
+  __syncthreads();
+  // (1024 threads, every load of the two trips issued up front: the kernel is one
+  // dependent chain of latencies on the step's critical path)
+#pragma unroll
+  for (int e = t; e < 64 * kS3KP; e += 1024) {
+    const int co = e / kS3KP, k = e % kS3KP;
+    const float g1 = scratch[kS3G1 + e], g2 = scratch[kS3G2 + e];
+    if (dw != nullptr && k < K) dw[co * K + k] += lk1[co] * g1 + lcc[co] * g2 + lbc[co] * lg3[k];
+    scratch[kS3G1 + e] = 0.f;
+    scratch[kS3G2 + e] = 0.f;
+  }
+  if (t < kS3Scratch - kS3G3) scratch[kS3G3 + t] = 0.f;   // G3, S1, S2 (read before the barrier)
+  if (zero_buf != nullptr)
+    for (int i = t; i < 2 * kBnSlots * 64; i += 1024) zero_buf[i] = 0.f;
+}
+
 bool stem3_supported(int CI, int R, int S, int CO, int stride, int pad, int W) {
   return CI >= 1 && CI <= 3 && R == 3 && S == 3 && CO == 64 && stride == 1 && pad == 1 &&
          W % 8 == 0;
@@ -723,6 +1011,41 @@ void launch_stem3_wgrad(const u16* dy, const u16* x, int xbytes, int sb, int sh,
   a.groups = (int)per;
   const long long nb = (steps + per - 1) / per;
   hipLaunchKernelGGL(stem3_wgrad_kernel, dim3((unsigned)nb), dim3(256), 0, s, a);
+}
+
+int stem3_bn_bwd_scratch_floats() { return kS3Scratch; }
+
+// 128-pixel steps per block of stem3_bn_bwd_kernel: launch_stem3_wgrad's rule
+// (about `target` blocks, default 512; >= 4 steps per block so the per-block
+// atomic flush stays a small part of the block's work)
+int stem3_bn_bwd_steps(long long P, int target) {
+  if (P <= 0 || P >= (1LL << 31)) return 0;   // pixels are indexed in 32 bits
+  const long long tg = target > 0 ? target : 512;
+  const long long steps = (P + 127) / 128;
+  long long per = (steps + tg - 1) / tg;
+  if (per < 4) per = 4;
+  return per > 0x7fffffff ? 0 : (int)per;
+}
+
+long long stem3_bn_bwd_blocks(long long P, int target) {
+  const int per = stem3_bn_bwd_steps(P, target);
+  return per > 0 ? ((P + 127) / 128 + per - 1) / per : 0;
+}
+
+void launch_stem3_bn_bwd(const u16* dy, const u16* x0, const u16* x, int xbytes, int sb, int sh,
+                         int sw, int sc, const float* stats, const float* gamma, float* dgamma,
+                         float* dbeta, float* dw, float* scratch, float* zero_buf, int B, int H,
+                         int W, int CI, int blocks, hipStream_t s) {
+  Stem3BnArgs a{};
+  a.x = x; a.x0 = x0; a.dy = dy; a.stats = stats; a.scratch = scratch;
+  a.sb = sb; a.sh = sh; a.sw = sw; a.sc = sc; a.xbytes = xbytes;
+  a.H = H; a.W = W; a.CI = CI; a.K = 9 * CI;
+  a.P = (long long)B * H * W;
+  a.groups = stem3_bn_bwd_steps(a.P, blocks);
+  const long long nb = stem3_bn_bwd_blocks(a.P, blocks);
+  hipLaunchKernelGGL(stem3_bn_bwd_kernel, dim3((unsigned)nb), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(stem3_bn_bwd_finalize_kernel, dim3(1), dim3(1024), 0, s, scratch, gamma, stats,
+                     dgamma, dbeta, dw, zero_buf, a.P, a.K);
 }
 
 }  // namespace dmp

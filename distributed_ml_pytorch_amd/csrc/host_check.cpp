@@ -122,7 +122,18 @@ void check_conv(const Conv& c) {
     }
   } else if (c.CI < 64) {
     // stems: 3x3 MFMA stem, VALU small conv, ImageNet s2d stem
-    dmp::stem3_supported(c.CI, c.R, c.S, c.CO, c.stride, c.pad, c.W);
+    if (dmp::stem3_supported(c.CI, c.R, c.S, c.CO, c.stride, c.pad, c.W) &&
+        dmp::guard::small_conv_ok(c.B, OH, OW, 2 * c.CO, (long long)c.B * c.CI * c.H * c.W)) {
+      // one-pass stem backward: the grid covers every 128-pixel step, >= 4 per block
+      const long long P = (long long)c.B * OH * OW;
+      for (int target : {0, 1, 64, 512, 4096, 1 << 20}) {
+        const int per = dmp::stem3_bn_bwd_steps(P, target);
+        const long long nb = dmp::stem3_bn_bwd_blocks(P, target);
+        EXPECT(per >= 4 && nb > 0 && nb * per * 128 >= P && (nb - 1) * per * 128 < P,
+               "stem3 bn bwd grid: P %lld target %d -> %lld blocks of %d steps", P, target, nb,
+               per);
+      }
+    }
     if (c.R * c.S * c.CI <= dmp::conv_small_max_k() &&
         dmp::guard::small_conv_ok(c.B, OH, OW, c.CO, (long long)c.B * c.CI * c.H * c.W)) {
       const long long P = (long long)c.B * OH * OW;
@@ -171,6 +182,14 @@ void check_guards() {
   EXPECT(small_conv_ok(512, 32, 32, 64, 512LL * 3 * 32 * 32), "small conv bs512");
   EXPECT(!small_conv_ok(int64_t(1) << 16, 32, 32, 1 << 10, 3), "small conv output over 2^31");
   EXPECT(!small_conv_ok(1, 32, 32, 64, int64_t(1) << 30), "small conv input over 2 GiB");
+  EXPECT(dmp::stem3_bn_bwd_steps(0, 0) == 0 && dmp::stem3_bn_bwd_steps(-5, 512) == 0 &&
+             dmp::stem3_bn_bwd_steps(INT64_MAX, 512) == 0 && dmp::stem3_bn_bwd_blocks(INT64_MAX, 0) == 0,
+         "stem3 bn bwd grid must reject empty / oversize pixel counts, not wrap");
+  EXPECT(dmp::stem3_bn_bwd_steps(8, 0) == 4 && dmp::stem3_bn_bwd_blocks(8, 0) == 1 &&
+             dmp::stem3_bn_bwd_steps(512LL * 1024, 0) == 8 &&
+             dmp::stem3_bn_bwd_blocks(512LL * 1024, 0) == 512 &&
+             dmp::stem3_bn_bwd_blocks(1152, 0) == 3 && dmp::stem3_bn_bwd_scratch_floats() > 0,
+         "stem3 bn bwd grid rule");
   EXPECT(stem_batch_ok(128, 224, 224) && !stem_batch_ok(int64_t(1) << 20, 224, 224), "stem");
   EXPECT(rows_bytes_ok(2, 12608, 3072) && !rows_bytes_ok(4, int64_t(1) << 20, 1 << 10),
          "rows 2 GiB");

@@ -216,6 +216,19 @@ void launch_stem3_fwd(const uint16_t* x, int xbytes, int sb, int sh, int sw, int
                       hipStream_t s);
 void launch_stem3_wgrad(const uint16_t* dy, const uint16_t* x, int xbytes, int sb, int sh, int sw,
                         int sc, float* dw, int B, int H, int W, int CI, hipStream_t s);
+// The stem's BatchNorm(+ReLU) backward and weight gradient in one pass over dy and
+// x0 (the conv's stored output), then a one-block finalize: dgamma / dbeta / dw
+// (fp32 [64][9*CI]) are accumulated (null = frozen, skipped), `scratch`
+// (stem3_bn_bwd_scratch_floats() zeroed floats, persistent per layer) is left
+// zeroed again, zero_buf (the layer's forward BN slot sums, or null) is zeroed.
+// blocks: target block count of the pass (<= 0: the default rule).
+int stem3_bn_bwd_scratch_floats();
+int stem3_bn_bwd_steps(long long P, int target);        // 128-pixel steps per block (0: bad P)
+long long stem3_bn_bwd_blocks(long long P, int target);
+void launch_stem3_bn_bwd(const uint16_t* dy, const uint16_t* x0, const uint16_t* x, int xbytes,
+                         int sb, int sh, int sw, int sc, const float* stats, const float* gamma,
+                         float* dgamma, float* dbeta, float* dw, float* scratch, float* zero_buf,
+                         int B, int H, int W, int CI, int blocks, hipStream_t s);
 // conv_small.hip: few-input-channel (stem) convolutions, VALU
 int conv_small_max_k();
 long long conv_small_fwd_blocks(long long P);

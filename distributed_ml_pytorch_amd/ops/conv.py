@@ -430,16 +430,62 @@ def _wgrad_only(master, launch):
     return sink.done()
 
 
+# ------------------------------------------------ stem backward hand-off
+# The CIFAR stem (3x3/s1/p1, CI <= 3 -> 64 channels) feeds a BatchNorm + ReLU,
+# and its input is data: the BN's dx would be written only for the stem's weight
+# gradient to read back.  On the MFMA stem route ``conv2d`` tags the conv output
+# with a ``StemHandoff``; the BatchNorm's backward (``ops.functional._BNAct``),
+# finding it on its input, runs the one-pass kernels (csrc/conv_small.hip
+# stem3_bn_bwd_*: dgamma, dbeta AND the conv's dW, no dx), parks the weight's
+# ``GradSink`` in the hand-off and returns its own incoming gradient marked with
+# it; ``_SmallConv.backward`` then launches nothing and closes the sink.
+class StemHandoff:
+    def __init__(self, x, master, scratch):
+        self.x, self.master, self.scratch = x, master, scratch
+        self.sink = None      # set by the BatchNorm backward that did the weight gradient
+        self.grad = None      # (the gradient tensor it returned, its version)
+
+    def give(self, dy, sink):
+        self.sink, self.grad = sink, (dy, dy._version)
+        return dy
+
+    def take(self, dy):
+        """The parked sink if the BatchNorm backward did the weight gradient (then
+        ``dy`` must be the very tensor it returned), else None."""
+        sink, grad = self.sink, self.grad
+        self.sink = self.grad = None
+        if grad is None:
+            return None
+        if dy is not grad[0] or dy._version != grad[1]:
+            # the weight gradient is already accumulated from the BatchNorm's own
+            # incoming gradient: anything added or changed on the way is lost
+            raise RuntimeError("stem conv: its output gradient was modified after the fused "
+                               "BatchNorm backward computed the weight gradient from it")
+        return sink
+
+
+def stem_bwd_scratch(owner, device):
+    """Persistent zeroed scratch of the one-pass stem backward on ``owner`` (the
+    kernels leave it zeroed)."""
+    n = native().stem3_bn_bwd_scratch_floats()
+    buf = getattr(owner, "_dmp_stem_scratch", None)
+    if buf is None or buf.device != device or buf.numel() != n:
+        buf = torch.zeros(n, dtype=torch.float32, device=device)
+        object.__setattr__(owner, "_dmp_stem_scratch", buf)
+    return buf
+
+
 class _SmallConv(Function):
     """Stem conv: forward + weight gradient only (the input is data)."""
 
     @staticmethod
-    def forward(ctx, x, w16, master, stride, pad, want_stats, slots=None):
+    def forward(ctx, x, w16, master, stride, pad, want_stats, slots=None, handoff=None):
         ctx.set_materialize_grads(False)
         y, part, _ = native().conv_small_fwd(x, w16, stride, pad, want_stats, slots)
         ctx.save_for_backward(x)
         ctx.master = master
         ctx.geom = (stride, pad)
+        ctx.handoff = handoff
         if want_stats:
             ctx.mark_non_differentiable(part)
             return y, part
@@ -448,10 +494,13 @@ class _SmallConv(Function):
     @staticmethod
     def backward(ctx, dy, _dpart):
         if dy is None:
-            return None, None, None, None, None, None, None
+            return None, None, None, None, None, None, None, None
+        sink = ctx.handoff.take(dy) if ctx.handoff is not None else None
+        if sink is not None:      # the BatchNorm backward did the weight gradient
+            return None, None, sink.done(), None, None, None, None, None
         (x,) = ctx.saved_tensors
         gw = _wgrad_only(ctx.master, lambda g: native().conv_small_wgrad(dy, x, g, *ctx.geom))
-        return None, None, gw, None, None, None, None
+        return None, None, gw, None, None, None, None, None
 
 
 class _StemConv(Function):
@@ -544,8 +593,11 @@ def im2col_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
 
 
 def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=False,
-           slots=None, alias=False, relu=False):
+           slots=None, alias=False, relu=False, stem_scratch=None):
     """Returns ``y`` (with BN slot sums attached as ``y._dmp_bn_part`` when ``want_stats``).
+
+    ``stem_scratch``: the layer's ``stem_bwd_scratch`` (used on the MFMA stem route
+    with ``want_stats``, see ``StemHandoff``); a fresh one when None.
 
     ``slots``: the layer's persistent ``[2][64][CO]`` fp32 BN slot buffer (zeroed;
     the consuming BatchNorm's finalize re-zeroes it); a fresh one when None.
@@ -574,10 +626,20 @@ def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=F
         if master is not None and b is None and not relu and _STEM != "im2col" and \
                 small_conv_supported(x, master, stride, padding, dilation, groups):
             w16 = _shadow16(master)
-            y, part = _SmallConv.apply(x, w16, master, _pair(stride)[0], _pair(padding)[0],
-                                       bool(want_stats), slots if want_stats else None)
+            st, pd = _pair(stride)[0], _pair(padding)[0]
+            co, ci, r, s = master.shape
+            handoff = None
+            if want_stats and native().stem3_route(ci, r, s, co, st, pd, x.shape[3]):
+                if stem_scratch is None:      # no owning layer: a one-off zeroed scratch
+                    stem_scratch = torch.zeros(native().stem3_bn_bwd_scratch_floats(),
+                                               dtype=torch.float32, device=x.device)
+                handoff = StemHandoff(x, master, stem_scratch)
+            y, part = _SmallConv.apply(x, w16, master, st, pd, bool(want_stats),
+                                       slots if want_stats else None, handoff)
             if part is not None:
                 y._dmp_bn_part = part
+            if handoff is not None:
+                y._dmp_stem = handoff
             return (y, x) if alias else y
         if master is not None and b is None and not relu and \
                 stem_conv_supported(x, master, stride, padding, dilation, groups):

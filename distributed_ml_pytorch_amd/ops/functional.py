@@ -258,7 +258,7 @@ def _fresh_slots(buf, C, device):
 class _BNAct(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, training, momentum, eps,
-                relu, part=None, slots=None):
+                relu, part=None, slots=None, stem=None):
         res_handoff = residual is not None and bool(
             getattr(residual, "_dmp_residual_only", False)
             and (getattr(residual, "_dmp_bn_out", False) or getattr(residual, "_dmp_conv_alias", False)))
@@ -307,6 +307,10 @@ class _BNAct(Function):
                              and x.dim() == 4)
         y._dmp_bn_out = True
         ctx.gamma, ctx.beta = gamma, beta
+        # one-pass stem backward: folded training BN + ReLU, no residual, 4-D input
+        # straight from the MFMA stem conv
+        ctx.stem = stem if (ctx.fold and relu and residual is None and x.dim() == 4
+                            and ctx.fpart is part and part is not None) else None
         # the backward re-derives the ReLU mask from x and the folded scale/shift
         # unless a residual entered the forward (then the bit mask, or y)
         ctx.save_for_backward(x, y if (relu and residual is not None and mask is None) else None,
@@ -325,6 +329,20 @@ class _BNAct(Function):
         sg = GradSink(gamma, ctx.needs_input_grad[1], dtype=None)
         sb = GradSink(beta, ctx.needs_input_grad[2], dtype=None)
         dg, db = sg.buf, sb.buf
+        stem = ctx.stem
+        if stem is not None and in_mask is None:
+            # dgamma, dbeta and the stem conv's weight gradient from one pass over
+            # dy and x; no dx (the stem's input is data).  The conv's backward finds
+            # its weight sink in the hand-off and launches nothing.
+            dy = dy.contiguous(memory_format=CL)
+            sw = GradSink(stem.master, stem.master is not None and stem.master.requires_grad,
+                          "cl")
+            native().stem3_bn_bwd(dy, x, stem.x, stats, gamma, dg, db, sw.buf, stem.scratch,
+                                  ctx.fpart)
+            mark_slots(ctx.fpart, False)       # zeroed by the finalize kernel
+            ctx.fpart = None
+            return (stem.give(dy, sw), sg.done(), sb.done(), None, None, None, None, None, None,
+                    None, None, None, None)
         if ctx.fold:
             if x.dim() == 4:
                 dy = dy.contiguous(memory_format=CL)
@@ -353,7 +371,7 @@ class _BNAct(Function):
             dx, dres = native().bn_bwd(x, dy, y, gamma, stats, dg, db, ctx.relu, ctx.has_res,
                                        ctx.bslots, mask)
         return (dx, sg.done(), sb.done(), (dres if ctx.has_res else None), None, None, None, None,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 def batch_norm_act(x, weight, bias, running_mean, running_var, training: bool, momentum: float,
@@ -367,8 +385,12 @@ def batch_norm_act(x, weight, bias, running_mean, running_var, training: bool, m
         if not training and (running_mean is None or running_var is None):
             training = True
         part = getattr(x, "_dmp_bn_part", None) if training else None
+        # the MFMA stem conv's output (ops.conv.StemHandoff): BN + ReLU backward and
+        # the conv's weight gradient run as one pass
+        stem = getattr(x, "_dmp_stem", None) if (training and relu and residual is None
+                                                   and part is not None) else None
         return _BNAct.apply(x, weight, bias, residual, running_mean, running_var, training,
-                            momentum, eps, relu, part, slots)
+                            momentum, eps, relu, part, slots, stem)
     if x.is_cuda and x.dtype == torch.bfloat16:
         raise RuntimeError(
             f"batch_norm_act: unsupported bf16 GPU input (C={x.shape[1]}); "

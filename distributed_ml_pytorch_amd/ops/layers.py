@@ -14,7 +14,7 @@ import torch.nn.functional as F
 from . import functional as DF
 from ._policy import stock_gpu
 from .conv import (bn_slot_buffer, conv2d as _conv2d, im2col_conv_supported,
-                   native_conv_supported, small_conv_supported)
+                   native_conv_supported, small_conv_supported, stem_bwd_scratch)
 from .linear import arena_linear_ok, linear as _arena_linear
 
 
@@ -44,9 +44,11 @@ class Conv2d(nn.Conv2d):
                                          self.dilation, self.groups)):
             want = self.emit_bn_stats and self.training and not relu
             slots = bn_slot_buffer(self, "_dmp_slots", self.out_channels, x.device) if want else None
+            # the one-pass stem backward's persistent scratch (few-input-channel stems)
+            scratch = stem_bwd_scratch(self, x.device) if want and self.in_channels <= 3 else None
             return _conv2d(x, None, self.bias, st, self.padding, self.dilation,
                            self.groups, master=self.weight, want_stats=want, slots=slots,
-                           alias=alias, relu=relu)
+                           alias=alias, relu=relu, stem_scratch=scratch)
         w = DF.compute_weight(self.weight, x.dtype)
         b = DF.compute_weight(self.bias, x.dtype)
         return _conv2d(x, w, b, st, self.padding, self.dilation, self.groups,
