@@ -68,22 +68,24 @@ __global__ void __launch_bounds__(64 * NW) dma_ceiling_kernel(const uint16_t* sr
   if (lds[threadIdx.x * 8] == 0x7fff && sink != nullptr) sink[0] = 1;   // keep the loads live
 }
 
+template <int NW, int INF>
+void launch_dma_ceiling(const void* src, unsigned mask, int blocks, int iters, int* sink,
+                        void* stream) {
+  dmp::allow_max_dynamic_lds<dma_ceiling_kernel<NW, INF>>();
+  hipLaunchKernelGGL((dma_ceiling_kernel<NW, INF>), dim3(blocks), dim3(64 * NW),
+                     (size_t)NW * INF * 1024, static_cast<hipStream_t>(stream),
+                     static_cast<const uint16_t*>(src), mask, iters, sink);
+}
+
 }  // namespace
 
 extern "C" int abl_dma_ceiling(const void* src, unsigned long long window_bytes, int blocks, int nw,
                                int inflight, int iters, int* sink, void* stream) {
   const unsigned mask = (unsigned)(window_bytes - 1);
-  const size_t lds = (size_t)nw * inflight * 1024;
-  auto go = [&](auto kern) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * nw), lds, static_cast<hipStream_t>(stream),
-                       static_cast<const uint16_t*>(src), mask, iters, sink);
-  };
-  if (nw == 4 && inflight == 8) go(dma_ceiling_kernel<4, 8>);
-  else if (nw == 4 && inflight == 16) go(dma_ceiling_kernel<4, 16>);
-  else if (nw == 8 && inflight == 8) go(dma_ceiling_kernel<8, 8>);
-  else if (nw == 8 && inflight == 16) go(dma_ceiling_kernel<8, 16>);
+  if (nw == 4 && inflight == 8) launch_dma_ceiling<4, 8>(src, mask, blocks, iters, sink, stream);
+  else if (nw == 4 && inflight == 16) launch_dma_ceiling<4, 16>(src, mask, blocks, iters, sink, stream);
+  else if (nw == 8 && inflight == 8) launch_dma_ceiling<8, 8>(src, mask, blocks, iters, sink, stream);
+  else if (nw == 8 && inflight == 16) launch_dma_ceiling<8, 16>(src, mask, blocks, iters, sink, stream);
   else return -1;
   return (int)hipGetLastError();
 }

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "bn_slots.h"
+#include "halo_plan.h"
 #include <stdint.h>
 
 namespace dmp {
@@ -96,6 +97,16 @@ inline int stream_grid(long long work_items, int block) {
   if (g < 1) g = 1;
   if (g > 2048) g = 2048;
   return (int)g;
+}
+
+// Let `Kernel` ask for up to kMaxDynamicLds bytes of dynamic LDS; the attribute
+// is set on the first call per kernel instantiation.
+template <auto Kernel>
+inline void allow_max_dynamic_lds() {
+  static const hipError_t once =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel),
+                          hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynamicLds);
+  (void)once;
 }
 
 }  // namespace dmp

@@ -44,6 +44,7 @@
 #ifndef DMP_HALO_STORE_AUX
 #define DMP_HALO_STORE_AUX 2
 #endif
+#include "halo_plan.h"
 #include "launchers.h"
 #include "mfma_prims.h"
 
@@ -454,19 +455,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_igemm_kernel(ConvArgs a) {
 // gradient: the same conv over dY with Wt[ci][r][s][co] and the taps mirrored.
 // NS = 2: two LDS stages (halo + 9 weight tiles each), one barrier per chunk;
 // NS = 1: one stage, more resident blocks per CU.
-// MV: output pixels per tile.  = BM, except for "padded whole-image" tiles
-// (ImageNet ResNet 14x14 / 7x7 maps, where no multiple of 16 is a whole number
-// of images): TB images (MV = TB * H * W < BM) in a BM-row tile whose last
-// BM - MV rows read a valid staged row and are dropped by the epilogue.
-struct HaloGeom {
-  int TH, TB, HROWS, A_INS, MV;
-  // conv_halo_kernel staging: staged row width W2 (W + 2, or W + 4 with PSW),
-  // rows per image block PI ((TH + 2) * W2 [+ pad]), PSW: swizzle keyed on the
-  // pixel-like index (see conv_halo_kernel)
-  int W2, PI, PSW;
-};
-
-constexpr int kHaloAPW = 8;   // max halo DMA instructions per wave per stage
+// The tile plan (HaloGeom, the config table, the tiling rule) is halo_plan.h.
 
 // Epilogue of the halo tiles (forward layout: output row m = pixel m) through
 // frag_epilogue; the LDS at lds_h is free (the caller synchronised after its
@@ -1047,31 +1036,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_dgrad_s2_kernel(ConvArgs a,
 // whatever order loads and stores retire in).  BN partial sums accumulate in
 // registers over all of a block's tiles (one slot reduction per block).
 // FLIP = stride-1 data gradient (dY, Wt, mirrored taps); no residual addend
-// (the host routes addend dgrads to conv_halo_kernel).
-struct HaloPGeom {
-  int TH, TB, HROWS, APW, AINS, ntiles;   // APW: pieces per wave (>= AINS / NW), AINS: exact
-  // DIAGNOSTIC (DMP_HALO64P_XFORM=1, forward only): the cost of applying a
-  // per-channel BatchNorm scale / shift + clamp to the staged input tile in LDS
-  // ("apply-in-consumer"): every wave rewrites its own landed halo pieces,
-  // x -> max(x * xs + xh, xlo), before the tile's barrier.  Run with the
-  // identity (xs 1, xh 0, xlo -inf: outputs unchanged, the work is not
-  // foldable: runtime values) to price the transform against the BN apply
-  // pass it would replace (profiles/bn_consumer_fusion_r3.txt).
-  int xform;
-  float xs, xh, xlo;
-  // 8-wave blocks: waves 4-7 (the SIMD partners of waves 0-3) run each tile as
-  // compute(k) -> epilogue(k) instead of epilogue(k-1) -> compute(k), so one
-  // wave's epilogue VALU and stores overlap its partner's MFMAs instead of both
-  // waves of a SIMD storing at once after the tile barrier (MI355X_MICROARCH.md,
-  // "Two waves per SIMD" item 9: split roles by wave number >= 4)
-  int stagger;
-};
-
-constexpr int kHpAPW = 12;   // max halo DMA pieces per wave per tile
-// 8-wave blocks need at most 8 (BM 256 on 32 x 32 / 64 x 64 maps: 6 / 7): the
-// smaller bound frees 8 VGPRs of slot offsets in the register-capped kernel
-constexpr int hp_apw_max(int nw) { return nw == 8 ? 8 : kHpAPW; }
-
+// (the host routes addend dgrads to conv_halo_kernel).  HaloPGeom: halo_plan.h.
 template <int BM, int NS, int NW, bool FLIP, bool STATS>
 __global__ void __launch_bounds__(64 * NW) conv_halo64p_kernel(ConvArgs a, HaloPGeom hg) {
   constexpr int BK = 64, BN = 64, RPI = 8;
@@ -1536,154 +1501,20 @@ static void dispatch(const ConvArgs& a, int cfg, int classes, hipStream_t s) {
   }
 }
 
-// Halo-tile configurations (BM, BN, BK, WM, WN), cfg ids kHaloBase + i; only for
-// 3x3 / stride 1 / pad 1 and block tiles of whole rows or whole images.
-#define DMP_HALO_CONFIGS(X)   \
-  X(0, 256, 64, 32, 4, 2, 2)  \
-  X(1, 128, 64, 32, 2, 2, 2)  \
-  X(2, 64, 64, 32, 2, 2, 2)   \
-  X(3, 128, 64, 32, 4, 2, 2)  \
-  X(4, 256, 64, 32, 2, 2, 2)  \
-  X(5, 128, 64, 32, 2, 2, 1)  \
-  X(6, 256, 64, 32, 4, 2, 1)  \
-  X(7, 64, 64, 32, 2, 2, 1)   \
-  X(8, 128, 64, 32, 4, 2, 1)   \
-  X(9, 256, 64, 32, 4, 1, 1)   \
-  X(10, 256, 64, 32, 4, 1, 2)  \
-  X(11, 128, 64, 32, 2, 1, 1)  \
-  X(12, 128, 128, 32, 2, 2, 1) \
-  X(13, 256, 128, 32, 4, 2, 1) \
-  X(14, 512, 64, 32, 8, 1, 1)  \
-  X(18, 224, 64, 32, 2, 2, 1)  \
-  X(19, 224, 64, 32, 2, 1, 1)  \
-  X(20, 112, 64, 32, 1, 2, 1)  \
-  X(21, 112, 128, 32, 1, 4, 1) \
-  X(22, 112, 128, 32, 1, 2, 1) \
-  X(23, 448, 64, 32, 4, 2, 1)  \
-  X(24, 224, 64, 32, 2, 2, 2)  \
-  X(25, 112, 128, 32, 1, 4, 2)
-// 18-25: whole-row tiles of 7 x 16 pixels for the ImageNet ResNet widths (56-
-// and 28-pixel rows: 4 / 2 / 8 rows of 56, 4 rows of 28), where none of the
-// power-of-two tiles above is a whole number of rows.  Ids 15-17 are the
-// persistent kernels below (kept: ids are cached by the tuner).
-
-constexpr int kHaloBase = 100, kNumHaloConfigs = 26;   // ids kHaloBase + [0, 26)
-// persistent 64-channel halo kernels (conv_halo64p_kernel): ids 115-117
-constexpr int kHaloPBase = kHaloBase + 15, kNumHaloPConfigs = 3;
-__host__ __device__ constexpr bool is_halop(int cfg) {
-  return cfg >= kHaloPBase && cfg < kHaloPBase + kNumHaloPConfigs;
-}
-
-static bool halo_cfg(int cfg, int* bm, int* bn, int* bk, int* nw, int* ns) {
-  switch (cfg - kHaloBase) {
-#define X(i, BM, BN, BK, WM, WN, NS) \
-  case i: *bm = BM; *bn = BN; *bk = BK; *nw = WM * WN; *ns = NS; return true;
-    DMP_HALO_CONFIGS(X)
-#undef X
-  }
-  return false;
-}
-
-// geometry of a halo config on a (B, H, W, C) input; false when it does not apply
-static bool halo_geom(int cfg, int H, int W, int C, int R, int S, int stride, int pad,
-                      HaloGeom* g, size_t* lds) {
-  int bm, bn, bk, nw, ns;
-  if (!halo_cfg(cfg, &bm, &bn, &bk, &nw, &ns)) return false;
-  if (R != 3 || S != 3 || stride != 1 || pad != 1 || C % bk != 0) return false;
-  const int img = H * W;
-  HaloGeom h{};
-  h.MV = bm;
-  if (bm <= img) {
-    h.TH = bm / W;
-    h.TB = 1;
-    if (bm % W != 0 || img % bm != 0) {
-      // padded row tiles: the most whole rows that tile the image, at most 1/8 idle
-      // (ImageNet 28x28: 7 rows = 196 pixels in 224; 56x56: 4 rows in 256)
-      while (h.TH > 0 && img % (h.TH * W) != 0) --h.TH;
-      if (h.TH == 0) return false;
-      h.MV = h.TH * W;
-      if (8 * (bm - h.MV) > bm) return false;
-    }
-  } else {
-    h.TH = H;
-    h.TB = bm / img;
-    // padded whole-image tiles: at most 1/8 of the tile's rows idle
-    if (bm % img != 0) {
-      h.MV = h.TB * img;
-      if (8 * (bm - h.MV) > bm) return false;
-    }
-  }
-  const int rpi = 64 / (bk / 8);
-  // fragments wrapping image rows (W not a multiple of 16, not the <= 8 widths the
-  // row-parity key covers): the W + 4-wide staging of conv_halo_kernel (PSW)
-  static const bool psw_on = [] {
+// The halo configs and their tile plans are halo_plan.h; here only the dispatch
+// from a plan to a kernel instantiation.
+// DMP_HALO_PSW=0: no W + 4-wide staging (diagnostic), read once
+static bool halo_psw() {
+  static const bool on = [] {
     const char* e = std::getenv("DMP_HALO_PSW");
     return e == nullptr || e[0] != '0';
   }();
-  h.PSW = psw_on && bk == 32 && W % 16 != 0 && !(W <= 8 && 16 % W == 0);
-  h.W2 = h.PSW ? W + 4 : W + 2;
-  h.PI = (h.TH + 2) * h.W2;
-  if (h.PSW) h.PI += (((h.TH * W - h.PI) % 4) + 4) % 4;   // PI == TH * W (mod 4)
-  h.HROWS = h.TB * h.PI;
-  h.A_INS = (h.HROWS + rpi - 1) / rpi;
-  if (h.A_INS > kHaloAPW * nw) return false;
-  const size_t stage = (size_t)h.A_INS * rpi * bk + (size_t)9 * bn * bk;
-  size_t bytes = (size_t)ns * stage * 2;
-  if (bytes < (size_t)bm * (bn + 8) * 2) bytes = (size_t)bm * (bn + 8) * 2;   // row epilogue tile
-  if (bytes > 160 * 1024) return false;
-  *g = h;
-  *lds = bytes;
-  return true;
-}
-
-// persistent 64-channel halo ids kHaloPBase + i -> (BM, NS, waves)
-static const int kHaloP[3][3] = {{256, 2, 4}, {128, 3, 4}, {256, 2, 8}};
-
-static bool halop_geom(int cfg, int B, int H, int W, int C, int R, int S, int stride, int pad,
-                       HaloPGeom* g, int* bm_out, int* ns_out, int* nw_out, size_t* lds) {
-  const int id = cfg - kHaloPBase;
-  if (id < 0 || id >= kNumHaloPConfigs) return false;
-  const int bm = kHaloP[id][0], ns = kHaloP[id][1], nw = kHaloP[id][2];
-  if (R != 3 || S != 3 || stride != 1 || pad != 1 || C != 64) return false;
-  const int img = H * W;
-  HaloPGeom h{};
-  if (bm <= img) {
-    if (bm % W != 0 || img % bm != 0) return false;
-    h.TH = bm / W;
-    h.TB = 1;
-  } else {
-    if (bm % img != 0) return false;
-    h.TH = H;
-    h.TB = bm / img;
-  }
-  h.HROWS = h.TB * (h.TH + 2) * (W + 2);
-  h.AINS = (h.HROWS + 7) / 8;
-  h.APW = (h.AINS + nw - 1) / nw;
-  if (h.APW > hp_apw_max(nw) || (ns - 2) * h.APW > 24) return false;
-  const long long P = (long long)B * img;
-  if (2LL * P * 64 >= (1LL << 31)) return false;
-  h.ntiles = (int)((P + bm - 1) / bm);
-  const size_t pieces = ns == 2 ? (size_t)h.AINS : (size_t)h.APW * nw;
-  const size_t bytes = 2 * ((size_t)9 * 64 * 64 + (size_t)ns * pieces * 8 * 64);
-  if (bytes > 160 * 1024) return false;
-  *g = h;
-  *bm_out = bm;
-  *ns_out = ns;
-  *nw_out = nw;
-  *lds = bytes;
-  return true;
+  return on;
 }
 
 bool conv_halo_ok(int cfg, int H, int W, int C, int R, int S, int stride, int pad) {
-  if (is_halop(cfg)) {
-    HaloPGeom g;
-    int bm, ns, nw;
-    size_t lds;
-    return halop_geom(cfg, 1, H, W, C, R, S, stride, pad, &g, &bm, &ns, &nw, &lds);
-  }
-  HaloGeom g;
-  size_t lds;
-  return halo_geom(cfg, H, W, C, R, S, stride, pad, &g, &lds);
+  if (is_halop(cfg)) return plan_halop(cfg, 1, H, W, C, R, S, stride, pad).ok;
+  return plan_halo(cfg, H, W, C, R, S, stride, pad, halo_psw()).ok;
 }
 
 int conv_num_halo_configs() { return kNumHaloConfigs; }
@@ -1691,13 +1522,8 @@ int conv_halo_base() { return kHaloBase; }
 
 template <int BM, int BN, int BK, int WM, int WN, int NS, bool FLIP, bool STATS>
 static void launch_halo_t(const ConvArgs& a, const HaloGeom& g, size_t lds, hipStream_t s) {
-  auto kern = conv_halo_kernel<BM, BN, BK, WM, WN, NS, FLIP, STATS>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  constexpr auto kern = conv_halo_kernel<BM, BN, BK, WM, WN, NS, FLIP, STATS>;
+  allow_max_dynamic_lds<kern>();
   const long long M = (long long)a.B * a.OH * a.OW;
   const dim3 grid((unsigned)((M + g.MV - 1) / g.MV), (unsigned)((a.CO + BN - 1) / BN));
   hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, a, g);
@@ -1705,13 +1531,8 @@ static void launch_halo_t(const ConvArgs& a, const HaloGeom& g, size_t lds, hipS
 
 template <int BM, int NS, int NW, bool FLIP, bool STATS>
 static void launch_halop_t(const ConvArgs& a, const HaloPGeom& g, size_t lds, hipStream_t s) {
-  auto kern = conv_halo64p_kernel<BM, NS, NW, FLIP, STATS>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  constexpr auto kern = conv_halo64p_kernel<BM, NS, NW, FLIP, STATS>;
+  allow_max_dynamic_lds<kern>();
   // persistent: one block per CU (the resident weights + ring fill the LDS)
   static int cus = 0;
   if (cus == 0) {
@@ -1729,13 +1550,8 @@ static void launch_halop_t(const ConvArgs& a, const HaloPGeom& g, size_t lds, hi
 // true if launched (cfg is a halo config that applies to this geometry)
 template <bool FLIP, bool STATS>
 static bool launch_halo(const ConvArgs& a, int cfg, hipStream_t s) {
-  HaloGeom g;
-  size_t lds;
   if (a.GH != a.OH || a.GW != a.OW) return false;
   if (is_halop(cfg)) {
-    HaloPGeom pg;
-    int bm, ns, nw;
-    size_t plds;
     // the persistent kernel's statistics forward carries no conv bias (HAS_BIAS)
     // (a statistics forward takes no bias / ReLU / addend in these kernels: PLAIN)
     if (!FLIP && STATS && (a.bias != nullptr || a.relu || a.addend != nullptr)) return false;
@@ -1744,9 +1560,9 @@ static bool launch_halo(const ConvArgs& a, int cfg, hipStream_t s) {
     if (FLIP && a.addend != nullptr && a.addend_sub)
       return launch_halo<FLIP, STATS>(a, kHaloBase + 9, s) ||
              launch_halo<FLIP, STATS>(a, kHaloBase + 5, s);
-    if (!halop_geom(cfg, a.B, a.GH, a.GW, a.CI, a.R, a.S, a.stride, a.pad, &pg, &bm, &ns, &nw,
-                    &plds))
-      return false;
+    const HaloPPlan p = plan_halop(cfg, a.B, a.GH, a.GW, a.CI, a.R, a.S, a.stride, a.pad);
+    if (!p.ok) return false;
+    HaloPGeom pg = p.g;
     static const int xform_env = [] {
       const char* e = getenv("DMP_HALO64P_XFORM");
       return e && e[0] == '1' ? 1 : 0;
@@ -1762,105 +1578,44 @@ static bool launch_halo(const ConvArgs& a, int cfg, hipStream_t s) {
     pg.xs = 1.f;
     pg.xh = 0.f;
     pg.xlo = -INFINITY;
-    if (nw == 8) launch_halop_t<256, 2, 8, FLIP, STATS>(a, pg, plds, s);
-    else if (bm == 256) launch_halop_t<256, 2, 4, FLIP, STATS>(a, pg, plds, s);
-    else launch_halop_t<128, 3, 4, FLIP, STATS>(a, pg, plds, s);
+    if (p.nw == 8) launch_halop_t<256, 2, 8, FLIP, STATS>(a, pg, p.lds, s);
+    else if (p.bm == 256) launch_halop_t<256, 2, 4, FLIP, STATS>(a, pg, p.lds, s);
+    else launch_halop_t<128, 3, 4, FLIP, STATS>(a, pg, p.lds, s);
     return true;
   }
-  if (!halo_geom(cfg, a.GH, a.GW, a.CI, a.R, a.S, a.stride, a.pad, &g, &lds)) return false;
+  const HaloPlan p = plan_halo(cfg, a.GH, a.GW, a.CI, a.R, a.S, a.stride, a.pad, halo_psw());
+  if (!p.ok) return false;
   // the statistics forward's epilogue has no bias / ReLU / addend (PLAIN in
   // halo_epilogue): such a conv takes the implicit GEMM instead
   if (!FLIP && STATS && (a.bias != nullptr || a.relu || a.addend != nullptr)) return false;
   switch (cfg - kHaloBase) {
 #define X(i, BM, BN, BK, WM, WN, NS) \
-  case i: launch_halo_t<BM, BN, BK, WM, WN, NS, FLIP, STATS>(a, g, lds, s); return true;
+  case i: launch_halo_t<BM, BN, BK, WM, WN, NS, FLIP, STATS>(a, p.g, p.lds, s); return true;
     DMP_HALO_CONFIGS(X)
 #undef X
   }
   return false;
 }
 
-// stride-2 halo data-gradient tiles (conv_dgrad_s2_kernel): id, BM, BN, WM, WN
-constexpr int kS2Base = 200;
-// (wave tiles of 32 pixels x 64 channels or 64 x 32 per class: 4 classes x 8
-// accumulator tiles = 128 registers)
-#define DMP_S2_CONFIGS(X)      \
-  X(0, 128, 64, 4, 1, 1)       \
-  X(1, 256, 64, 8, 1, 1)       \
-  X(2, 128, 128, 4, 2, 1)      \
-  X(3, 256, 32, 4, 1, 1)       \
-  X(4, 64, 64, 2, 1, 1)        \
-  X(5, 112, 64, 7, 1, 1)       \
-  X(6, 256, 64, 8, 1, 2)       \
-  X(7, 128, 128, 4, 2, 2)      \
-  X(8, 128, 64, 8, 1, 2)       \
-  X(9, 112, 64, 7, 1, 2)
-constexpr int kNumS2Configs = 10;
-static bool s2_cfg(int cfg, int* bm, int* bn, int* nw, int* ns) {
-  switch (cfg - kS2Base) {
-#define X(i, BM, BN, WM, WN, NS) \
-  case i: *bm = BM; *bn = BN; *nw = WM * WN; *ns = NS; return true;
-    DMP_S2_CONFIGS(X)
-#undef X
-  }
-  return false;
-}
-// geometry of a stride-2 halo dgrad config: dY (OH x OW, K channels) -> dX (H x W, N channels)
-static bool s2_geom(int cfg, int H, int W, int OH, int OW, int K, int N, int R, int S, int stride,
-                    int pad, HaloGeom* g, size_t* lds) {
-  int bm, bn, nw, ns;
-  if (!s2_cfg(cfg, &bm, &bn, &nw, &ns)) return false;
-  if (R != 3 || S != 3 || stride != 2 || pad != 1 || H != 2 * OH || W != 2 * OW) return false;
-  if (K % 32 != 0 || N % bn != 0) return false;
-  const int img = OH * OW;
-  HaloGeom h{};
-  h.MV = bm;
-  if (bm <= img) {
-    if (bm % OW != 0 || img % bm != 0) return false;
-    h.TH = bm / OW;
-    h.TB = 1;
-  } else {
-    if (bm % img != 0) return false;
-    h.TH = OH;
-    h.TB = bm / img;
-  }
-  h.HROWS = h.TB * (h.TH + 1) * (OW + 1);
-  h.A_INS = (h.HROWS + 15) / 16;
-  if (h.A_INS > kHaloAPW * nw) return false;
-  const size_t bytes = (size_t)ns * 2 * ((size_t)h.A_INS * 512 + (size_t)9 * bn * 32);
-  if (bytes > 160 * 1024) return false;
-  *g = h;
-  *lds = bytes;
-  return true;
-}
+// stride-2 halo data-gradient tiles (conv_dgrad_s2_kernel; plan: halo_plan.h)
 bool conv_dgrad_s2_ok(int cfg, int H, int W, int OH, int OW, int K, int N, int R, int S, int stride,
                       int pad) {
-  HaloGeom g;
-  size_t lds;
-  return s2_geom(cfg, H, W, OH, OW, K, N, R, S, stride, pad, &g, &lds);
+  return plan_s2(cfg, H, W, OH, OW, K, N, R, S, stride, pad).ok;
 }
 int conv_dgrad_s2_base() { return kS2Base; }
 int conv_dgrad_s2_num_configs() { return kNumS2Configs; }
 
 template <int BM, int BN, int WM, int WN, int NS>
 static void launch_s2_t(const ConvArgs& a, const HaloGeom& g, size_t lds, hipStream_t s) {
-  auto kern = conv_dgrad_s2_kernel<BM, BN, WM, WN, NS>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  constexpr auto kern = conv_dgrad_s2_kernel<BM, BN, WM, WN, NS>;
+  allow_max_dynamic_lds<kern>();
   const long long M = (long long)a.B * a.GH * a.GW;   // class-grid pixels (= dY pixels)
   const dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)(a.CO / BN));
   hipLaunchKernelGGL(kern, grid, dim3(64 * WM * WN), lds, s, a, g);
 }
 
 int conv_fwd_num_mblocks(long long M, int CO, int cfg) {
-  {
-    int bm, bn, bk, nw, ns;
-    if (halo_cfg(cfg, &bm, &bn, &bk, &nw, &ns)) return (int)((M + bm - 1) / bm);
-  }
+  if (const HaloCfg h = halo_cfg(cfg); h.ok) return (int)((M + h.bm - 1) / h.bm);
   if (cfg < 0 || cfg >= kNumConvConfigs) cfg = conv_default_config(M, CO);
   const int bm = config_bm(cfg);
   return (int)((M + bm - 1) / bm);
@@ -1894,12 +1649,10 @@ void launch_conv_dgrad(const u16* dy, const u16* wt, u16* dx, int B, int H, int 
   a.addend_sub = addend_sub ? 1 : 0;
   a.addmask = addend ? addend_mask : nullptr;
   if (cfg >= kS2Base && cfg < kS2Base + kNumS2Configs) {
-    HaloGeom g;
-    size_t lds;
-    if (s2_geom(cfg, H, W, OH, OW, CO, CI, R, S, stride, pad, &g, &lds)) {
+    if (const S2Plan p = plan_s2(cfg, H, W, OH, OW, CO, CI, R, S, stride, pad); p.ok) {
       switch (cfg - kS2Base) {
 #define X(i, BM, BN, WM, WN, NS) \
-  case i: launch_s2_t<BM, BN, WM, WN, NS>(a, g, lds, s); return;
+  case i: launch_s2_t<BM, BN, WM, WN, NS>(a, p.g, p.lds, s); return;
         DMP_S2_CONFIGS(X)
 #undef X
       }

@@ -23,6 +23,7 @@
 //   NS   - pipeline depth: NS-1 stages of DMA in flight, retired with a
 //          counted s_waitcnt vmcnt(N) before one raw s_barrier per stage.
 #include "common.h"
+#include "halo_plan.h"
 #include "mfma_prims.h"
 
 #ifndef DMP_ABLATE
@@ -293,15 +294,9 @@ __global__ void __launch_bounds__(256) conv_wgrad_kernel(WgradArgs a) {
 // at BM 128, TR 1) had to cover a whole HBM round trip.
 // Blocks are mapped XCD-aware: the tiles of one pixel split share an XCD's L2.
 // Partial sums go to dW with fp32 atomics, or plain read-add-write when one
-// block owns the tile (splits == 1).
-// MV: pixels per tile (= BM, or TB * H * W < BM for padded whole-image tiles on
-// 14x14 / 7x7 maps: the dY rows past MV stage zeros, so they add nothing)
-struct WgradHaloGeom {
-  int TH, TB, THX, XROWS, XPW, ntiles, tiles_per_split, MV;
-};
-
-constexpr int kWhXPW = 12;   // max X-row DMA instructions per wave per stage
-
+// block owns the tile (splits == 1).  The tile plan (WgradHaloGeom, the config
+// ids, the tiling rule) is halo_plan.h.
+//
 // PG = 2: 8 waves in two pixel groups.  Group g (waves 4g..4g+3) owns the
 // same 64 x 16-column slices as the 4-wave block but only pk steps
 // [g * NPK / 2, (g+1) * NPK / 2) of every tile; at the end group 1 parks its
@@ -591,115 +586,20 @@ __global__ void __launch_bounds__(256 * PG) conv_wgrad_halo_kernel(WgradArgs a, 
       }
 }
 
-// halo wgrad cfg ids: kWhBase + variant * 12 + bm_sel * 4 + spl; BM = 64 << bm_sel,
-// target block count 128 << spl; variant -> (NS, TR) below (ids 1000..1011 are
-// the round-1 kernel's configs: NS 2, one tap row per block)
-constexpr int kWhBase = 1000;
-// variants 6-7: BM fixed at 224 = 4 rows of 56 (ImageNet ResNet stage 1, where no
-// power-of-two tile is a whole number of rows); only bm_sel 0 is valid there
-constexpr int kWhVariants = 8;
-constexpr int kWhNS[kWhVariants] = {2, 3, 4, 2, 3, 2, 2, 3};
-constexpr int kWhTR[kWhVariants] = {1, 1, 1, 3, 3, 1, 1, 1};
-constexpr int kWhPG[kWhVariants] = {1, 1, 1, 1, 1, 2, 1, 1};   // pixel groups (8 waves when 2)
-constexpr int kWhBM[kWhVariants] = {0, 0, 0, 0, 0, 0, 224, 224};   // 0: 64 << bm_sel
-
-// slab mode (ids kWhSlabBase + i = halo config kWhBase + i): the split-K partials
-// go to a [splits][dW] fp32 slab with plain stores (~6 TB/s chip-wide) and one
-// streaming pass adds them into dW, instead of fp32 atomics (~1.3 TB/s of added
-// bytes, ~25 % of the 64-channel wgrad: profiles/conv_kernels_r2.txt); offered
-// for the NS-2 one-tap-row variants when the geometry splits K
-constexpr int kWhSlabBase = 3000;
-constexpr bool wh_slab_variant(int var) { return var == 0 || var == 5 || var == 6; }
-
-static bool wgrad_halo_geom(int cfg, int B, int H, int W, int CI, int CO, int R, int S, int stride,
-                            int pad, WgradHaloGeom* g, int* bm_out, int* ns_out, int* tr_out,
-                            int* pg_out, size_t* lds, int* splits) {
-  if (cfg >= kWhSlabBase) cfg -= kWhSlabBase - kWhBase;
-  const int id = cfg - kWhBase;
-  if (id < 0 || id >= 12 * kWhVariants) return false;
-  const int var = id / 12, rest = id % 12;
-  if (kWhBM[var] != 0 && rest / 4 != 0) return false;
-  const int bm = kWhBM[var] != 0 ? kWhBM[var] : 64 << (rest / 4), target = 128 << (rest % 4);
-  const int ns = kWhNS[var], tr = kWhTR[var], pg = kWhPG[var];
-  if (pg == 2 && bm < 128) return false;
-  if (R != 3 || S != 3 || pad != 1 || CI % 64 || CO % 64) return false;
-  const bool s2 = stride == 2;
-  if (stride != 1 && !(s2 && tr == 1 && H % 2 == 0 && W % 2 == 0 && ns <= 3 && kWhBM[var] == 0))
-    return false;
-  if (tr == 3 && bm > 128) return false;   // 36 accumulator tiles + hoisted addresses spill
-  const int XW = W;                        // staged X row width - 2 (input columns)
-  if (s2) { H /= 2; W /= 2; }              // tiles run over the dY (output) geometry
-  const int img = H * W;
-  WgradHaloGeom h{};
-  h.MV = bm;
-  if (bm <= img) {
-    h.TH = bm / W;
-    h.TB = 1;
-    if (bm % W != 0 || img % bm != 0) {
-      // padded row tiles: the most whole rows that tile the image, at most 1/8 idle
-      // (ImageNet 28x28: 7 rows = 196 pixels in 224; 56x56: 4 rows in 256)
-      while (h.TH > 0 && img % (h.TH * W) != 0) --h.TH;
-      if (h.TH == 0) return false;
-      h.MV = h.TH * W;
-      if (8 * (bm - h.MV) > bm) return false;
-    }
-  } else {
-    h.TH = H;
-    h.TB = bm / img;
-    if (bm % img != 0) {   // padded whole-image tiles: at most 1/8 of the rows idle
-      h.MV = h.TB * img;
-      if (8 * (bm - h.MV) > bm) return false;
-    }
-  }
-  h.THX = h.TH + tr - 1;
-  h.XROWS = h.TB * h.THX * (XW + 2);
-  h.XPW = ((h.XROWS + 7) / 8 + 4 * pg - 1) / (4 * pg);
-  if (h.XPW > kWhXPW || h.THX + 1 > 127 || h.TB > 0x7fff) return false;
-  if ((ns - 2) * (bm / 32 + h.XPW) > 40) return false;
-  const long long M = (long long)B * img;
-  if (2LL * M * (CO > CI ? CO : CI) * (s2 ? 4 : 1) >= (1LL << 31)) return false;
-  h.ntiles = (int)((M + h.MV - 1) / h.MV);
-  const int per = (CI / 64) * (CO / 64) * (3 / tr);
-  int sp = target / per;
-  if (sp < 1) sp = 1;
-  if (sp > h.ntiles) sp = h.ntiles;
-  h.tiles_per_split = (h.ntiles + sp - 1) / sp;
-  sp = (h.ntiles + h.tiles_per_split - 1) / h.tiles_per_split;
-  const size_t stage = (size_t)bm * 64 + (size_t)h.XPW * 4 * pg * 512;
-  *lds = (size_t)ns * stage * 2;
-  if (*lds > 160 * 1024) return false;
-  *g = h;
-  *bm_out = bm;
-  *ns_out = ns;
-  *tr_out = tr;
-  *pg_out = pg;
-  *splits = sp;
-  return true;
-}
-
+// halo wgrad cfg ids and their tile plans: halo_plan.h
 bool conv_wgrad_halo_ok(int cfg, int B, int H, int W, int CI, int CO, int R, int S, int stride,
                         int pad) {
-  WgradHaloGeom g;
-  int bm, ns, tr, pg, sp;
-  size_t lds;
-  if (!wgrad_halo_geom(cfg, B, H, W, CI, CO, R, S, stride, pad, &g, &bm, &ns, &tr, &pg, &lds, &sp))
-    return false;
-  if (cfg >= kWhSlabBase) return sp > 1 && wh_slab_variant((cfg - kWhSlabBase) / 12);
-  return true;
+  const WgradHaloPlan p = plan_wgrad_halo(cfg, B, H, W, CI, CO, R, S, stride, pad);
+  return p.ok && (cfg < kWhSlabBase || p.slab_elems > 0);
 }
 // fp32 elements of the slab a slab-mode cfg needs (0: not a slab cfg / no split)
 long long conv_wgrad_halo_slab_elems(int cfg, int B, int H, int W, int CI, int CO, int R, int S,
                                      int stride, int pad) {
-  if (cfg < kWhSlabBase || !conv_wgrad_halo_ok(cfg, B, H, W, CI, CO, R, S, stride, pad)) return 0;
-  WgradHaloGeom g;
-  int bm, ns, tr, pg, sp;
-  size_t lds;
-  wgrad_halo_geom(cfg, B, H, W, CI, CO, R, S, stride, pad, &g, &bm, &ns, &tr, &pg, &lds, &sp);
-  return (long long)sp * CO * R * S * CI;
+  return plan_wgrad_halo(cfg, B, H, W, CI, CO, R, S, stride, pad).slab_elems;
 }
 int conv_wgrad_halo_base() { return kWhBase; }
 int conv_wgrad_halo_slab_base() { return kWhSlabBase; }
-int conv_wgrad_num_halo_configs() { return 12 * kWhVariants; }
+int conv_wgrad_num_halo_configs() { return kNumWhConfigs; }
 
 // dW[e] += sum_s slab[s][e]: a block = 16 float4 columns x 16 split lanes (the
 // split count runs to the hundreds on the 64-channel layers: a thread per
@@ -737,13 +637,8 @@ __global__ void __launch_bounds__(256) wgrad_slab_reduce_kernel(const float* __r
 template <int BM, int NS, int TR, int PG = 1, bool S2 = false>
 static void launch_wgrad_halo_t(const WgradArgs& a, const WgradHaloGeom& g, size_t lds, int splits,
                                 hipStream_t s) {
-  static bool attr = false;
   static int diag = -1;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_wgrad_halo_kernel<BM, NS, TR, PG, S2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  allow_max_dynamic_lds<conv_wgrad_halo_kernel<BM, NS, TR, PG, S2>>();
   if (diag < 0) {
     const char* e = getenv("DMP_WGRAD_HALO_DIAG");
     diag = (e && e[0] == 's') ? 1 : 0;
@@ -797,11 +692,10 @@ void launch_conv_wgrad(const u16* dy, const u16* x, float* dw, int B, int H, int
     else cfg -= kWhSlabBase - kWhBase;   // no slab given: the atomic variant
   }
   if (cfg >= kWhBase && dbias == nullptr) {
-    WgradHaloGeom g;
-    int bm, ns, tr, pg, sp;
-    size_t lds;
-    if (wgrad_halo_geom(cfg, B, H, W, CI, CO, R, S, stride, pad, &g, &bm, &ns, &tr, &pg, &lds,
-                        &sp)) {
+    if (const WgradHaloPlan p = plan_wgrad_halo(cfg, B, H, W, CI, CO, R, S, stride, pad); p.ok) {
+      const WgradHaloGeom& g = p.g;
+      const int bm = p.bm, ns = p.ns, tr = p.tr, pg = p.pg, sp = p.splits;
+      const size_t lds = p.lds;
       if (stride == 2) {   // (geometry: TR 1, NS 2-3, BM 64 / 128 / 256)
         if (pg == 2) {
           if (bm == 128) launch_wgrad_halo_t<128, 2, 1, 2, true>(a, g, lds, sp, s);

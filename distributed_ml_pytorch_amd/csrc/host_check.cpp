@@ -9,12 +9,17 @@
 // plus oversize batches that must be REJECTED, not wrapped.  Any signed overflow,
 // out-of-range shift or bad access in that arithmetic aborts the run (UBSan /
 // ASan, -fno-sanitize-recover).  Exit status 0 and a summary line on success.
+// Every accepted tile plan of the four 3x3 halo-tile families (halo_plan.h) is
+// checked against the tile invariants on the way; `host_check --plans` prints
+// the plans of a fixed shape list instead (one line each, every field).
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "geom_guard.h"
+#include "halo_plan.h"
 #include "launchers.h"
 
 namespace {
@@ -76,6 +81,138 @@ void resnet_convs(std::vector<Conv>& v, const char* name, int B, bool bottleneck
   }
 }
 
+// what every tile of the halo families must satisfy: bm rows, MV of them in use,
+// TB images x TH rows of a gh x gw map (the class grid for stride 2)
+void check_tile(int cfg, int bm, int TH, int TB, int MV, int gh, int gw, size_t lds) {
+  EXPECT(MV == TB * TH * gw, "cfg %d: MV %d != %d x %d x %d", cfg, MV, TB, TH, gw);
+  EXPECT(MV <= bm && 8 * (bm - MV) <= bm, "cfg %d: %d of %d rows in use", cfg, MV, bm);
+  EXPECT(TB == 1 ? TH > 0 && (gh * gw) % (TH * gw) == 0 : TH == gh,
+         "cfg %d: TB %d TH %d on %d x %d", cfg, TB, TH, gh, gw);
+  EXPECT(lds <= (size_t)dmp::kMaxDynamicLds, "cfg %d: %zu B of LDS", cfg, lds);
+}
+
+// Every id of the four halo-tile families on one conv: the public predicates
+// agree with the planners, every accepted plan holds the tile invariants, and
+// (out != nullptr: --plans) after a `shape` line each accepted plan is written
+// with all its fields, in the order of kPlanLegend, then the rejected ids
+// counted per family.  The planners get DMP_HALO_PSW's
+// default (on).  Returns how many stride-1 forward ids conv_halo_ok accepts.
+const char kPlanLegend[] =
+    "# halo cfg bm bn bk nw ns TH TB MV HROWS A_INS W2 PI PSW lds\n"
+    "# halop cfg bm ns nw TH TB HROWS APW AINS ntiles lds\n"
+    "# s2 cfg bm bn nw ns TH TB MV HROWS A_INS lds\n"
+    "# wgrad cfg bm ns tr pg TH TB THX XROWS XPW ntiles tiles_per_split MV lds splits"
+    " [slab_elems]\n";
+
+int check_plans(const Conv& c, std::FILE* out) {
+  const int OH = out_dim(c.H, c.pad, c.R, c.stride), OW = out_dim(c.W, c.pad, c.S, c.stride);
+  char tag[96];
+  std::snprintf(tag, sizeof tag, "B%d C%d %dx%d K%d %dx%d s%d p%d", c.B, c.CI, c.H, c.W, c.CO,
+                c.R, c.S, c.stride, c.pad);
+  if (out) std::fprintf(out, "shape %s\n", tag);
+  auto rejected = [&](const char* family, int n, int of) {
+    if (out) std::fprintf(out, "%s rejected %d of %d\n", family, n, of);
+  };
+  int nfwd = 0, nhalop = 0, rej = 0;
+  for (int i = 0; i < dmp::conv_num_halo_configs(); ++i) {
+    const int cfg = dmp::conv_halo_base() + i;
+    const bool ok = dmp::conv_halo_ok(cfg, c.H, c.W, c.CI, c.R, c.S, c.stride, c.pad);
+    nfwd += ok;
+    if (dmp::is_halop(cfg)) {
+      const dmp::HaloPPlan p =
+          dmp::plan_halop(cfg, c.B, c.H, c.W, c.CI, c.R, c.S, c.stride, c.pad);
+      // the predicate plans for batch 1: only the 2 GiB guard can differ
+      EXPECT(!p.ok || ok, "cfg %d: plan ok, predicate not", cfg);
+      nhalop += p.ok;
+      if (!p.ok) continue;
+      const dmp::HaloPGeom& g = p.g;
+      check_tile(cfg, p.bm, g.TH, g.TB, p.bm, c.H, c.W, p.lds);
+      EXPECT(g.APW <= dmp::hp_apw_max(p.nw) && g.APW * p.nw >= g.AINS, "cfg %d: APW %d AINS %d",
+             cfg, g.APW, g.AINS);
+      EXPECT((long long)g.ntiles * p.bm >= (long long)c.B * c.H * c.W, "cfg %d: %d tiles", cfg,
+             g.ntiles);
+      if (out)
+        std::fprintf(out, "halop %d %d %d %d %d %d %d %d %d %d %zu\n", cfg, p.bm, p.ns, p.nw, g.TH,
+                     g.TB, g.HROWS, g.APW, g.AINS, g.ntiles, p.lds);
+      continue;
+    }
+    const dmp::HaloPlan p =
+        dmp::plan_halo(cfg, c.H, c.W, c.CI, c.R, c.S, c.stride, c.pad, true);
+    EXPECT(p.ok == ok, "cfg %d: plan %d predicate %d", cfg, p.ok, ok);
+    rej += !p.ok;
+    if (!p.ok) continue;
+    const dmp::HaloGeom& g = p.g;
+    check_tile(cfg, p.c.bm, g.TH, g.TB, g.MV, c.H, c.W, p.lds);
+    EXPECT(g.A_INS <= dmp::kHaloAPW * p.c.nw, "cfg %d: A_INS %d", cfg, g.A_INS);
+    if (out)
+      std::fprintf(out, "halo %d %d %d %d %d %d %d %d %d %d %d %d %d %d %zu\n", cfg, p.c.bm,
+                   p.c.bn, p.c.bk, p.c.nw, p.c.ns, g.TH, g.TB, g.MV, g.HROWS, g.A_INS, g.W2, g.PI,
+                   g.PSW, p.lds);
+  }
+  rejected("halo", rej, dmp::kNumHaloConfigs - dmp::kNumHaloPConfigs);
+  rejected("halop", dmp::kNumHaloPConfigs - nhalop, dmp::kNumHaloPConfigs);
+  // stride-2 halo data gradient: dY (OH x OW, CO) -> dX (H x W, CI)
+  rej = 0;
+  for (int i = 0; i < dmp::conv_dgrad_s2_num_configs(); ++i) {
+    const int cfg = dmp::conv_dgrad_s2_base() + i;
+    const dmp::S2Plan p =
+        dmp::plan_s2(cfg, c.H, c.W, OH, OW, c.CO, c.CI, c.R, c.S, c.stride, c.pad);
+    const bool ok = dmp::conv_dgrad_s2_ok(cfg, c.H, c.W, OH, OW, c.CO, c.CI, c.R, c.S, c.stride,
+                                          c.pad);
+    EXPECT(p.ok == ok, "cfg %d: plan %d predicate %d", cfg, p.ok, ok);
+    rej += !p.ok;
+    if (!p.ok) continue;
+    const dmp::HaloGeom& g = p.g;
+    check_tile(cfg, p.bm, g.TH, g.TB, g.MV, OH, OW, p.lds);
+    EXPECT(g.MV == p.bm && g.A_INS <= dmp::kHaloAPW * p.nw, "cfg %d: MV %d A_INS %d", cfg, g.MV,
+           g.A_INS);
+    if (out)
+      std::fprintf(out, "s2 %d %d %d %d %d %d %d %d %d %d %zu\n", cfg, p.bm, p.bn, p.nw, p.ns,
+                   g.TH, g.TB, g.MV, g.HROWS, g.A_INS, p.lds);
+  }
+  rejected("s2", rej, dmp::conv_dgrad_s2_num_configs());
+  // halo weight gradient, atomic and slab (split-K partials) forms
+  rej = 0;
+  const int nwh = dmp::conv_wgrad_num_halo_configs();
+  for (int i = 0; i < 2 * nwh; ++i) {
+    const bool slab = i >= nwh;
+    const int cfg = slab ? dmp::conv_wgrad_halo_slab_base() + i - nwh
+                         : dmp::conv_wgrad_halo_base() + i;
+    const dmp::WgradHaloPlan p =
+        dmp::plan_wgrad_halo(cfg, c.B, c.H, c.W, c.CI, c.CO, c.R, c.S, c.stride, c.pad);
+    const bool ok = dmp::conv_wgrad_halo_ok(cfg, c.B, c.H, c.W, c.CI, c.CO, c.R, c.S, c.stride,
+                                            c.pad);
+    const long long se = dmp::conv_wgrad_halo_slab_elems(cfg, c.B, c.H, c.W, c.CI, c.CO, c.R, c.S,
+                                                         c.stride, c.pad);
+    EXPECT(ok == (p.ok && (!slab || se > 0)) && se == p.slab_elems && (slab || se == 0),
+           "wgrad cfg %d: plan %d predicate %d slab %lld / %lld", cfg, p.ok, ok, se, p.slab_elems);
+    if (se > 0)
+      EXPECT(se == (long long)p.splits * c.CO * c.R * c.S * c.CI && p.splits > 1,
+             "slab elems %lld", se);
+    rej += !ok;
+    if (!ok) continue;
+    const dmp::WgradHaloGeom& g = p.g;
+    const int gh = c.stride == 2 ? c.H / 2 : c.H, gw = c.stride == 2 ? c.W / 2 : c.W;
+    check_tile(cfg, p.bm, g.TH, g.TB, g.MV, gh, gw, p.lds);
+    EXPECT(g.XPW <= dmp::kWhXPW && g.XPW * 4 * p.pg * 8 >= g.XROWS, "cfg %d: XPW %d XROWS %d", cfg,
+           g.XPW, g.XROWS);
+    EXPECT((long long)g.ntiles * g.MV >= (long long)c.B * gh * gw, "cfg %d: %d tiles", cfg,
+           g.ntiles);
+    EXPECT((long long)p.splits * g.tiles_per_split >= g.ntiles &&
+               g.ntiles > (long long)(p.splits - 1) * g.tiles_per_split,
+           "cfg %d: %d splits of %d tiles over %d", cfg, p.splits, g.tiles_per_split, g.ntiles);
+    if (out) {
+      std::fprintf(out, "wgrad %d %d %d %d %d %d %d %d %d %d %d %d %d %zu %d", cfg, p.bm, p.ns,
+                   p.tr, p.pg, g.TH, g.TB, g.THX, g.XROWS, g.XPW, g.ntiles, g.tiles_per_split,
+                   g.MV, p.lds, p.splits);
+      if (slab) std::fprintf(out, " %lld", se);
+      std::fprintf(out, "\n");
+    }
+  }
+  rejected("wgrad", rej, 2 * nwh);
+  return nfwd;
+}
+
 void check_conv(const Conv& c) {
   const int OH = out_dim(c.H, c.pad, c.R, c.stride), OW = out_dim(c.W, c.pad, c.S, c.stride);
   EXPECT(OH > 0 && OW > 0, "%s empty output", c.model);
@@ -96,30 +233,10 @@ void check_conv(const Conv& c) {
     }
     const int dflt = dmp::conv_default_config(M, c.CO);
     EXPECT(dflt >= 0 && dflt < ncfg, "default cfg %d", dflt);
-    // 3x3 stride-1 halo tiles (incl. the persistent 64-channel ones)
-    int nhalo = 0;
-    for (int i = 0; i < dmp::conv_num_halo_configs(); ++i)
-      nhalo += dmp::conv_halo_ok(dmp::conv_halo_base() + i, c.H, c.W, c.CI, c.R, c.S, c.stride,
-                                 c.pad);
+    // every plan of the four 3x3 halo-tile families
+    const int nhalo = check_plans(c, nullptr);
     if (c.R == 3 && c.stride == 1 && c.pad == 1 && c.H >= 4)
       EXPECT(nhalo > 0, "%s: no halo config for %dx%dx%d", c.model, c.H, c.W, c.CI);
-    // stride-2 halo data gradient: dY (OH x OW, CO) -> dX (H x W, CI)
-    for (int i = 0; i < dmp::conv_dgrad_s2_num_configs(); ++i)
-      dmp::conv_dgrad_s2_ok(dmp::conv_dgrad_s2_base() + i, c.H, c.W, OH, OW, c.CO, c.CI, c.R,
-                            c.S, c.stride, c.pad);
-    // halo weight gradient, atomic and slab (split-K partials) forms
-    for (int i = 0; i < dmp::conv_wgrad_num_halo_configs(); ++i) {
-      const int cfg = dmp::conv_wgrad_halo_base() + i;
-      dmp::conv_wgrad_halo_ok(cfg, c.B, c.H, c.W, c.CI, c.CO, c.R, c.S, c.stride, c.pad);
-      const int scfg = dmp::conv_wgrad_halo_slab_base() + i;
-      const long long se = dmp::conv_wgrad_halo_slab_elems(scfg, c.B, c.H, c.W, c.CI, c.CO, c.R,
-                                                           c.S, c.stride, c.pad);
-      const bool ok = dmp::conv_wgrad_halo_ok(scfg, c.B, c.H, c.W, c.CI, c.CO, c.R, c.S,
-                                              c.stride, c.pad);
-      EXPECT(ok == (se > 0), "slab cfg %d: ok %d elems %lld", scfg, ok, se);
-      if (se > 0)
-        EXPECT(se % ((long long)c.CO * c.R * c.S * c.CI) == 0, "slab elems %lld", se);
-    }
   } else if (c.CI < 64) {
     // stems: 3x3 MFMA stem, VALU small conv, ImageNet s2d stem
     if (dmp::stem3_supported(c.CI, c.R, c.S, c.CO, c.stride, c.pad, c.W) &&
@@ -245,8 +362,47 @@ int selftest(const char* kind) {
   return big + n;                  // UBSan: signed integer overflow
 }
 
-int main() {
+// The fixed 3x3 / pad-1 shape list of the plan table.  --plans writes the table
+// to stdout (tests/golden/halo_plans.txt is that output; tests/test_asan_cpu.py
+// compares); the default run checks the same plans silently.
+void check_plan_shapes(std::FILE* out) {
+  struct { int B, CI, H, W, CO, stride; } const shapes[] = {
+      // tests/test_conv_gpu.py HALO_SHAPES
+      {4, 64, 32, 32, 64, 1}, {3, 128, 16, 16, 128, 1}, {5, 256, 8, 8, 256, 1},
+      {9, 512, 4, 4, 512, 1}, {2, 64, 8, 8, 128, 1}, {2, 64, 56, 56, 64, 1},
+      {3, 128, 28, 28, 128, 1}, {3, 256, 14, 14, 256, 1}, {5, 512, 7, 7, 512, 1},
+      // test_halo_wgrad_stride2, test_stride2_halo_dgrad_configs
+      {3, 64, 32, 32, 128, 2}, {5, 128, 16, 16, 256, 2}, {9, 256, 8, 8, 512, 2},
+      {2, 128, 56, 56, 128, 2}, {4, 64, 32, 32, 128, 2}, {2, 128, 16, 16, 256, 2},
+      {8, 256, 8, 8, 512, 2}, {2, 64, 56, 56, 128, 2},
+      // ResNet-18 CIFAR at batch 512
+      {512, 64, 32, 32, 64, 1}, {512, 64, 32, 32, 128, 2}, {512, 128, 16, 16, 128, 1},
+      {512, 128, 16, 16, 256, 2}, {512, 256, 8, 8, 256, 1}, {512, 256, 8, 8, 512, 2},
+      {512, 512, 4, 4, 512, 1},
+      // ResNet-50 ImageNet at batch 128
+      {128, 64, 56, 56, 64, 1}, {128, 128, 56, 56, 128, 2}, {128, 128, 28, 28, 128, 1},
+      {128, 256, 28, 28, 256, 2}, {128, 256, 14, 14, 256, 1}, {128, 512, 14, 14, 512, 2},
+      {128, 512, 7, 7, 512, 1},
+      // edges.  W not a multiple of 16 and H != W (28 / 14 / 7 wide: above)
+      {2, 64, 9, 11, 64, 1},
+      // a map smaller than any tile (4x4: above)
+      {4, 64, 2, 2, 64, 1},
+      // C not a multiple of 32 or 64
+      {2, 48, 16, 16, 48, 1}, {2, 96, 16, 16, 96, 1},
+      // batch 1, and batches past the 2 GiB guard
+      {1, 64, 32, 32, 64, 1}, {16384, 64, 32, 32, 64, 1}, {1 << 20, 64, 32, 32, 128, 2},
+  };
+  if (out) std::fputs(kPlanLegend, out);
+  for (const auto& s : shapes)
+    check_plans({"plans", s.B, s.CI, s.H, s.W, s.CO, 3, 3, s.stride, 1}, out);
+}
+
+int main(int argc, char** argv) {
   if (const char* st = std::getenv("DMP_ASAN_SELFTEST")) return selftest(st);
+  if (argc > 1 && std::strcmp(argv[1], "--plans") == 0) {
+    check_plan_shapes(stdout);
+    return g_fail == 0 ? 0 : 1;
+  }
   std::vector<Conv> convs;
   for (int B : {1, 8, 64, 512, 1024}) resnet_convs(convs, "resnet18-cifar", B, false, true);
   for (int B : {1, 32, 128}) resnet_convs(convs, "resnet50-imagenet", B, true, false);
@@ -260,6 +416,7 @@ int main() {
     convs.push_back({"lenet", B, 3, 32, 32, 6, 5, 5, 1, 0});
   }
   for (const Conv& c : convs) check_conv(c);
+  check_plan_shapes(nullptr);
   // ViT-B/16 bs64 (197 tokens, D 768, MLP 3072) and the CNN heads
   for (int M : {64 * 197, 8 * 197, 64 * 196})
     for (int NK : {768, 2304, 3072}) {

@@ -1,4 +1,4 @@
-"""Every halo-tile config (csrc/conv.hip DMP_HALO_CONFIGS) on the ResNet-18 CIFAR
+"""Every halo-tile config (csrc/halo_plan.h DMP_HALO_CONFIGS) on the ResNet-18 CIFAR
 3x3 stride-1 layers: forward (+BN partial sums) and data gradient, us per call
 (min over rounds) and TF/s of the best.  Run on the GPU box."""
 import argparse

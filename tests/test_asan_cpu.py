@@ -33,6 +33,22 @@ def test_make_asan_runs_clean(host_check):
     assert checks > 10000, line
 
 
+def test_halo_plans_match_golden(host_check):
+    """`host_check --plans`: every accepted tile plan of the four halo-tile kernel
+    families (csrc/halo_plan.h) over a fixed shape list, line for line against the
+    table recorded from the commit before the planners were shared."""
+    exe, _ = host_check
+    r = subprocess.run([exe, "--plans"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    with open(os.path.join(ROOT, "tests", "golden", "halo_plans.txt")) as f:
+        want = f.read().splitlines()
+    got = r.stdout.splitlines()
+    assert len(want) > 1000
+    for n, (g, w) in enumerate(zip(got, want), 1):
+        assert g == w, f"line {n}"
+    assert len(got) == len(want)
+
+
 @pytest.mark.parametrize("kind,marker", [("asan", "AddressSanitizer"),
                                          ("ubsan", "runtime error")])
 def test_sanitizers_are_live(host_check, kind, marker):
