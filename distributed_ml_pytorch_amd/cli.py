@@ -52,10 +52,15 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--staleness", type=int, default=1)
     p.add_argument("--pull-mode", default="overwrite", choices=["overwrite", "rebase"])
     p.add_argument("--wire-dtype", default="fp32", choices=["fp32", "bf16"])
-    p.add_argument("--push-wire", default="same", choices=["same", "mx8"],
+    p.add_argument("--push-wire", default="same", choices=["same", "mx8", "topk"],
                    help="'mx8': pushes travel as block-scaled 8-bit payloads (MXFP8, ~1.03 B per "
                         "parameter) and the rounding error stays in the accumulator for the next "
-                        "push; local and central PS only.  'same': pushes use --wire-dtype")
+                        "push.  'topk': a push carries the --push-topk largest entries of every "
+                        "256-element block as bf16 (K / 64 B per parameter) and the rest stays in "
+                        "the accumulator.  Both: local and central PS only.  'same': pushes use "
+                        "--wire-dtype")
+    p.add_argument("--push-topk", type=int, default=8, metavar="K",
+                   help="--push-wire topk: entries sent per 256-element block, 1..32")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     p.add_argument("--momentum", type=float, default=0.0)
     p.add_argument("--weight-decay", type=float, default=0.0)
@@ -121,7 +126,8 @@ def config_from_args(a) -> TrainConfig:
         test_batch_size=a.test_batch_size, epochs=a.epochs, max_steps=a.max_steps, lr=a.lr,
         momentum=a.momentum, weight_decay=a.weight_decay, lr_schedule=a.lr_schedule,
         n_push=a.num_push, n_pull=a.num_pull, staleness=a.staleness, pull_mode=a.pull_mode,
-        wire_dtype=a.wire_dtype, push_wire=a.push_wire, mode=mode, ps=a.ps, payload=a.payload, dtype=a.dtype,
+        wire_dtype=a.wire_dtype, push_wire=a.push_wire, push_topk=a.push_topk, mode=mode, ps=a.ps,
+        payload=a.payload, dtype=a.dtype,
         cuda=a.cuda, log_interval=a.log_interval, evaluate=not a.no_eval, seed=a.seed,
         log_dir=a.log_dir, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every,
         resume=a.resume, ps_resume=a.ps_resume, delta_scale=a.delta_scale,

@@ -276,6 +276,57 @@ void ps_apply_dc_mx8(Tensor shard, Tensor payload, Tensor bak, optional<Tensor> 
                           ptr_or_null<const float>(factor));
 }
 
+// ---- sparse block top-k push wire (parallel/wire_topk.py)
+// payload of an n-element arena at K = k: topk_words(n, k) int32 words
+uint32_t* topk_payload(const Tensor& payload, int64_t n, int64_t k, const Tensor& like,
+                       const char* fn) {
+  TORCH_CHECK(k >= 1 && k <= dmp::kTopkMaxK, fn, ": k must be in 1..", dmp::kTopkMaxK, ", got ", k);
+  const long long nwords = dmp::topk_words(n, (int)k);
+  TORCH_CHECK(nwords >= 0, fn, ": ", n, " elements are out of range for the top-k wire");
+  check_flat(payload, at::kInt, nwords, "payload");
+  TORCH_CHECK(payload.is_contiguous() && payload.device() == like.device(), fn,
+              ": payload must be contiguous and on the arena's device");
+  return reinterpret_cast<uint32_t*>(payload.data_ptr<int>());
+}
+
+int64_t topk_words(int64_t n, int64_t k) {
+  TORCH_CHECK(k >= 1 && k <= dmp::kTopkMaxK, "topk_words: k must be in 1..", dmp::kTopkMaxK);
+  const long long nwords = dmp::topk_words(n, (int)k);
+  TORCH_CHECK(nwords >= 0, "topk_words: ", n, " elements are out of range");
+  return nwords;
+}
+
+// payload <- the k largest of every 256-block of acc, acc <- what was not sent
+void push_handoff_topk(Tensor acc, Tensor payload, int64_t k) {
+  const int64_t n = flat_len(acc, "arena length");
+  check_flat(acc, at::kFloat, n, "acc");
+  TORCH_CHECK(acc.is_contiguous(), "acc must be contiguous");
+  uint32_t* out = topk_payload(payload, n, k, acc, "push_handoff_topk");
+  dmp::launch_push_handoff_topk(acc.data_ptr<float>(), out, n, (int)k, cur_stream());
+}
+
+// ps_apply for a top-k payload: the same shapes (plain + mirror, atomic, factor)
+void ps_apply_topk(Tensor shard, Tensor payload, optional<Tensor> mirror, double scale,
+                   bool atomic, optional<Tensor> factor, int64_t k) {
+  const int64_t n = check_apply("ps_apply_topk", shard, mirror, atomic, factor);
+  TORCH_CHECK(shard.is_contiguous(), "shard must be contiguous");
+  const uint32_t* in = topk_payload(payload, n, k, shard, "ps_apply_topk");
+  dmp::launch_ps_apply_topk(shard.data_ptr<float>(), in, nullptr, bf16_or_null(mirror), n, (int)k,
+                            (float)scale, 0.f, atomic, cur_stream(),
+                            ptr_or_null<const float>(factor));
+}
+
+void ps_apply_dc_topk(Tensor shard, Tensor payload, Tensor bak, optional<Tensor> mirror,
+                      double scale, double c, bool atomic, optional<Tensor> factor, int64_t k) {
+  const int64_t n = check_apply("ps_apply_dc_topk", shard, mirror, atomic, factor);
+  TORCH_CHECK(shard.is_contiguous(), "shard must be contiguous");
+  const float* b = check_dc("ps_apply_dc_topk", shard, bak, n, c);
+  const uint32_t* in = topk_payload(payload, n, k, shard, "ps_apply_dc_topk");
+  dmp::launch_ps_apply_topk(shard.data_ptr<float>(), in, b, bf16_or_null(mirror), n, (int)k,
+                            (float)scale, (float)c, atomic, cur_stream(),
+                            ptr_or_null<const float>(factor));
+}
+
 // One read of the shard into any of out32 (fp32 copy), out16 (bf16 copy) and
 // bak (the backup a later ps_apply_dc compensates against); at least one
 void ps_snapshot(Tensor shard, optional<Tensor> out32, optional<Tensor> out16,
@@ -360,6 +411,19 @@ void bind_optim(pybind11::module_& m) {
         py::arg("shard"), py::arg("payload"), py::arg("bak"), py::arg("mirror") = py::none(),
         py::arg("scale") = 1.0, py::arg("c") = 0.0, py::arg("atomic") = false,
         py::arg("factor") = py::none());
+  m.def("topk_words", &topk_words, "int32 words of a top-k push payload", py::arg("n"),
+        py::arg("k"));
+  m.def("push_handoff_topk", &push_handoff_topk,
+        "send the k largest of every 256-block of the push accumulator, keep the rest",
+        py::arg("acc"), py::arg("payload"), py::arg("k"));
+  m.def("ps_apply_topk", &ps_apply_topk, "parameter-server apply of a top-k payload",
+        py::arg("shard"), py::arg("payload"), py::arg("mirror") = py::none(),
+        py::arg("scale") = 1.0, py::arg("atomic") = false, py::arg("factor") = py::none(),
+        py::arg("k") = 8);
+  m.def("ps_apply_dc_topk", &ps_apply_dc_topk, "delay-compensated apply of a top-k payload",
+        py::arg("shard"), py::arg("payload"), py::arg("bak"), py::arg("mirror") = py::none(),
+        py::arg("scale") = 1.0, py::arg("c") = 0.0, py::arg("atomic") = false,
+        py::arg("factor") = py::none(), py::arg("k") = 8);
   m.def("ps_snapshot", &ps_snapshot, "one read of a shard into fp32 / bf16 copies and a backup",
         py::arg("shard"), py::arg("out32") = py::none(), py::arg("out16") = py::none(),
         py::arg("bak") = py::none());

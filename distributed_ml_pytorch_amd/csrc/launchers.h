@@ -56,6 +56,18 @@ void launch_push_handoff(float* acc, float* out32, uint16_t* out16, long long n,
 // length out of range.  The kernels take n % 4 == 0 and a 16-B aligned payload.
 long long mx8_layout(long long n, long long* scales_off);
 void launch_push_handoff_mx8(float* acc, uint8_t* payload, long long n, hipStream_t s);
+// Sparse block top-k push wire (parallel/wire_topk.py): k slots for every block
+// of 256 elements.  topk_words: int32 words of the payload of n elements, -1 for
+// a k outside 1..kTopkMaxK or a length out of range.  The hand-off takes
+// n % 4 == 0.  launch_ps_apply_topk: `bak` null = the plain apply, else the
+// delay-compensated one; atomic / mirror / factor as launch_ps_apply.
+constexpr int kTopkBlock = 256;
+constexpr int kTopkMaxK = 32;
+long long topk_words(long long n, int k);
+void launch_push_handoff_topk(float* acc, uint32_t* payload, long long n, int k, hipStream_t s);
+void launch_ps_apply_topk(float* shard, const uint32_t* payload, const float* bak,
+                          uint16_t* mirror, long long n, int k, float scale, float c, bool atomic,
+                          hipStream_t s, const float* factor = nullptr);
 void launch_cast_f32_bf16(const float* src, uint16_t* dst, long long n, hipStream_t s);
 int launch_sumsq_partial(const float* x, float* partial, long long n, hipStream_t s);
 void launch_zero_fill(void* p, long long bytes, hipStream_t s);

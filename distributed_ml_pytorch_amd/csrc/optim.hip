@@ -577,6 +577,128 @@ __global__ void __launch_bounds__(256) ps_apply_dc_atomic_kernel(
     unsafeAtomicAdd(shard + i, dc_term(shard[i], delta.load1(i), bak[i], c, scale));
 }
 
+// ---- sparse block top-k push wire (specification: parallel/wire_topk.py) --------
+// Payload of n elements at K: ceil(n / 256) * K int32 words, K slots per block
+// of 256 elements; a word is (bf16 bits << 16) | offset in the block.  The one
+// host-side definition; -1 for a K or a length the kernels do not take (the
+// applies divide a 32-bit word index by K).
+long long topk_words(long long n, int k) {
+  if (k < 1 || k > kTopkMaxK || n < 0 || n > (1LL << 33)) return -1;
+  return (n + kTopkBlock - 1) / kTopkBlock * k;
+}
+
+// torch's fp32 -> bf16 on the bits (round to nearest even as integer arithmetic,
+// every NaN to 0x7fc0): no dependence on the conversion instruction's NaN
+// payload or denormal handling.  Only a round's one winning lane runs it.
+__device__ __forceinline__ u32 topk_bf16(u32 bits) {
+  if ((bits & 0x7fffffffu) > 0x7f800000u) return 0x7fc0u;
+  return (bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16;
+}
+
+// max over the wave of a per-lane value, wave-uniform: xor 1, xor 2 inside the
+// quad, row_half_mirror and row_mirror give every lane its row's max (16
+// lanes), then one lane of each row is read.  All 64 lanes must be active.
+__device__ __forceinline__ u32 topk_wave_max(u32 m) {
+  m = max(m, (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0xB1, 0xF, 0xF, true));
+  m = max(m, (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x4E, 0xF, 0xF, true));
+  m = max(m, (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x141, 0xF, 0xF, true));
+  m = max(m, (u32)__builtin_amdgcn_update_dpp(0, (int)m, 0x140, 0xF, 0xF, true));
+  const u32 a = (u32)__builtin_amdgcn_readlane((int)m, 0), b = (u32)__builtin_amdgcn_readlane((int)m, 16);
+  const u32 c = (u32)__builtin_amdgcn_readlane((int)m, 32), d = (u32)__builtin_amdgcn_readlane((int)m, 48);
+  return max(max(a, b), max(c, d));
+}
+
+// Push hand-off on the top-k wire: payload = sparsify(acc), acc = residual, one
+// pass.  One wave owns one block of 256: lane l holds the float4 at block * 64
+// + l (a 16-B load per lane, contiguous across the wave), so element offset
+// idx = 4 * lane + component.  The wave loops over blocks with a wave-uniform
+// bound: all 64 lanes are active in every cross-lane step; a lane past the end
+// holds zeros (never selected) and stores nothing.
+// One round: every lane offers the largest magnitude key among its components
+// not yet taken, the wave takes the max, __ballot finds the lanes that hold it,
+// the lowest such lane and in it the lowest such component win (the lowest
+// index).  The winner writes slot r, replaces its component with the residual
+// and marks it in its 4-bit `taken` mask, which also zeroes the component's key:
+// a residual is non-zero and would otherwise be selected again.  No LDS, no
+// atomics.  A block stops when the wave max is 0 and zero-fills the remaining
+// slots.  Only lanes that took something store their float4 back: the pass
+// reads 4 B per parameter and writes next to nothing.
+__global__ void __launch_bounds__(256) push_handoff_topk_kernel(
+    f32x4* __restrict__ acc, u32* __restrict__ payload, long long n4, long long nblk, int k) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const long long nwaves = (long long)gridDim.x * 4;
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); b < nblk; b += nwaves) {
+    const long long i = b * 64 + lane;
+    const bool v = i < n4;
+    f32x4 a = z;
+    if (v) a = acc[i];
+    u32 k0 = __float_as_uint(a[0]) & 0x7fffffffu, k1 = __float_as_uint(a[1]) & 0x7fffffffu;
+    u32 k2 = __float_as_uint(a[2]) & 0x7fffffffu, k3 = __float_as_uint(a[3]) & 0x7fffffffu;
+    u32 m = max(max(k0, k1), max(k2, k3));
+    u32 taken = 0;
+    u32* __restrict__ out = payload + b * k;
+    int r = 0;
+    for (; r < k; ++r) {
+      const u32 top = topk_wave_max(m);
+      if (top == 0) break;                                  // wave-uniform
+      const unsigned long long holders = __ballot(m == top);
+      if (lane == __ffsll((long long)holders) - 1) {
+        const int c = k0 == top ? 0 : k1 == top ? 1 : k2 == top ? 2 : 3;
+        const float x = c == 0 ? a[0] : c == 1 ? a[1] : c == 2 ? a[2] : a[3];
+        const u32 h = topk_bf16(__float_as_uint(x));
+        out[r] = (h << 16) | (u32)(4 * lane + c);
+        const float left = top >= 0x7f800000u ? 0.f : x - __uint_as_float(h << 16);
+        if (c == 0) { a[0] = left; k0 = 0; }
+        else if (c == 1) { a[1] = left; k1 = 0; }
+        else if (c == 2) { a[2] = left; k2 = 0; }
+        else { a[3] = left; k3 = 0; }
+        taken |= 1u << c;
+        m = max(max(k0, k1), max(k2, k3));
+      }
+    }
+    if (lane >= r && lane < k) out[lane] = 0;               // empty slots (k <= 32 lanes)
+    if (taken) acc[i] = a;                                  // taken: a real element, i < n4
+  }
+}
+
+// Sparse applies: one thread per payload word, shard[block * 256 + idx] +=
+// scale * value, in the forms the dense wires have (plain with an optional bf16
+// mirror store of the touched elements, fp32-atomic, either with the damping
+// factor, either delay-compensated against bak[addr]).  A scatter, not a fourth
+// wire reader.  Every form skips a word whose value is +-0 (an empty slot, or a
+// value that rounded to zero) and a word whose address is >= n (a malformed
+// payload must not write outside the shard).  The plain form rounds scale * v
+// and the sum separately (mx8_axpy, dc_axpy): plain, atomic and the CPU
+// expression give the same bits.  Addresses within one well-formed payload are
+// distinct, so the plain form needs no atomics; a payload with duplicate
+// addresses is malformed and is defined only for the atomic form.
+template <bool ATOMIC, bool DC>
+__global__ void __launch_bounds__(256) ps_apply_topk_kernel(
+    float* __restrict__ shard, const u32* __restrict__ payload, const float* __restrict__ bak,
+    u16* __restrict__ mirror, u32 nwords, long long n, u32 k, float scale, float c,
+    const float* factor) {
+  scale = ps_scale(scale, factor);
+  const u32 stride = gridDim.x * blockDim.x;                // nwords <= 2^30: no wrap below
+  for (u32 j = blockIdx.x * blockDim.x + threadIdx.x; j < nwords; j += stride) {
+    const u32 w = payload[j];
+    if ((w & 0x7fff0000u) == 0) continue;
+    const long long at = (long long)(j / k) * kTopkBlock + (w & 0xffu);
+    if (at >= n) continue;
+    const float d = __uint_as_float(w & 0xffff0000u);
+    if constexpr (ATOMIC) {
+      if constexpr (DC) unsafeAtomicAdd(shard + at, dc_term(shard[at], d, bak[at], c, scale));
+      else unsafeAtomicAdd(shard + at, scale * d);
+    } else {
+      float s = shard[at];
+      if constexpr (DC) s = dc_axpy(s, d, bak[at], c, scale);
+      else s = mx8_axpy(s, scale, d);
+      shard[at] = s;
+      if (mirror) mirror[at] = f2bf(s);
+    }
+  }
+}
+
 // Reply snapshot: ONE read of the shard feeds the fp32 payload, the bf16
 // payload and the worker's backup (any of them null), so the backup is the very
 // values that were sent even while other link streams add to the shard.
@@ -822,6 +944,39 @@ void launch_push_handoff_mx8(float* acc, u8* payload, long long n, hipStream_t s
   const long long n4 = n / 4;
   hipLaunchKernelGGL(push_handoff_mx8_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
                      (f32x4*)acc, payload, n4, so);
+}
+
+// payload: topk_words(n, k) int32 words; n % 4 == 0 (both checked by the binding)
+void launch_push_handoff_topk(float* acc, u32* payload, long long n, int k, hipStream_t s) {
+  if (n <= 0) return;
+  const long long nblk = (n + kTopkBlock - 1) / kTopkBlock;
+  hipLaunchKernelGGL(push_handoff_topk_kernel, dim3(stream_grid(nblk * 64, 256)), dim3(256), 0, s,
+                     (f32x4*)acc, payload, n / 4, nblk, k);
+}
+
+// bak null: the plain apply; else the delay-compensated one with coefficient c
+void launch_ps_apply_topk(float* shard, const u32* payload, const float* bak, u16* mirror,
+                          long long n, int k, float scale, float c, bool atomic, hipStream_t s,
+                          const float* factor) {
+  const long long nwords = topk_words(n, k);
+  if (nwords <= 0) return;
+  const dim3 grid((unsigned)std::min<long long>((nwords + 255) / 256, 256LL * 16)), block(256);
+  const u32 nw = (u32)nwords, ku = (u32)k;
+  if (bak) {
+    if (atomic)
+      hipLaunchKernelGGL((ps_apply_topk_kernel<true, true>), grid, block, 0, s, shard, payload,
+                         bak, mirror, nw, n, ku, scale, c, factor);
+    else
+      hipLaunchKernelGGL((ps_apply_topk_kernel<false, true>), grid, block, 0, s, shard, payload,
+                         bak, mirror, nw, n, ku, scale, c, factor);
+  } else {
+    if (atomic)
+      hipLaunchKernelGGL((ps_apply_topk_kernel<true, false>), grid, block, 0, s, shard, payload,
+                         bak, mirror, nw, n, ku, scale, c, factor);
+    else
+      hipLaunchKernelGGL((ps_apply_topk_kernel<false, false>), grid, block, 0, s, shard, payload,
+                         bak, mirror, nw, n, ku, scale, c, factor);
+  }
 }
 
 void launch_cast_f32_bf16(const float* src, u16* dst, long long n, hipStream_t s) {

@@ -44,11 +44,14 @@ class Asynchronous(Optimizer):
                  pull_mode: str = "overwrite", wire_dtype: torch.dtype = torch.float32,
                  shadow_dtype: torch.dtype | None | str = "auto", optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0,
-                 schedule=None, push_wire: str = "same"):
+                 schedule=None, push_wire: str = "same", push_topk: int = 8):
         """``push_wire="mx8"``: pushes travel as block-scaled 8-bit payloads
         (:mod:`.wire8`) and the accumulator keeps the quantisation residual, so
-        nothing is lost, only delayed to the next push.  Local and central PS
-        clients only; ``"same"`` (default) pushes in ``wire_dtype``."""
+        nothing is lost, only delayed to the next push.  ``push_wire="topk"``:
+        a push carries the ``push_topk`` (1..32) largest entries of every
+        256-element block (:mod:`.wire_topk`); everything else stays in the
+        accumulator for a later push.  Local and central PS clients only;
+        ``"same"`` (default) pushes in ``wire_dtype``."""
         if lr is required or n_push is required or n_pull is required or model is required:
             raise TypeError("Asynchronous needs lr, n_push, n_pull and model")
         if lr < 0.0:
@@ -91,9 +94,11 @@ class Asynchronous(Optimizer):
         self.timer = _NO_TIMER      # a utils.metrics.StepTimer when the trainer wires one
         if client is None:
             client = default_client(staleness=staleness, pull_mode=pull_mode,
-                                    wire_dtype=wire_dtype, push_wire=push_wire)
-        elif check_push_wire(push_wire) != "same":
+                                    wire_dtype=wire_dtype, push_wire=push_wire,
+                                    push_topk=push_topk)
+        elif check_push_wire(push_wire, push_topk) != "same":
             client.push_wire = push_wire       # an explicit client takes the optimizer's knob
+            client.push_topk = int(push_topk)
         self.client = client
         self.client.attach(self)
         self.client.init()

@@ -30,7 +30,7 @@ import torch
 import torch.distributed as dist
 
 from . import messaging as M
-from . import wire
+from . import wire, wire_topk
 from .links import warm_stream
 
 _LOG = logging.getLogger(__name__)
@@ -40,9 +40,11 @@ MX8_FLAVOURS = ("the local PS (LocalPSClient) and the central PS over gloo or RC
                 "(GlooPSClient, RcclPSClient)")
 
 
-def check_push_wire(push_wire: str) -> str:
-    if push_wire not in ("same", "mx8"):
-        raise ValueError(f"push_wire must be 'same' or 'mx8', got {push_wire!r}")
+def check_push_wire(push_wire: str, push_topk: int = wire_topk.K_DEFAULT) -> str:
+    """``push_topk``: K of the ``"topk"`` wire, checked on every wire."""
+    if push_wire not in ("same", "mx8", "topk"):
+        raise ValueError(f"push_wire must be 'same' or 'mx8' or 'topk', got {push_wire!r}")
+    wire_topk.check_k(push_topk)
     return push_wire
 
 
@@ -58,14 +60,18 @@ class _Pending:
 class PSClient:
     """Base class: owns staging buffers and the landing logic."""
 
-    # clients whose push can travel as a block-scaled 8-bit payload (wire8.py)
+    # clients whose push can travel as a block-scaled 8-bit payload (wire8.py) or as
+    # a sparse top-k payload (wire_topk.py): one worker's push reaches one server
     supports_mx8 = False
 
     def __init__(self, staleness: int = 1, pull_mode: str = "overwrite",
-                 wire_dtype: torch.dtype = torch.float32, push_wire: str = "same"):
+                 wire_dtype: torch.dtype = torch.float32, push_wire: str = "same",
+                 push_topk: int = wire_topk.K_DEFAULT):
         """``push_wire``: ``"same"`` pushes in ``wire_dtype``; ``"mx8"`` pushes the
         MXFP8 payload of :mod:`.wire8` and keeps the quantisation residual in the
-        accumulator (error feedback).  Pulls always use ``wire_dtype``."""
+        accumulator (error feedback); ``"topk"`` pushes the ``push_topk`` largest
+        entries of every 256-element block (:mod:`.wire_topk`) and keeps the rest
+        in the accumulator.  Pulls always use ``wire_dtype``."""
         if staleness < 0:
             raise ValueError("staleness must be >= 0")
         if pull_mode not in ("overwrite", "rebase"):
@@ -73,7 +79,8 @@ class PSClient:
         self.staleness = staleness
         self.pull_mode = pull_mode
         self.wire_dtype = wire_dtype
-        self.push_wire = check_push_wire(push_wire)
+        self.push_wire = check_push_wire(push_wire, push_topk)
+        self.push_topk = int(push_topk)
         self.pending: deque[_Pending] = deque()
         self.version = 0            # version of the PS params last landed
         self.pushes = 0
@@ -89,12 +96,14 @@ class PSClient:
 
     # -- wiring ------------------------------------------------------------
     def attach(self, opt):
-        if self.push_wire == "mx8" and not self.supports_mx8:
+        if self.push_wire != "same" and not self.supports_mx8:
+            name = "8-bit" if self.push_wire == "mx8" else "sparse"
             raise ValueError(
-                f"push_wire='mx8' is not supported by {type(self).__name__}: the 8-bit push "
-                f"wire runs on {MX8_FLAVOURS}")
+                f"push_wire={self.push_wire!r} is not supported by {type(self).__name__}: the "
+                f"{name} push wire runs on {MX8_FLAVOURS}")
         # pushes travel through this codec; pulls always in wire_dtype
-        self.push_codec = wire.MX8 if self.push_wire == "mx8" else wire.codec(self.wire_dtype)
+        self.push_codec = {"mx8": wire.MX8, "topk": wire.topk(self.push_topk)}.get(
+            self.push_wire) or wire.codec(self.wire_dtype)
         self.opt = opt
         self.arena = opt.arena
         self.device = self.arena.device

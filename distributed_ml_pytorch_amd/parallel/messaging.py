@@ -40,6 +40,26 @@ HEADER_LEN = 6
 MX8 = "mx8"
 
 _DTYPES = {0: torch.float32, 1: torch.bfloat16, 2: torch.float16, 3: MX8}
+
+# header dtype of a sparse block top-k push (parallel/wire_topk.py) at K slots per
+# block: code 16 + K, so the header carries K.  ``nelem`` stays the element count,
+# the payload is ``wire_topk.layout(nelem, K).nwords`` int32 words
+TOPK_CODE0 = 16
+
+
+def topk(k: int) -> str:
+    """The header dtype value of the top-k wire at ``k`` (1..32)."""
+    from .wire_topk import check_k
+
+    return f"topk{check_k(k)}"
+
+
+def topk_k(dtype) -> int:
+    """K of a top-k header dtype value, 0 for every other wire."""
+    return int(dtype[4:]) if isinstance(dtype, str) and dtype.startswith("topk") else 0
+
+
+_DTYPES.update({TOPK_CODE0 + k: f"topk{k}" for k in range(1, 33)})
 _DTYPE_CODES = {v: k for k, v in _DTYPES.items()}
 
 
@@ -142,7 +162,8 @@ def send_message(message_code, payload: torch.Tensor | None = None, dst: int = 0
                  nelem: int | None = None, dtype=None):
     """Fire-and-track send of a header (+ payload) to ``dst`` (default: the PS, rank 0).
     ``nelem`` / ``dtype``: what the header says when the payload is not one tensor
-    element per element (:data:`MX8`: uint8 bytes of ``nelem`` quantised elements).
+    element per element (:data:`MX8`: uint8 bytes of ``nelem`` quantised elements;
+    :func:`topk`: int32 words holding K entries of every 256 of ``nelem`` elements).
 
     Signature-compatible with the reference's ``send_message(code, payload)``
     call sites (Asynchronous.py:34,49,59); a ParameterRequest's payload is
@@ -171,6 +192,10 @@ def payload_buffer(nelem: int, dtype, device=None) -> torch.Tensor:
         from .wire8 import layout
 
         return torch.empty(layout(nelem)[2], dtype=torch.uint8, device=device)
+    if topk_k(dtype):
+        from .wire_topk import layout
+
+        return torch.empty(layout(nelem, topk_k(dtype))[1], dtype=torch.int32, device=device)
     return torch.empty(nelem, dtype=dtype, device=device)
 
 

@@ -43,7 +43,7 @@ import torch
 import torch.distributed as dist
 
 from . import messaging as M
-from . import wire
+from . import wire, wire_topk
 from .arena import FlatArena
 from .links import AppliedCount, PairGroupTransport, PairLinks, wait_on
 from .staleness import DeviceStaleLog, StalenessGate
@@ -77,7 +77,7 @@ class ParameterServer:
                  checkpoint_path: str | None = None, checkpoint_every: int = 0,
                  worker_timeout: float | None = None, delta_scale: str | float = "sum",
                  transport=None, trace_links: bool = False, stale_bound: int = 0,
-                 stale_policy: str = "off", delay_comp: float = 0.0):
+                 stale_policy: str = "off", delay_comp: float = 0.0, push_topk: int = 0):
         """``delta_scale``: factor on every pushed delta -- ``"sum"`` (1.0, the
         reference Downpour PS: /root/reference/asgd/optim/Asynchronous.py:48-55
         ships raw accumulated updates that the PS adds), ``"mean"`` (1 / #workers:
@@ -97,9 +97,15 @@ class ParameterServer:
         the worker's delta ``d`` as ``d - c * d*d * (shard - backup)``.  It composes
         with both policies (``damp``'s factor multiplies the scale).  A worker's
         pushes are uncompensated until its first reply after an initialisation or
-        a checkpoint load: backups are not checkpointed."""
+        a checkpoint load: backups are not checkpointed.
+
+        ``push_topk``: K of the sparse top-k push wire (:mod:`.wire_topk`) the
+        workers were started with, ``0`` = that wire is off.  Like every other wire
+        the server reserves its link rings and warms its kernels up front; a push
+        on this wire at another K, or while it is off, is an error."""
         if not dist.is_initialized():
             raise RuntimeError("ParameterServer needs torch.distributed to be initialised")
+        self.push_topk = wire_topk.check_k(push_topk) if push_topk else 0
         self.delay_comp = float(delay_comp)
         if not (0.0 <= self.delay_comp < float("inf")):
             raise ValueError(f"delay_comp must be finite and >= 0, got {delay_comp!r}")
@@ -203,13 +209,16 @@ class ParameterServer:
             self._warm_kernels()
 
     def _mx8_ok(self) -> bool:
-        """The MX8 kernels take whole float4 items (every model arena is a
-        multiple of 64 elements); the CPU path takes any length."""
+        """The MX8 and top-k kernels take whole float4 items (every model arena is
+        a multiple of 64 elements); the CPU path takes any length."""
         return self.device.type != "cuda" or self.numel % 4 == 0
 
     def _codecs(self):
         """The wires a worker may push on."""
-        return (wire.FP32, wire.BF16, wire.MX8) if self._mx8_ok() else (wire.FP32, wire.BF16)
+        if not self._mx8_ok():
+            return (wire.FP32, wire.BF16)
+        topk = (wire.topk(self.push_topk),) if self.push_topk else ()
+        return (wire.FP32, wire.BF16, wire.MX8, *topk)
 
     def _backup(self, worker) -> torch.Tensor | None:
         """``worker``'s backup row (delay compensation on)."""
@@ -267,6 +276,14 @@ class ParameterServer:
                                f"{self.numel} (model/arena layout mismatch)")
         if dtype == M.MX8 and not self._mx8_ok():
             raise RuntimeError(f"PS: an MX8 push needs a shard length that is a multiple "
+                               f"of 4 on the GPU, the shard has {self.numel}")
+        k = M.topk_k(dtype)
+        if k and k != self.push_topk:
+            raise RuntimeError(f"PS: worker {sender} pushed on the top-k wire at K = {k}, this "
+                               f"server was started with push_topk = {self.push_topk}"
+                               + (" (the top-k wire is off)" if not self.push_topk else ""))
+        if k and not self._mx8_ok():
+            raise RuntimeError(f"PS: a top-k push needs a shard length that is a multiple "
                                f"of 4 on the GPU, the shard has {self.numel}")
         nelem, padded, dtype = wire.codec(dtype).payload_shape(nelem)
         self.bytes_in += nelem * torch.empty(0, dtype=dtype).element_size()
@@ -422,6 +439,9 @@ class ParameterServer:
             if dtype == M.MX8:
                 raise RuntimeError(f"PS: worker {sender} sent parameters on the MX8 wire; only "
                                    "pushed deltas are quantised")
+            if M.topk_k(dtype):
+                raise RuntimeError(f"PS: worker {sender} sent parameters on the top-k wire; only "
+                                   "pushed deltas are sparsified")
             params, ready, slot = self._recv_payload(sender, nelem, dtype)
             if not self.initialized or self.init_policy == "last":
                 self._set(params, ready, slot)

@@ -1,19 +1,23 @@
-"""The wire formats of a push, as codecs: fp32, bf16 and MX8 (:mod:`.wire8`).
+"""The wire formats of a push, as codecs: fp32, bf16, MX8 (:mod:`.wire8`) and
+sparse block top-k (:mod:`.wire_topk`).
 
 Every client and server asks a codec how a push accumulator becomes a payload
 (``handoff``), how large the payload of ``n`` elements is and what its header
 says (``payload_shape``, ``header``), and how a payload lands in an fp32 master
-(``apply``; ``apply_dc`` with delay compensation, :func:`dc_delta`).  On the GPU these are the native kernels (``csrc/optim.hip``: one
-wire reader per format); on the CPU the torch expressions below, which the
-kernels match bit for bit (``tests/test_wire_codec_gpu.py``).  The codecs hold
-no state: :data:`FP32`, :data:`BF16` and :data:`MX8` are shared by everyone.
+(``apply``; ``apply_dc`` with delay compensation, :func:`dc_delta`).  On the GPU
+these are the native kernels (``csrc/optim.hip``: one wire reader per dense
+format, a scatter for top-k); on the CPU the torch expressions below, which the
+kernels match bit for bit (``tests/test_wire_codec_gpu.py``,
+``tests/test_wire_topk_gpu.py``).  The codecs hold
+no state: :data:`FP32`, :data:`BF16`, :data:`MX8` and the one :func:`topk` codec
+per K are shared by everyone.
 """
 from __future__ import annotations
 
 import torch
 
 from . import messaging as M
-from . import wire8
+from . import wire8, wire_topk
 
 
 def _native():
@@ -151,16 +155,117 @@ class _MX8:
             _apply_dc_cpu(master, bak, self.decode(payload, master.numel()), scale, c, factor)
 
 
+class TopK:
+    """Sparse block top-k payload (:mod:`.wire_topk`): ``k`` int32 words for every
+    256 elements.  One instance per K (:func:`topk`).  ``k=None`` is the reader of
+    an ``int32`` payload tensor whose K is not known beforehand: it consumes a
+    payload at the K its size gives (``numel / nblk``; a size that does not
+    divide is an error) and produces none."""
+
+    dtype = torch.int32
+
+    def __init__(self, k: int | None):
+        self.k = None if k is None else wire_topk.check_k(k)
+
+    @property
+    def header(self):
+        return M.topk(self._mine("header"))
+
+    def _mine(self, what: str) -> int:
+        if self.k is None:
+            raise ValueError(f"wire.TopK.{what}: the reader of a top-k payload has no K of its "
+                             "own; take the codec of a K (wire.topk(k))")
+        return self.k
+
+    def _k(self, payload: torch.Tensor, n: int) -> int:
+        """K of ``payload`` for ``n`` elements; it must be this codec's when it has one."""
+        if payload.dtype != torch.int32:
+            raise ValueError(f"wire.TopK: a top-k payload is int32 words, got {payload.dtype}")
+        k = wire_topk.k_of(payload.numel(), n)
+        if self.k is not None and k != self.k:
+            raise ValueError(f"wire.TopK: a payload at K = {k} reached the codec of K = {self.k}")
+        return k
+
+    def payload_shape(self, n: int):
+        nwords = wire_topk.layout(n, self._mine("payload_shape"))[1]    # no padding of its own
+        return nwords, nwords, torch.int32
+
+    def new_payload(self, n: int, device) -> torch.Tensor:
+        # zeroed once (an all-zero payload is the empty one); every hand-off rewrites all of it
+        buf = torch.empty(self.payload_shape(n)[0], dtype=torch.int32, device=device)
+        if buf.is_cuda:
+            _native().zero_(buf)
+        else:
+            buf.zero_()
+        return buf
+
+    def handoff(self, acc: torch.Tensor, buf: torch.Tensor):
+        """``buf = sparsify(acc)``, ``acc = residual``: what this push does not send
+        stays in the accumulator and travels with a later one."""
+        k = self._mine("handoff")
+        if acc.is_cuda:
+            _native().push_handoff_topk(acc, buf, k)
+        else:
+            payload, resid = wire_topk.sparsify(acc, k)
+            buf.copy_(payload)
+            acc.copy_(resid)
+
+    def decode(self, payload: torch.Tensor, n: int) -> torch.Tensor:
+        return wire_topk.densify(payload, n, self._k(payload, n))
+
+    def apply(self, master: torch.Tensor, payload: torch.Tensor, scale: float,
+              atomic: bool = False, factor=None):
+        """``master[addr] += scale [* factor] * value`` for every word of the payload;
+        every other element keeps its bits.  CPU: the product and the sum are two
+        separately rounded torch operations, what the kernels compute."""
+        k = self._k(payload, master.numel())
+        if master.is_cuda:
+            _native().ps_apply_topk(master, payload, None, scale, atomic, factor, k)
+        else:
+            at, val = wire_topk.entries(payload, master.numel(), k)
+            sc = _f32(scale)
+            if factor is not None:
+                sc = sc * _f32(factor)
+            p = sc * val
+            master[at] = master[at] + p
+
+    def apply_dc(self, master: torch.Tensor, bak: torch.Tensor, payload: torch.Tensor,
+                 scale: float, c: float, atomic: bool = False, factor=None):
+        """The delay-compensated apply on the touched elements, against ``bak[addr]``."""
+        k = self._k(payload, master.numel())
+        if master.is_cuda:
+            _native().ps_apply_dc_topk(master, payload, bak, None, scale, c, atomic, factor, k)
+        else:
+            at, val = wire_topk.entries(payload, master.numel(), k)
+            s = master[at]
+            _apply_dc_cpu(s, bak[at], val, scale, c, factor)
+            master[at] = s
+
+
 FP32, BF16, MX8 = _Dense(torch.float32), _Dense(torch.bfloat16), _MX8()
 _CODECS = {torch.float32: FP32, torch.bfloat16: BF16, M.MX8: MX8, torch.uint8: MX8}
+_TOPK_READER = TopK(None)       # of an int32 payload tensor; the dtype alone names no wire
+
+
+def topk(k: int) -> TopK:
+    """The codec of the top-k wire at ``k`` slots per block (one shared instance per K)."""
+    key = M.topk(k)
+    if key not in _CODECS:
+        _CODECS[key] = TopK(k)
+    return _CODECS[key]
 
 
 def codec(what):
     """The codec of a torch dtype, of a header's dtype field (:data:`.messaging.MX8`
-    included) or of a payload tensor (``uint8`` bytes are an MX8 payload)."""
+    and the :func:`.messaging.topk` values included) or of a payload tensor
+    (``uint8`` bytes are an MX8 payload, ``int32`` words a top-k payload)."""
+    if torch.is_tensor(what) and what.dtype == torch.int32:
+        return _TOPK_READER
     key = what.dtype if torch.is_tensor(what) else what
     if key == torch.float16 and key not in _CODECS:
         _CODECS[key] = _Dense(key)      # a CPU-only wire: the dense expressions in fp16
+    if M.topk_k(key):
+        return topk(M.topk_k(key))
     return _CODECS[key]
 
 
@@ -176,7 +281,7 @@ def warm_applies(master: torch.Tensor, codecs, scale: float, with_factor: bool,
     and that load waited for the work in flight: the first apply stalled every
     other link until the first receive had landed (tests/test_links_gpu.py).
     An all-zero payload leaves the master unchanged (MX8: codes 0 at scale
-    2^-127 add +0).  ``with_factor``: the damped forms too (policy "damp").
+    2^-127 add +0; top-k: every slot is empty).  ``with_factor``: the damped forms too (policy "damp").
     ``bak`` (one worker's backup) and ``dc``: the server compensates delays, so
     the compensated forms are launched as well, for the same reason -- their
     first launch must not happen during a transfer either (a zero delta gives a

@@ -84,7 +84,9 @@ class TrainConfig:
     staleness: int = 1
     pull_mode: str = "overwrite"
     wire_dtype: str = "fp32"
-    push_wire: str = "same"           # same | mx8 (parallel/wire8.py; local and central PS only)
+    push_wire: str = "same"           # same | mx8 (parallel/wire8.py) | topk (wire_topk.py);
+                                      # mx8 and topk: local and central PS only
+    push_topk: int = 8                # K of push_wire topk: entries per 256-element block, 1..32
     mode: str = "asgd"                # asgd | sync | single
     ps: str = "central"               # central | sharded | sharded_async | local
     payload: str = "auto"             # central PS payload transport: gloo | rccl | auto
@@ -185,6 +187,7 @@ class Worker:
                 okw.update(optimizer="adamw", **adam)
             if cfg.push_wire != "same":      # an explicit client takes the configured wire too
                 okw["push_wire"] = cfg.push_wire
+                okw["push_topk"] = cfg.push_topk
             self.opt = Asynchronous(params, lr=cfg.lr, n_push=cfg.n_push, n_pull=cfg.n_pull,
                                     model=self.model, client=client, momentum=cfg.momentum,
                                     weight_decay=cfg.weight_decay, **okw)
@@ -217,7 +220,8 @@ class Worker:
     def _make_client(self, ps_groups):
         cfg, info = self.cfg, self.info
         kw = dict(staleness=cfg.staleness, pull_mode=cfg.pull_mode,
-                  wire_dtype=_dtype(cfg.wire_dtype), push_wire=cfg.push_wire)
+                  wire_dtype=_dtype(cfg.wire_dtype), push_wire=cfg.push_wire,
+                  push_topk=cfg.push_topk)
         if cfg.ps == "local" or not info.is_distributed:
             return LocalPSClient(**kw)
         if cfg.ps == "sharded":
@@ -498,9 +502,10 @@ def check_delay_comp_config(cfg: TrainConfig, info: DistInfo, client=None):
 
 
 def check_push_wire_config(cfg: TrainConfig, client=None):
-    """The 8-bit push wire exists where one worker's push reaches one server:
-    the local PS and the central PS.  Anywhere else it is an error at start-up."""
-    if check_push_wire(cfg.push_wire) == "same":
+    """The 8-bit and the sparse top-k push wire exist where one worker's push
+    reaches one server: the local PS and the central PS.  Anywhere else they are
+    an error at start-up."""
+    if check_push_wire(cfg.push_wire, cfg.push_topk) == "same":
         return
     what = None
     if cfg.mode != "asgd":
@@ -510,8 +515,9 @@ def check_push_wire_config(cfg: TrainConfig, client=None):
     elif client is None and cfg.ps in ("sharded", "sharded_async"):
         what = f"--ps {cfg.ps}"
     if what:
-        raise ValueError(f"--push-wire mx8 is not supported with {what}: the 8-bit push wire "
-                         f"runs on {MX8_FLAVOURS}")
+        name = "8-bit" if cfg.push_wire == "mx8" else "sparse"
+        raise ValueError(f"--push-wire {cfg.push_wire} is not supported with {what}: the {name} "
+                         f"push wire runs on {MX8_FLAVOURS}")
 
 
 def _payload(cfg: TrainConfig, info: DistInfo) -> str:
@@ -533,7 +539,8 @@ def run_server(cfg: TrainConfig, info: DistInfo, ps_groups):
                              worker_timeout=cfg.ps_worker_timeout or None,
                              delta_scale=cfg.delta_scale, stale_bound=cfg.stale_bound,
                              stale_policy=cfg.stale_policy,
-                             delay_comp=delay_comp_coefficient(cfg))
+                             delay_comp=delay_comp_coefficient(cfg),
+                             push_topk=cfg.push_topk if cfg.push_wire == "topk" else 0)
     ps_path = _ps_resume_path(cfg)
     if ps_path:
         server.load_checkpoint(ps_path)

@@ -39,7 +39,8 @@ class VirtualWorkers:
         self.workers: list[Worker] = []
         self.streams = [torch.cuda.Stream(device) if self.cuda else None for _ in range(k)]
         kw = dict(staleness=cfg.staleness, pull_mode=cfg.pull_mode,
-                  wire_dtype=_dtype(cfg.wire_dtype), push_wire=cfg.push_wire)
+                  wire_dtype=_dtype(cfg.wire_dtype), push_wire=cfg.push_wire,
+                  push_topk=cfg.push_topk)
         for i in range(k):
             with self._on(i):
                 w = Worker(replace(cfg, seed=cfg.seed + i), DistInfo(device=device),
