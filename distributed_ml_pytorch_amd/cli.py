@@ -110,6 +110,15 @@ def build_parser() -> argparse.ArgumentParser:
                         "it last sent each worker and applies that worker's delta d as "
                         "d - c d*d (w_now - w_sent), c = LAMBDA / (lr * num-push); costs one "
                         "fp32 copy of the model per worker on the PS.  SGD only; 0 = off")
+    p.add_argument("--device-data", action="store_true", default=False,
+                   help="keep the dataset on the device as uint8 and assemble every batch with "
+                        "one native kernel (gather, crop / flip, normalise) straight into the "
+                        "step's input buffers: no host loader, no upload, no cast")
+    p.add_argument("--augment", default="none", choices=["none", "crop", "flip", "crop_flip"],
+                   help="--device-data: per-sample random crop (zero padding --crop-pad) and / "
+                        "or horizontal flip of the training batches")
+    p.add_argument("--crop-pad", type=int, default=4, metavar="P",
+                   help="--augment crop: zero padding of the random crop, 0..16")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log-dir", default="log")
     p.add_argument("--no-eval", action="store_true", default=False)
@@ -136,7 +145,8 @@ def config_from_args(a) -> TrainConfig:
         label_smoothing=a.label_smoothing, divergence_check=not a.no_divergence_check,
         deterministic=a.deterministic, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
         adam_eps=a.adam_eps, clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,
-        lr_min=a.lr_min, schedule_steps=a.schedule_steps)
+        lr_min=a.lr_min, schedule_steps=a.schedule_steps, device_data=a.device_data,
+        augment=a.augment, crop_pad=a.crop_pad)
 
 
 def main(argv=None):

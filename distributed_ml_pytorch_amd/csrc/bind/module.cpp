@@ -8,6 +8,7 @@ void bind_norm_pool(pybind11::module_& m);
 void bind_conv(pybind11::module_& m);
 void bind_gemm(pybind11::module_& m);
 void bind_transformer(pybind11::module_& m);
+void bind_data(pybind11::module_& m);
 }  // namespace dmp::bind
 
 PYBIND11_MODULE(_native, m) {
@@ -17,5 +18,6 @@ PYBIND11_MODULE(_native, m) {
   dmp::bind::bind_conv(m);
   dmp::bind::bind_gemm(m);
   dmp::bind::bind_transformer(m);
+  dmp::bind::bind_data(m);
   m.attr("arch") = "gfx950";
 }

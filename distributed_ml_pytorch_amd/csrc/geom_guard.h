@@ -73,5 +73,20 @@ inline bool rows_bytes_ok(int64_t elem, int64_t rows, int64_t ld) {
   return elem * rows * ld < kTwoGiB;
 }
 
+// device-resident uint8 NHWC dataset (data.hip): 32-bit BYTE offsets into the
+// n*h*w*c image bytes, an `int` sample count, 1..4 channels (the look-up table
+// the kernel keeps in LDS is [4][256])
+constexpr int64_t kDatasetMaxChannels = 4;
+constexpr int64_t kDatasetMaxPad = 16;
+inline bool dataset_ok(int64_t n, int64_t h, int64_t w, int64_t c) {
+  if (c < 1 || c > kDatasetMaxChannels || h < 1 || w < 1 || !fits_int(n)) return false;
+  return prod_lt(kTwoGiB, 1, n, h, w, c);
+}
+
+// one assembled batch: `count` bf16 NHWC images under 2 GiB, pad in range
+inline bool assemble_ok(int64_t count, int64_t h, int64_t w, int64_t c, int64_t pad) {
+  return pad >= 0 && pad <= kDatasetMaxPad && fits_int(count) && bf16_bytes_ok(count, h, w, c);
+}
+
 }  // namespace guard
 }  // namespace dmp

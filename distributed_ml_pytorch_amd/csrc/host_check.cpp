@@ -345,6 +345,29 @@ void check_mx8_layout() {
          "mx8 lengths out of range must be rejected, not wrapped");
 }
 
+// device-resident datasets (data.hip): the shipped sets fit, the 2 GiB / 2^31
+// edges and bad channel counts are rejected without wrapping
+void check_dataset_guard() {
+  using namespace dmp::guard;
+  EXPECT(dataset_ok(50000, 32, 32, 3) && dataset_ok(60000, 28, 28, 1) && dataset_ok(1, 1, 1, 4),
+         "CIFAR-10 / MNIST / one-pixel datasets fit");
+  EXPECT(dataset_ok(14263, 224, 224, 3) && !dataset_ok(14267, 224, 224, 3),
+         "ImageNet-shaped images: the 2 GiB edge");
+  EXPECT(dataset_ok((int64_t(1) << 31) - 1, 1, 1, 1) && !dataset_ok(int64_t(1) << 31, 1, 1, 1),
+         "dataset 2 GiB edge");
+  EXPECT(!dataset_ok(int64_t(1) << 31, 1, 1, 0) && !dataset_ok(4, 8, 8, 5) &&
+             !dataset_ok(4, 8, 8, 0) && !dataset_ok(-1, 8, 8, 3) && !dataset_ok(4, 0, 8, 3),
+         "dataset bad extents");
+  EXPECT(!dataset_ok(int64_t(1) << 30, int64_t(1) << 30, int64_t(1) << 30, 4),
+         "dataset product overflowing int64 must be rejected, not wrapped");
+  EXPECT(assemble_ok(512, 32, 32, 3, 4) && assemble_ok(0, 32, 32, 3, 0) &&
+             assemble_ok(128, 224, 224, 3, 16),
+         "assembled batches fit");
+  EXPECT(!assemble_ok(512, 32, 32, 3, 17) && !assemble_ok(512, 32, 32, 3, -1) &&
+             !assemble_ok(int64_t(1) << 20, 32, 32, 3, 4) && !assemble_ok(-1, 32, 32, 3, 4),
+         "assemble bad pad / oversize batch");
+}
+
 }  // namespace
 
 // DMP_ASAN_SELFTEST=asan|ubsan: a deliberate heap overflow / signed overflow,
@@ -432,6 +455,7 @@ int main(int argc, char** argv) {
          "bn_maxpool window");
   check_guards();
   check_mx8_layout();
+  check_dataset_guard();
   std::printf("host_check: %lld checks over %zu conv shapes, %d failed\n", g_checks, convs.size(),
               g_fail);
   return g_fail == 0 ? 0 : 1;

@@ -82,6 +82,19 @@ void launch_softmax_xent_f32(const float* logits, const int64_t* labels, float* 
                              int C, float grad_scale, float smoothing, int ignore_index,
                              hipStream_t s);
 
+// data.hip: batch assembler of a device-resident uint8 NHWC dataset
+// (utils/device_data.py): count samples data[index[b]] -> bf16 NHWC out_x through
+// the [C][256] bf16 lut, labels -> out_y, with a per-sample Philox crop (zero
+// padding `pad`) and flip; draws (null or [count][3] int8) receives (dy, dx, f).
+// path: -1 the staged (LDS) form where batch_assemble_staged says it applies,
+// 0 always the direct gather.
+bool batch_assemble_staged(const void* data, int H, int W, int C);
+void launch_batch_assemble(const uint8_t* data, const long long* labels, const uint16_t* lut,
+                           const int* index, int count, int N, int H, int W, int C,
+                           uint16_t* out_x, long long* out_y, signed char* draws, int pad,
+                           bool flip, unsigned long long seed, uint32_t epoch, int path,
+                           hipStream_t s);
+
 // bn.hip
 int bn_num_partials(long long M, int C);
 // inference-time BN folding into the producing conv (bn.hip): w16 = bf16(w * s),

@@ -43,6 +43,7 @@ from ..parallel.server import ParameterServer, make_ps_groups
 from ..parallel.staleness import check_policy
 from ..utils import checkpoint as ckpt
 from ..utils.data import get_datasets, make_loaders
+from ..utils.device_data import AUGMENTS, MAX_PAD, DeviceLoader, get_device_datasets
 from ..utils.metrics import IterationLog, StepTimer, Throughput, classification_report
 from .determinism import enable_determinism
 from .dist import DistInfo, preflight
@@ -109,6 +110,10 @@ class TrainConfig:
     label_smoothing: float = 0.0
     divergence_check: bool = True     # halt on non-finite parameters at each log interval
     deterministic: bool = False       # bitwise-reproducible debug mode (runtime/determinism.py)
+    device_data: bool = False         # dataset resident on the device as uint8, batches assembled
+                                      # by one native kernel per step (utils/device_data.py)
+    augment: str = "none"             # none | crop | flip | crop_flip (device_data only)
+    crop_pad: int = 4                 # zero padding of the random crop
     verbose: bool = True
     extra: dict = field(default_factory=dict)
 
@@ -129,6 +134,7 @@ class Worker:
         check_stale_config(cfg, info)
         check_push_wire_config(cfg, client)
         check_delay_comp_config(cfg, info, client)
+        check_device_data_config(cfg, info)
         if cfg.deterministic:
             cfg = self.cfg = enable_determinism(cfg)
         torch.manual_seed(cfg.seed + info.rank)
@@ -337,13 +343,24 @@ class Worker:
         dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.ddp.group)
         return bool(flag.item())
 
+    def static_inputs(self):
+        """The captured step's own input buffers ``(x, y)``, or ``None`` while no
+        graph is captured.  A batch written into them (utils/device_data.py) and
+        handed to :meth:`train_step` as these very tensors is replayed in place,
+        with no copy."""
+        if getattr(self, "use_graph", False) and self.graph is not None:
+            return self._gx, self._gy
+        return None
+
     def _graph_step(self, x, y, keep: bool = True):
         key = self._make_graph_key(x)
         if self.graph is None or key != self._graph_key:
             return self._capture(x, y)
         with self.timer.time("compute_launch"):
-            self._gx.copy_(x, non_blocking=True)
-            self._gy.copy_(y, non_blocking=True)
+            if x is not self._gx:
+                self._gx.copy_(x, non_blocking=True)
+            if y is not self._gy:
+                self._gy.copy_(y, non_blocking=True)
             self.graph.replay()
         self.opt.comm_step()
         self.step_idx += 1
@@ -460,6 +477,43 @@ def check_stale_config(cfg: TrainConfig, info: DistInfo):
             "(the local PS has one worker, the collective sharded PS is lock-step)")
 
 
+def check_device_data_config(cfg: TrainConfig, info: DistInfo):
+    """Augmentation exists in the device-resident data path only, and that path
+    writes bf16 batches on a GPU: anything else is an error at start-up."""
+    if cfg.augment not in AUGMENTS:
+        raise ValueError(f"unknown --augment {cfg.augment!r}; one of {sorted(AUGMENTS)}")
+    if cfg.augment != "none" and not cfg.device_data:
+        raise ValueError(f"--augment {cfg.augment} needs --device-data: the host loader applies "
+                         "no augmentation (random crop and flip run in the batch assembler)")
+    if not cfg.device_data:
+        return
+    if not 0 <= cfg.crop_pad <= MAX_PAD:
+        raise ValueError(f"--crop-pad must be in 0..{MAX_PAD}, got {cfg.crop_pad}")
+    on_gpu = cfg.cuda and info.device.type == "cuda"
+    if on_gpu and (cfg.deterministic or _dtype(cfg.dtype) != torch.bfloat16):
+        raise ValueError("--device-data on the GPU assembles bf16 batches: it cannot feed "
+                         f"--dtype {cfg.dtype}{' --deterministic' if cfg.deterministic else ''} "
+                         "(fp32 compute); use --dtype bf16 or the host loader")
+
+
+def make_device_loaders(cfg: TrainConfig, info: DistInfo, w: "Worker"):
+    """Train and test :class:`DeviceLoader` of a run with ``device_data``: the
+    train loader augments as configured and shards as the host path does (sync DP
+    by rank, every other mode the whole set in the rank's own order); the test
+    loader serves the test set in order, unaugmented."""
+    tr, te, source = get_device_datasets(cfg.dataset, cfg.data_dir, w.input_shape, w.num_classes,
+                                         cfg.n_train, cfg.n_test, cfg.seed, w.device)
+    crop, flip = AUGMENTS[cfg.augment]
+    shard = cfg.mode == "sync" and info.is_distributed
+    train = DeviceLoader(tr, cfg.batch_size, shuffle=True, drop_last=True,
+                         pad=cfg.crop_pad if crop else 0, flip=flip, seed=cfg.seed + info.rank,
+                         rank=info.rank if shard else 0, world=info.world_size if shard else 1,
+                         out_dtype=w.compute_dtype)
+    test = DeviceLoader(te, cfg.test_batch_size, shuffle=False, drop_last=False,
+                        out_dtype=w.compute_dtype)
+    return train, test, source + "+device"
+
+
 def delay_comp_coefficient(cfg: TrainConfig) -> float:
     """``c = lambda / (lr * n_push)``: what the servers take.  A push carries
     ``d = -lr * sum(g_i)`` of ``n_push`` steps; DC-ASGD's ``lambda * g*g`` becomes
@@ -557,6 +611,7 @@ def run_training(cfg: TrainConfig, info: DistInfo):
     check_stale_config(cfg, info)
     check_push_wire_config(cfg)
     check_delay_comp_config(cfg, info)
+    check_device_data_config(cfg, info)
     ps_groups = None
     central = cfg.mode == "asgd" and cfg.ps == "central" and info.is_distributed
     if central:
@@ -569,15 +624,21 @@ def run_training(cfg: TrainConfig, info: DistInfo):
     if central and info.rank == 0:
         return {"role": "ps", "preflight": pf, **run_server(cfg, info, ps_groups)}
     w = Worker(cfg, info, ps_groups)
-    tr, te, source = get_datasets(cfg.dataset, cfg.data_dir, w.input_shape, w.num_classes,
-                                  cfg.n_train, cfg.n_test, seed=cfg.seed)
-    # every worker sees the full dataset in its own shuffle order (reference has no
-    # DistributedSampler, main.py:27); sync-DP shards by rank instead.
-    if cfg.mode == "sync" and info.is_distributed:
-        idx = list(range(info.rank, len(tr), info.world_size))
-        tr = torch.utils.data.Subset(tr, idx)
-    train_loader, test_loader = make_loaders(tr, te, cfg.batch_size, cfg.test_batch_size,
-                                             shuffle_seed=cfg.seed + info.rank)
+    if cfg.device_data:
+        # the dataset lives on the device; the step replays as a graph whose input
+        # buffers the loader's kernel writes in place
+        train_loader, test_loader, source = make_device_loaders(cfg, info, w)
+        w.enable_graph(True)
+    else:
+        tr, te, source = get_datasets(cfg.dataset, cfg.data_dir, w.input_shape, w.num_classes,
+                                      cfg.n_train, cfg.n_test, seed=cfg.seed)
+        # every worker sees the full dataset in its own shuffle order (reference has no
+        # DistributedSampler, main.py:27); sync-DP shards by rank instead.
+        if cfg.mode == "sync" and info.is_distributed:
+            idx = list(range(info.rank, len(tr), info.world_size))
+            tr = torch.utils.data.Subset(tr, idx)
+        train_loader, test_loader = make_loaders(tr, te, cfg.batch_size, cfg.test_batch_size,
+                                                 shuffle_seed=cfg.seed + info.rank)
     core = getattr(w.opt, "core", None)
     if core is not None and cfg.lr_schedule == "warmup_cosine" and \
             not (cfg.schedule_steps or cfg.max_steps) and core.t == 0:
@@ -593,8 +654,10 @@ def run_training(cfg: TrainConfig, info: DistInfo):
             w.set_lr(base_lr / (epoch + 1))
         if cfg.verbose and info.rank <= 1:
             print(f"Training for epoch {epoch}", flush=True)
-        for i, (xb, yb) in enumerate(train_loader):
-            xb, yb = w.prepare(xb, yb)
+        batches = train_loader.iter_into(w.static_inputs) if cfg.device_data else train_loader
+        for i, (xb, yb) in enumerate(batches):
+            if not cfg.device_data:
+                xb, yb = w.prepare(xb, yb)
             loss, hits = w.train_step(xb, yb)
             meter.add(yb.numel())
             row = log.append(epoch, i, loss)
