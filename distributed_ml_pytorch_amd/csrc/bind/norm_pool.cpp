@@ -140,14 +140,14 @@ BnBwd bn_bwd_front(const Tensor& x, Tensor& dy, const optional<Tensor>& y,
 std::vector<Tensor> bn_bwd(Tensor x, Tensor dy, optional<Tensor> y, optional<Tensor> gamma,
                            Tensor stats, optional<Tensor> dgamma, optional<Tensor> dbeta,
                            bool relu, bool want_dres, optional<Tensor> slots,
-                           optional<Tensor> mask) {
+                           optional<Tensor> mask, bool batch_stats) {
   auto b = bn_bwd_front(x, dy, y, gamma, stats, dgamma, dbeta, relu, want_dres, mask);
   auto part = bn_slots(slots, b.C, b.fopt);
   auto coef = at::empty({3, b.C}, b.fopt);
   dmp::launch_bn_bwd(bf16(x), bf16(dy), b.y, ptr_or_null<float>(gamma), stats.data_ptr<float>(),
                      ptr_or_null<float>(dgamma), ptr_or_null<float>(dbeta), coef.data_ptr<float>(),
                      part.data_ptr<float>(), bf16(b.dx), bf16_or_null(b.dres), b.M, (int)b.C, relu,
-                     cur_stream(), b.mask);
+                     cur_stream(), b.mask, batch_stats);
   return b.result();
 }
 
@@ -446,7 +446,7 @@ void bind_norm_pool(pybind11::module_& m) {
   m.def("bn_bwd", &bn_bwd, "NHWC batchnorm(+residual)(+relu) backward", py::arg("x"),
         py::arg("dy"), py::arg("y"), py::arg("gamma"), py::arg("stats"), py::arg("dgamma"),
         py::arg("dbeta"), py::arg("relu"), py::arg("want_dres"), py::arg("slots") = py::none(),
-        py::arg("mask") = py::none());
+        py::arg("mask") = py::none(), py::arg("batch_stats") = true);
   m.def("relu_bwd", &relu_bwd, "ReLU backward from the saved output", py::arg("dy"), py::arg("y"),
         py::arg("out") = py::none());
   m.def("gap_fwd", &gap_fwd, "NHWC global average pool forward");

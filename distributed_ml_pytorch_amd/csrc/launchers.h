@@ -132,7 +132,7 @@ void launch_maxpool_bn_bwd_fold(const uint16_t* x, const uint16_t* dp, const uin
 void launch_bn_bwd(const uint16_t* x, const uint16_t* dy, const uint16_t* y, const float* gamma,
                    const float* stats, float* dgamma, float* dbeta, float* coef, float* part,
                    uint16_t* dx, uint16_t* dres, long long M, int C, bool relu, hipStream_t s,
-                   const uint8_t* mask = nullptr);
+                   const uint8_t* mask = nullptr, bool batch_stats = true);
 
 // pool.hip
 void launch_gap_fwd(const uint16_t* x, uint16_t* y, int N, int HW, int C, hipStream_t s);

@@ -51,7 +51,7 @@ def _bn_calls():
                             eps=1e-5, relu=True, want_mask=True, zero_buf=vec(SLOTS)),
         "bn_bwd": dict(x=x, dy=dy, y=None, gamma=vec(C), stats=vec(4 * C), dgamma=vec(C),
                        dbeta=vec(C), relu=True, want_dres=False, slots=vec(SLOTS),
-                       mask=vec(M * C // 8, torch.uint8)),
+                       mask=vec(M * C // 8, torch.uint8), batch_stats=True),
         "bn_bwd_fold": dict(x=x, dy=dy, y=None, gamma=vec(C), stats=vec(4 * C), dgamma=vec(C),
                             dbeta=vec(C), relu=True, want_dres=False, slots=vec(SLOTS),
                             mask=vec(M * C // 8, torch.uint8), zero_buf=vec(SLOTS)),

@@ -195,3 +195,195 @@ def test_gelu_floor(numel):
     dx_ref = ko.f64(dy) * ko.gelu_grad_ref(x)
     torch.testing.assert_close(ko.gelu_bwd_emul(x, dy), dx_ref, rtol=ko.GELU_DX_TOL / 3,
                                atol=ko.GELU_DX_TOL / 3)
+
+
+# ------------------------------------------------------- BatchNorm and pooling
+def _bn_case(shape, regime, relu, res, seed=0, training=True, emul=True, **kw):
+    N, C, H, W = shape
+    d = ko.bn_inputs(N, C, H, W, regime, seed)
+    args = dict(residual=d["res"] if res else None, relu=relu, dy=d["dy"], training=training,
+                running=None if training else (d["rm"], d["rv"]))
+    em = ko.bn_emul(d["x"], d["gamma"], d["beta"], **args, **kw) if emul else None
+    ref = ko.bn_ref(d["x"], d["gamma"], d["beta"], **args,
+                    y_stored=em["y"] if emul else None)
+    return d, em, ref
+
+
+def test_bn_inputs_regimes():
+    d = ko.bn_inputs(4, 40, 5, 5, "mixed")
+    x, gamma, beta = d["x"].double(), d["gamma"], d["beta"]
+    assert gamma.unique().numel() == 40 and beta.unique().numel() == 40
+    assert float(gamma[3]) == 0.0 and int((gamma == 0).sum()) == 1
+    assert bool((gamma[::7] < 0).all()) and int((gamma < 0).sum()) == 6
+    mean, std = x.mean(dim=(0, 2, 3)), x.std(dim=(0, 2, 3))
+    # the five base regimes inside every 8-channel vector
+    for c in range(40):
+        want = {0: (0.5, 2.0), 1: (16.0, 1.0), 2: (64.0, 1.0), 3: (0.0, 1e-3), 4: (250.0, 1e3)}[c % 5]
+        assert abs(float(mean[c]) - want[0]) < 0.5 * want[1] and 0.7 < float(std[c]) / want[1] < 1.3
+    c = ko.bn_inputs(2, 16, 3, 3, "const")["x"].double()
+    assert bool((c[:, 1::2] == 3.0).all()) and float(c[:, ::2].std()) > 1.0
+    n = ko.bn_inputs(2, 8, 9, 9, "near1024")["x"].double()
+    assert set(n.unique().tolist()) <= {1016.0, 1020.0, 1024.0, 1032.0}    # the bf16 grid there
+    assert ko.bn_inputs(30, 24, 0, 0, "std")["x"].shape == (30, 24)
+
+
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("relu,res", ko.BN_ACT)
+def test_bn_ref_matches_torch(training, relu, res):
+    """bn_ref against F.batch_norm in fp64: forward, running statistics (momentum
+    1) and every gradient, training and eval; eval-mode dx is k1 * dz."""
+    for shape in ((3, 16, 5, 4), (11, 8, 0, 0)):
+        d, _, ref = _bn_case(shape, "std", relu, res, training=training, emul=False)
+        x = ko.f64(d["x"]).requires_grad_(True)
+        r = ko.f64(d["res"]).requires_grad_(True)
+        g, b = ko.f64(d["gamma"]).requires_grad_(True), ko.f64(d["beta"]).requires_grad_(True)
+        rm, rv = ko.f64(d["rm"]).clone(), ko.f64(d["rv"]).clone()
+        y = F.batch_norm(x, rm, rv, g, b, training, 1.0, ko.BN_EPS)
+        if res:
+            y = y + r
+        if relu:
+            y = F.relu(y)
+        (y * ko.f64(d["dy"])).sum().backward()
+        close = lambda a, w: torch.testing.assert_close(a, w, rtol=1e-9, atol=1e-10)
+        close(ref["y"], y.detach())
+        close(ref["dx"], x.grad)
+        close(ref["dgamma"], g.grad)
+        close(ref["dbeta"], b.grad)
+        if res:
+            close(ref["dres"], r.grad)
+        if training:
+            close(ref["rmean"], rm)
+            close(ref["rvar"], rv)
+        else:
+            close(ref["dx"], ko._unmc(ko._mc(ref["dres"]) * ko.f64(d["gamma"]) * ref["invstd"],
+                                      d["x"]))
+
+
+def test_bn_emul_is_really_fp32():
+    """At |mean|/sigma = 64 two-moment fp32 statistics are off by about
+    2^-23 * 64^2 = 5e-4 on invstd: an emulation whose accumulator were silently
+    wider would sit orders of magnitude below.  One run over all M rows (the
+    literal worst order) is worse still, and grows with M."""
+    for cell in ("c24", "trip", "wrap"):
+        _, em, ref = _bn_case(ko.BN_CELLS[cell], "off64", False, False)
+        e = ko.bn_stat_errs(em["mean"], em["invstd"], ref)[1]
+        assert 1e-4 < e <= ko.BN_OFF64_INVSTD_TOL / 3, (cell, e)
+    _, em1, ref = _bn_case(ko.BN_CELLS["wrap"], "off64", False, False, chunk=None)
+    e1 = ko.bn_stat_errs(em1["mean"], em1["invstd"], ref)[1]
+    print(f"wrap off64 invstd error: one sequential run {e1:.2e}, 64-row runs {e:.2e}")
+    assert e1 > 10 * e
+    _, em16, ref16 = _bn_case(ko.BN_CELLS["trip"], "off16", False, False)
+    assert 3e-6 < ko.bn_stat_errs(em16["mean"], em16["invstd"], ref16)[1] < 1e-4
+
+
+def test_chan_checkers_see_one_bad_channel():
+    d, em, ref = _bn_case(ko.BN_CELLS["trip"], "mixed", True, True)
+    bad = {k: v.clone() if torch.is_tensor(v) else v for k, v in em.items()}
+    # channel 9 (a "loud" channel: tiny k1) takes channel 10's dx and y
+    bad["dx"][:, 9], bad["y"][:, 9] = em["dx"][:, 10], em["y"][:, 10]
+    e = ko.bn_errors(bad, ref, 162, True)
+    assert e["dx"] > 0.5 and e["y"] > 0.5
+    whole = float((ko.f64(bad["dx"]) - ref["dx"]).norm() / ref["dx"].norm())
+    assert whole < 1e-2                      # the whole-tensor norm does not notice
+    # gamma == 0 on channel 3: dx must be exactly zero there
+    assert float(ref["dx"][:, 3].abs().max()) == 0.0
+    bad = dict(em, dx=em["dx"].clone())
+    bad["dx"][0, 3, 0, 0] = 1e-3
+    with pytest.raises(AssertionError):
+        ko.bn_errors(bad, ref, 162, True)
+
+
+@pytest.mark.parametrize("cell,regime,relu,res", ko.bn_fold_cases())
+def test_bn_floor(cell, regime, relu, res):
+    """Training mode: the folded, unfolded and mode-1 GPU tests run these cells
+    (two steps: seeds 0 and 1)."""
+    shape = ko.BN_CELLS[cell]
+    for seed in (0, 1):
+        _, em, ref = _bn_case(shape, regime, relu, res, seed)
+        if not res:
+            em["dres"] = None
+        e = ko.bn_errors(em, ref, shape[0] * shape[2] * shape[3], relu)
+        ko.bn_assert(e, regime, 3.0, f"floor {cell} relu={relu} res={res} seed={seed}")
+
+
+@pytest.mark.parametrize("cell,regime,relu,res", ko.bn_eval_cases())
+def test_bn_eval_floor(cell, regime, relu, res):
+    shape = ko.BN_CELLS[cell]
+    _, em, ref = _bn_case(shape, regime, relu, res, training=False)
+    got = {k: em[k] for k in ("y", "dx", "dgamma", "dbeta")}
+    got["dres"] = em["dres"] if res else None
+    ko.bn_assert(ko.bn_errors(got, ref, shape[0] * shape[2] * shape[3], relu), regime, 3.0,
+                 f"eval floor {cell}")
+
+
+@pytest.mark.parametrize("M,C", ko.BN_1D)
+@pytest.mark.parametrize("regime", ["std", "off64"])
+@pytest.mark.parametrize("training", [True, False])
+def test_bn1d_floor(M, C, regime, training):
+    _, em, ref = _bn_case((M, C, 0, 0), regime, True, False, training=training)
+    got = {k: em[k] for k in ("y", "dx", "dgamma", "dbeta")}
+    ko.bn_assert(ko.bn_errors(got, ref, M, True), regime, 3.0, "1d floor")
+
+
+@pytest.mark.parametrize("shape", ko.BN_POOL_SHAPES)
+@pytest.mark.parametrize("regime", ko.BN_POOL_REGIMES)
+def test_bn_pool_floor(shape, regime):
+    """The fused stem: BN emulation -> pool of its stored y -> BN backward of the
+    gathered, bf16-rounded dz."""
+    d = ko.bn_inputs(*shape, regime)
+    fwd = ko.bn_emul(d["x"], d["gamma"], d["beta"], relu=True)
+    dp = ko.bn_pool_dp(shape)
+    yp, tap, dz, ref = ko.bn_pool_ref(d, fwd["y"], dp)
+    em = ko.bn_emul(d["x"], d["gamma"], d["beta"], relu=True, dy=ko.bf(dz), dy_sums=dz)
+    assert torch.equal(em["y"], fwd["y"])
+    em["dres"] = None
+    ko.bn_assert(ko.bn_errors(em, ref, shape[0] * shape[2] * shape[3], True), regime, 3.0,
+                 f"stem floor {shape}")
+
+
+POOL_KSP = [(2, 2, 0), (3, 2, 1), (3, 3, 0), (5, 2, 2), (2, 3, 0)]
+POOL_SHAPES = [(2, 8, 9, 7), (1, 16, 3, 3), (2, 6, 9, 7)]
+
+
+@pytest.mark.parametrize("k,s,p", POOL_KSP)
+@pytest.mark.parametrize("shape", POOL_SHAPES + [(2, 64, 15, 17)])
+def test_maxpool_ref_matches_torch(shape, k, s, p):
+    """First maximum in scan order on tie-heavy integers, against
+    F.max_pool2d(return_indices=True) and its autograd; all-negative inputs with
+    padding (a padded tap that won would show)."""
+    for lo, hi in ((-1, 2), (-3, -1)):
+        x, dy = ko.pool_int_inputs(shape, k, s, p, lo=lo, hi=hi)
+        y, tap, dx = ko.maxpool_ref(x, k, s, p, dy=dy)
+        xr = x.double().requires_grad_(True)
+        yr, ir = F.max_pool2d(xr, k, s, p, return_indices=True)
+        (yr * dy.double()).sum().backward()
+        assert torch.equal(y, yr.detach())
+        assert torch.equal(ko.maxpool_flat_index(tap, shape[2], shape[3], k, s, p), ir)
+        assert torch.equal(dx, xr.grad)
+        assert torch.equal(ko.bf(dx), dx)        # exact in bf16
+        # relu_in: tap 255 exactly where the window maximum is not positive
+        _, tap_r, dx_r = ko.maxpool_ref(x, k, s, p, relu_in=True, dy=dy)
+        assert torch.equal(tap_r == 255, ~(y > 0))
+        assert torch.equal(tap_r[y > 0], tap[y > 0])
+        xr.grad = None
+        (F.max_pool2d(F.relu(xr), k, s, p) * dy.double()).sum().backward()
+        assert torch.equal(dx_r, xr.grad)
+
+
+def test_gap_ref_matches_torch():
+    x = torch.randn(3, 8, 5, 6, dtype=torch.float64, requires_grad=True)
+    dy = torch.randn(3, 8, dtype=torch.float64)
+    x.mean(dim=(2, 3)).backward(dy)
+    y, dx = ko.gap_ref(x, dy)
+    torch.testing.assert_close(y, x.detach().mean(dim=(2, 3)))
+    torch.testing.assert_close(dx, x.grad)
+
+
+@pytest.mark.parametrize("HW", list(ko.GAP_HW))
+@pytest.mark.parametrize("C", ko.GAP_C)
+def test_gap_floor(HW, C):
+    for offset in ko.GAP_OFFSETS:
+        x, dy = ko.gap_inputs(HW, C, offset)
+        y, dx = ko.gap_ref(x, dy)
+        e_y, e_dx = ko.gap_errors(ko.bf(y), ko.bf(dx), x, dy)
+        assert e_y <= ko.GAP_Y_TOL / 3 and e_dx <= ko.GAP_DX_TOL / 3, (e_y, e_dx)
