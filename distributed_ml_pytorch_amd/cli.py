@@ -39,7 +39,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--port", type=str, default="29500")
     # ---- extensions -----------------------------------------------------------
     p.add_argument("--model", default="alexnet",
-                   help="mlp | lenet | alexnet | resnet18 | resnet34 | resnet50 | vit_b16 ...")
+                   help="mlp | lenet | alexnet | resnet18 | resnet34 | resnet50 | vit_b16 | vit_b16_384 | "
+                        "vit_tiny | vit_mini_long ...")
     p.add_argument("--num-classes", type=int, default=None)
     p.add_argument("--dataset", default="synthetic", help="synthetic | cifar10 | mnist")
     p.add_argument("--data-dir", default="./data")

@@ -9,7 +9,11 @@
 // backward writes dqkv in the qkv layout: no permute / contiguous copies, no
 // zero-filled select-backward buffers, no gradient adds, no materialised
 // [B, H, N, N] scores.  One workgroup per (batch, head): the whole key/value
-// (or query/dO) set of a head, <= 256 tokens, is staged once in LDS.
+// (or query/dO) set of a head, <= 256 tokens, is staged once in LDS.  These are
+// the RESIDENT kernels; longer sequences take the streaming kernels of
+// attention_stream.hip, which also holds the public launchers.  The fragment
+// helpers both share live in attn_prims.h, the shape -> LDS / grid plan in
+// attn_plan.h.
 //
 // MFMA 16x16x32 fragments (lane l, g = l / 16, l16 = l % 16):
 //   A (16 x 32): row l16, k = 8g .. 8g+7        B (32 x 16): col l16, k = 8g .. 8g+7
@@ -31,52 +35,14 @@
 // scaled scores (lse2), so P = exp2(s * scale * log2e - lse2) in the backward.
 #include <cstdlib>
 
-#include "common.h"
-#include "mfma_prims.h"
+#include "attn_plan.h"
+#include "attn_prims.h"
 
 namespace dmp {
 
 namespace {
 
-constexpr int kDH = 64;          // head dim
-constexpr int kRS = kDH + 8;     // row stride (elements) of row-major [token][64] LDS tiles
-constexpr int kMaxKB = 16;       // <= 256 tokens: 16 blocks of 16
-constexpr float kLn2 = 0.6931471805599453f;
-
-__device__ __forceinline__ bf16x8 pack8(const f32x4& lo, const f32x4& hi) {
-  bf16x8 r;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    r.v[i] = f2bf(lo[i]);
-    r.v[4 + i] = f2bf(hi[i]);
-  }
-  return r;
-}
-
-__device__ __forceinline__ bf16x8 ld16(const u16* p) { return *reinterpret_cast<const bf16x8*>(p); }
-
-__device__ __forceinline__ void st4(u16* p, const f32x4& v, float s) {
-  uint2 w;
-  w.x = (u32)f2bf(v[0] * s) | ((u32)f2bf(v[1] * s) << 16);
-  w.y = (u32)f2bf(v[2] * s) | ((u32)f2bf(v[3] * s) << 16);
-  *reinterpret_cast<uint2*>(p) = w;
-}
-
-// k-permuted operand read TRANSPOSED out of a row-major [token][kRS] image with
-// ds_read_b64_tr_b16: lane 16g + 4q + p addresses token row0 + 4g + q (and
-// row0 + 16 + 4g + q), head dims col0 + 4p .. col0 + 4p + 3; lane 16g + i gets
-// head dim col0 + i of those 4 tokens, i.e. A[i][k] for k = {4g..4g+3,
-// 16+4g..16+4g+3}.  The gather crosses lanes, so EXEC must be full: every call
-// site sits in wave-uniform control flow.
-__device__ __forceinline__ bf16x8 ld_tr_perm(const u16* img, int row0, int col0, int lane) {
-  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-  const u16* a = img + (row0 + 4 * g + q) * kRS + col0 + 4 * p;
-  const s16x4_t lo =
-      __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(a));
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) s16x4_t*)(a + 16 * kRS));
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
+constexpr int kMaxKB = kAttnResidentMax / 16;   // <= 256 tokens: 16 blocks of 16
 
 // Stage token rows [0, NP) of two [token][64] head slices into row-major LDS
 // images (stride kRS).  Rows >= N repeat row N-1 -- finite values that every
@@ -369,43 +335,29 @@ __global__ void __launch_bounds__(64 * NW) attn_bwd_dkv_kernel(
 }
 
 // ---------------------------------------------------------------- launchers
-int attention_max_tokens() { return 16 * kMaxKB; }
-int attention_head_dim() { return kDH; }
-
+// The resident route.  attention_stream.hip owns the public launchers
+// (launch_attention_fwd / _bwd): they plan (attn_plan.h) and dispatch here.
 namespace {
 constexpr int kFwdWaves = 8, kBwdWaves = 8;
-// two row-major [NP][kRS] bf16 images per kernel (+ lse2 / Di rows for dK,dV):
-// 64.5 KiB at N = 197, two workgroups per CU
-size_t fwd_lds(int N) {
-  const int NP = (N + 31) & ~31;
-  return (size_t)2 * NP * kRS * 2;
-}
-size_t dq_lds(int N) { return fwd_lds(N); }
-size_t dkv_lds(int N) {
-  const int NP = (N + 31) & ~31;
-  return fwd_lds(N) + (size_t)2 * NP * 4;
-}
-template <typename K>
-void allow_lds(K kernel, size_t bytes) {
-  if (bytes > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
+static_assert(kFwdWaves == kAttnStreamWaves && kBwdWaves == kAttnStreamWaves, "AttnPlan::waves");
 }  // namespace
 
-void launch_attention_fwd(const u16* qkv, u16* out, float* lse2, int B, int N, int H, float scale,
-                          hipStream_t s) {
-  const size_t lds = fwd_lds(N);
+// two row-major [NP][kRS] bf16 images per kernel (+ lse2 / Di rows for dK,dV):
+// 64.5 KiB at N = 197, two workgroups per CU (AttnPlan::lds_*)
+void launch_attention_resident_fwd(const AttnPlan& p, const u16* qkv, u16* out, float* lse2, int B,
+                                   int N, int H, float scale, hipStream_t s) {
+  const size_t lds = p.lds_fwd;
   const float sl2 = scale * 1.4426950408889634f;
   allow_lds(attn_fwd_kernel<kFwdWaves>, lds);
   hipLaunchKernelGGL(attn_fwd_kernel<kFwdWaves>, dim3(B * H), dim3(64 * kFwdWaves), lds, s, qkv,
                      out, lse2, N, H, sl2);
 }
 
-void launch_attention_bwd(const u16* qkv, const u16* out, const u16* dout, const float* lse2,
-                          u16* dqkv, int B, int N, int H, float scale, hipStream_t s) {
+void launch_attention_resident_bwd(const AttnPlan& p, const u16* qkv, const u16* out,
+                                   const u16* dout, const float* lse2, u16* dqkv, int B, int N,
+                                   int H, float scale, hipStream_t s) {
   const float sl2 = scale * 1.4426950408889634f;
-  const size_t l1 = dkv_lds(N), l2 = dq_lds(N);
+  const size_t l1 = p.lds_dkv, l2 = p.lds_dq;
   allow_lds(attn_bwd_dkv_kernel<kBwdWaves>, l1);
   allow_lds(attn_bwd_dq_kernel<kBwdWaves>, l2);
   hipLaunchKernelGGL(attn_bwd_dkv_kernel<kBwdWaves>, dim3(B * H), dim3(64 * kBwdWaves), l1, s, qkv,

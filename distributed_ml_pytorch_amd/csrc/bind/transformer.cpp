@@ -2,6 +2,8 @@
 // attention, dropout and the softmax cross-entropy loss.
 #include "util.h"
 
+#include "attn_plan.h"
+
 namespace dmp::bind {
 namespace {
 
@@ -41,8 +43,11 @@ std::vector<Tensor> softmax_xent(Tensor logits, Tensor labels, bool want_grad, d
 }
 
 // ------------------------------------------------------- fused attention
-// qkv: [B, N, 3*H*64] bf16 rows of the qkv projection ([B, N, 3, H, 64])
-void check_attn(const Tensor& qkv, int64_t heads, int64_t& B, int64_t& N, int64_t& D) {
+// qkv: [B, N, 3*H*64] bf16 rows of the qkv projection ([B, N, 3, H, 64]).
+// route (attn_plan.h): -1 automatic, 0 resident (N <= 256), 1 streaming
+// (N <= 4096); the planner refuses what no route takes.
+void check_attn(const Tensor& qkv, int64_t heads, int64_t route, int64_t& B, int64_t& N,
+                int64_t& D) {
   check_rows_bf16(qkv, "qkv");
   TORCH_CHECK(qkv.dim() == 3, "attention: qkv must be a [B, N, 3*D] tensor");
   B = qkv.size(0);
@@ -51,33 +56,46 @@ void check_attn(const Tensor& qkv, int64_t heads, int64_t& B, int64_t& N, int64_
   D = qkv.size(2) / 3;
   TORCH_CHECK(heads > 0 && D % heads == 0 && D / heads == dmp::attention_head_dim(),
               "attention: head dim must be ", dmp::attention_head_dim());
+  TORCH_CHECK(route >= dmp::kAttnAuto && route <= dmp::kAttnStream,
+              "attention: route must be -1 (automatic), 0 (resident) or 1 (streaming), got ", route);
   TORCH_CHECK(N >= 1 && N <= dmp::attention_max_tokens(), "attention: 1 <= N <= ",
               dmp::attention_max_tokens());
+  TORCH_CHECK(route != dmp::kAttnResident || N <= dmp::kAttnResidentMax,
+              "attention: the resident route takes N <= ", dmp::kAttnResidentMax, ", got ", N);
+  TORCH_CHECK(B >= 1 && dmp::plan_attention((int)N, (int)route, B * heads).ok,
+              "attention: no kernel plan for B ", B, ", N ", N, ", heads ", heads);
 }
 
 float attn_scale() { return 1.f / std::sqrt((float)dmp::attention_head_dim()); }
 
-std::vector<Tensor> attention_fwd(Tensor qkv, int64_t heads) {
+std::vector<Tensor> attention_fwd(Tensor qkv, int64_t heads, int64_t route) {
   int64_t B, N, D;
-  check_attn(qkv, heads, B, N, D);
+  check_attn(qkv, heads, route, B, N, D);
   auto out = at::empty({B, N, D}, qkv.options());
   auto lse = at::empty({B, heads, N}, qkv.options().dtype(at::kFloat));
   dmp::launch_attention_fwd(bf16(qkv), bf16(out), lse.data_ptr<float>(), (int)B, (int)N,
-                            (int)heads, attn_scale(), cur_stream());
+                            (int)heads, attn_scale(), (int)route, cur_stream());
   return {out, lse};
 }
 
-Tensor attention_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads) {
+Tensor attention_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t heads,
+                     int64_t route) {
   int64_t B, N, D;
-  check_attn(qkv, heads, B, N, D);
+  check_attn(qkv, heads, route, B, N, D);
   dout = dout.contiguous();
   check_vec(out, at::kBFloat16, B * N * D, "attention_bwd: out [B, N, D]");
   check_vec(dout, at::kBFloat16, B * N * D, "attention_bwd: dout [B, N, D]");
   TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == at::kFloat && lse.numel() == B * heads * N,
               "attention_bwd: bad lse");
   auto dqkv = at::empty_like(qkv);
+  // streaming route: rowsum(dO * O) per (b, head, token), written by the dQ
+  // kernel and read by the dK, dV kernel (every element written before it is read)
+  Tensor ws;
+  const int64_t nws = dmp::attention_bwd_workspace_floats((int)B, (int)N, (int)heads, (int)route);
+  if (nws > 0) ws = at::empty({nws}, qkv.options().dtype(at::kFloat));
   dmp::launch_attention_bwd(bf16(qkv), bf16(out), bf16(dout), lse.data_ptr<float>(), bf16(dqkv),
-                            (int)B, (int)N, (int)heads, attn_scale(), cur_stream());
+                            ptr_or_null<float>(ws), (int)B, (int)N, (int)heads, attn_scale(),
+                            (int)route, cur_stream());
   return dqkv;
 }
 
@@ -329,8 +347,11 @@ void bind_transformer(pybind11::module_& m) {
         py::arg("x"), py::arg("dy"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
         py::arg("dgamma"), py::arg("dbeta"), py::arg("slots") = py::none(),
         py::arg("dres") = py::none());
-  m.def("attention_fwd", &attention_fwd, "fused MHSA forward on qkv rows -> (out, lse2)");
-  m.def("attention_bwd", &attention_bwd, "fused MHSA backward -> dqkv (qkv layout)");
+  m.def("attention_fwd", &attention_fwd, "fused MHSA forward on qkv rows -> (out, lse2)",
+        py::arg("qkv"), py::arg("heads"), py::arg("route") = -1);
+  m.def("attention_bwd", &attention_bwd, "fused MHSA backward -> dqkv (qkv layout)",
+        py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("heads"),
+        py::arg("route") = -1);
   m.def("gelu_fwd", &gelu_fwd, "tanh-GELU forward");
   m.def("gelu_bwd", &gelu_bwd, "tanh-GELU backward");
   m.def("softmax_fwd", &softmax_fwd, "scaled row softmax forward");

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "geom_guard.h"
+#include "attn_plan.h"
 #include "halo_plan.h"
 #include "launchers.h"
 
@@ -368,6 +369,67 @@ void check_dataset_guard() {
          "assemble bad pad / oversize batch");
 }
 
+// attention plans (attn_plan.h) over every token count either route takes, the
+// edges that must be refused, and batch * heads products up to the grid limit
+void check_attention_plans() {
+  using namespace dmp;
+  for (int N = 1; N <= kAttnStreamMax + 1; ++N) {
+    for (int route = kAttnAuto; route <= kAttnStream; ++route) {
+      const AttnPlan p = plan_attention(N, route, 16 * 12);
+      const bool want = route == kAttnResident ? N <= kAttnResidentMax : N <= kAttnStreamMax;
+      EXPECT(p.ok == want, "N %d route %d: ok %d", N, route, p.ok);
+      if (!p.ok) continue;
+      EXPECT(p.route == (route == kAttnAuto ? (N <= kAttnResidentMax ? kAttnResident : kAttnStream)
+                                            : route),
+             "N %d request %d -> route %d", N, route, p.route);
+      // blocks x block size and tiles x tile size cover N, the last of each is not empty
+      EXPECT((long long)p.q_blocks * p.q_block >= N && (long long)(p.q_blocks - 1) * p.q_block < N &&
+                 (long long)p.k_blocks * p.k_block >= N && (long long)(p.k_blocks - 1) * p.k_block < N,
+             "N %d: blocks %d x %d, %d x %d", N, p.q_blocks, p.q_block, p.k_blocks, p.k_block);
+      EXPECT((long long)p.k_tiles * p.k_tile >= N && (long long)(p.k_tiles - 1) * p.k_tile < N &&
+                 (long long)p.q_tiles * p.q_tile >= N && (long long)(p.q_tiles - 1) * p.q_tile < N,
+             "N %d: tiles %d x %d, %d x %d", N, p.k_tiles, p.k_tile, p.q_tiles, p.q_tile);
+      EXPECT(p.q_block == kAttnStrip * p.waves || p.route == kAttnResident, "N %d: strips", N);
+      EXPECT(p.k_tile % 32 == 0 && p.q_tile % 32 == 0, "N %d: tiles of whole k-step pairs", N);
+      const size_t stage = attn_image_pair_bytes(p.k_tile);
+      EXPECT(p.lds_fwd == p.stages * stage && p.lds_dq == p.lds_fwd &&
+                 p.lds_dkv == p.stages * (attn_image_pair_bytes(p.q_tile) + (size_t)8 * p.q_tile),
+             "N %d: lds %zu %zu %zu", N, p.lds_fwd, p.lds_dq, p.lds_dkv);
+      EXPECT(p.lds_fwd <= (size_t)kAttnLdsLimit && p.lds_dkv <= (size_t)kAttnLdsLimit,
+             "N %d: %zu B of LDS", N, p.lds_dkv);
+      // two workgroups per CU on the streaming route
+      EXPECT(p.route == kAttnResident || 2 * p.lds_dkv <= (size_t)kAttnLdsLimit, "N %d", N);
+      EXPECT(p.grid_fwd == 16LL * 12 * p.q_blocks && p.grid_dq == p.grid_fwd &&
+                 p.grid_dkv == 16LL * 12 * p.k_blocks,
+             "N %d: grids %lld %lld", N, p.grid_fwd, p.grid_dkv);
+    }
+  }
+  for (int route = kAttnAuto; route <= kAttnStream; ++route) {
+    EXPECT(!plan_attention(0, route).ok && !plan_attention(-1, route).ok &&
+               !plan_attention(kAttnStreamMax + 1, route).ok &&
+               !plan_attention(0x7fffffff, route).ok,
+           "route %d: N out of range accepted", route);
+    EXPECT(!plan_attention(197, route, 0).ok && !plan_attention(197, route, -3).ok &&
+               !plan_attention(197, route, 1LL << 31).ok && !plan_attention(197, route, 1LL << 62).ok,
+           "route %d: bad batch * heads accepted", route);
+  }
+  EXPECT(!plan_attention(197, 2).ok && !plan_attention(197, -2).ok, "unknown route accepted");
+  EXPECT(!plan_attention(257, kAttnResident).ok && plan_attention(256, kAttnResident).ok,
+         "resident route cap");
+  // the grid limit: 32 blocks at 4096 tokens
+  EXPECT(plan_attention(4096, kAttnStream, 0x7fffffffLL / 32).ok &&
+             !plan_attention(4096, kAttnStream, 0x7fffffffLL / 32 + 1).ok &&
+             plan_attention(256, kAttnAuto, 0x7fffffffLL).ok,
+         "grid past 2^31 - 1 must be refused, not wrapped");
+  EXPECT(attention_max_tokens() == kAttnStreamMax && attn_plan_max_tokens() == kAttnStreamMax,
+         "attention cap");
+  EXPECT(attention_bwd_workspace_floats(16, 577, 12, kAttnAuto) == 16LL * 12 * 577 &&
+             attention_bwd_workspace_floats(16, 197, 12, kAttnAuto) == 0 &&
+             attention_bwd_workspace_floats(16, 197, 12, kAttnStream) == 16LL * 12 * 197 &&
+             attention_bwd_workspace_floats(16, 4097, 12, kAttnAuto) == 0,
+         "attention backward workspace");
+}
+
 }  // namespace
 
 // DMP_ASAN_SELFTEST=asan|ubsan: a deliberate heap overflow / signed overflow,
@@ -456,6 +518,7 @@ int main(int argc, char** argv) {
   check_guards();
   check_mx8_layout();
   check_dataset_guard();
+  check_attention_plans();
   std::printf("host_check: %lld checks over %zu conv shapes, %d failed\n", g_checks, convs.size(),
               g_fail);
   return g_fail == 0 ? 0 : 1;

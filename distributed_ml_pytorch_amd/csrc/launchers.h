@@ -266,14 +266,18 @@ void launch_conv_small_wgrad(const uint16_t* dy, const uint16_t* x, int xbytes, 
                              float* dw, float* ws, int B, int H, int W, int CI, int OH, int OW,
                              int CO, int R, int S, int stride, int pad, hipStream_t s);
 
-// attention.hip: fused MHSA on [B, N, 3, H, 64] qkv rows (ViT)
+// attention.hip, attention_stream.hip: fused MHSA on [B, N, 3, H, 64] qkv rows
+// (ViT).  route (attn_plan.h): -1 automatic (resident up to 256 tokens, streaming
+// above), 0 resident, 1 streaming; the caller has checked plan_attention(N, route).
 int attention_max_tokens();
 int attention_head_dim();
 void launch_attention_fwd(const uint16_t* qkv, uint16_t* out, float* lse2, int B, int N, int H,
-                          float scale, hipStream_t s);
+                          float scale, int route, hipStream_t s);
+// fp32 elements of the backward's workspace `ws` (uninitialised; 0: none, ws may be null)
+long long attention_bwd_workspace_floats(int B, int N, int H, int route);
 void launch_attention_bwd(const uint16_t* qkv, const uint16_t* out, const uint16_t* dout,
-                          const float* lse2, uint16_t* dqkv, int B, int N, int H, float scale,
-                          hipStream_t s);
+                          const float* lse2, uint16_t* dqkv, float* ws, int B, int N, int H,
+                          float scale, int route, hipStream_t s);
 
 // linear.hip: bias gradient out[n] += sum_m dy[m][n] (bf16 dy, fp32 out)
 int colsum_num_slots();

@@ -3,7 +3,7 @@ from __future__ import annotations
 
 from .cnn import MLP, AlexNet, LeNet
 from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101
-from .vit import VisionTransformer, vit_b16, vit_tiny
+from .vit import VisionTransformer, vit_b16, vit_mini_long, vit_tiny
 
 # name -> (constructor, input shape (C,H,W), num_classes)
 REGISTRY = {
@@ -16,7 +16,9 @@ REGISTRY = {
     "resnet50_cifar": (lambda nc=10: resnet50(nc, stem="cifar"), (3, 32, 32), 10),
     "resnet101": (lambda nc=1000: resnet101(nc, stem="imagenet"), (3, 224, 224), 1000),
     "vit_b16": (lambda nc=1000: vit_b16(nc), (3, 224, 224), 1000),
+    "vit_b16_384": (lambda nc=1000: vit_b16(nc, image_size=384), (3, 384, 384), 1000),
     "vit_tiny": (lambda nc=10: vit_tiny(nc), (3, 32, 32), 10),
+    "vit_mini_long": (lambda nc=10: vit_mini_long(nc), (3, 80, 80), 10),
 }
 
 
@@ -33,4 +35,4 @@ def build_model(name: str, num_classes: int | None = None):
 
 
 __all__ = ["MLP", "AlexNet", "LeNet", "ResNet", "resnet18", "resnet34", "resnet50", "resnet101",
-           "VisionTransformer", "vit_b16", "vit_tiny", "REGISTRY", "build_model"]
+           "VisionTransformer", "vit_b16", "vit_mini_long", "vit_tiny", "REGISTRY", "build_model"]

@@ -155,3 +155,11 @@ def vit_tiny(num_classes: int = 10, image_size: int = 32, patch: int = 4) -> Vis
     """Small ViT for CPU tests and CIFAR-shaped smoke runs."""
     return VisionTransformer(image_size=image_size, patch=patch, dim=64, depth=2, heads=4,
                              num_classes=num_classes)
+
+
+def vit_mini_long(num_classes: int = 10) -> VisionTransformer:
+    """80 x 80 images in 4 x 4 patches: 401 tokens, head dim 64.  The smallest
+    model whose step runs the streaming attention kernels (more than 256
+    tokens, ``csrc/attention_stream.hip``); for tests and smoke runs."""
+    return VisionTransformer(image_size=80, patch=4, dim=128, depth=2, heads=2,
+                             num_classes=num_classes)

@@ -854,19 +854,32 @@ class _ScaledSoftmax(Function):
         return native().softmax_bwd(p, dp, float(ctx.scale)), None
 
 
+# most tokens the fused attention takes (csrc/attn_plan.h: resident kernels up to
+# 256, streaming kernels up to 4096)
+ATTENTION_MAX_TOKENS = 4096
+
+
+def attention_route() -> int:
+    """Route request of the fused attention bindings: -1 automatic (resident up
+    to 256 tokens, streaming above); ``DMP_ATTN_STREAM=1`` forces the streaming
+    kernels at every token count (A/Bs of the two routes at <= 256 tokens)."""
+    return 1 if os.environ.get("DMP_ATTN_STREAM", "0") == "1" else -1
+
+
 class _FusedQKVAttention(Function):
     @staticmethod
-    def forward(ctx, qkv, heads):
+    def forward(ctx, qkv, heads, route=-1):
         qkv = qkv.contiguous()
-        out, lse = native().attention_fwd(qkv, int(heads))
+        out, lse = native().attention_fwd(qkv, int(heads), int(route))
         ctx.save_for_backward(qkv, out, lse)
         ctx.heads = int(heads)
+        ctx.route = int(route)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         qkv, out, lse = ctx.saved_tensors
-        return native().attention_bwd(qkv, out, dout, lse, ctx.heads), None
+        return native().attention_bwd(qkv, out, dout, lse, ctx.heads, ctx.route), None, None
 
 
 def fused_attention_supported(qkv, heads: int) -> bool:
@@ -874,22 +887,25 @@ def fused_attention_supported(qkv, heads: int) -> bool:
         return False
     D = qkv.shape[-1] // 3
     return (qkv.shape[-1] % 3 == 0 and D % heads == 0 and D // heads == 64
-            and 1 <= qkv.shape[1] <= 256)
+            and 1 <= qkv.shape[1] <= ATTENTION_MAX_TOKENS)
 
 
 def attention_qkv(qkv, heads: int):
     """Multi-head self-attention straight from the qkv projection rows.
 
     ``qkv``: [B, N, 3*D] (= [B, N, 3, heads, D/heads]); returns [B, N, D] (the
-    proj Linear's input rows).  On GPU (head dim 64, N <= 256) this is the
-    fused MFMA kernel pair of ``csrc/attention.hip``: scores never leave the
-    chip and the backward writes d(qkv) in place of the qkv layout (no
-    permute copies, zero fills or gradient adds).  Elsewhere: SDPA.
+    proj Linear's input rows).  On GPU (head dim 64, bf16, N <= 4096) this is a
+    fused MFMA kernel set: up to 256 tokens the resident kernels of
+    ``csrc/attention.hip`` (a head's keys and values staged once), above them
+    the streaming kernels of ``csrc/attention_stream.hip`` (key / query tiles
+    through LDS, online softmax).  Scores never leave the chip and the backward
+    writes d(qkv) in place of the qkv layout (no permute copies, zero fills or
+    gradient adds).  Elsewhere: SDPA.
     """
     B, N, three_d = qkv.shape
     D = three_d // 3
     if fused_attention_supported(qkv, heads):
-        return _FusedQKVAttention.apply(qkv, heads)
+        return _FusedQKVAttention.apply(qkv, heads, attention_route())
     q, k, v = qkv.view(B, N, 3, heads, D // heads).permute(2, 0, 3, 1, 4)
     o = attention(q, k, v)
     return o.transpose(1, 2).reshape(B, N, D)
@@ -897,7 +913,7 @@ def attention_qkv(qkv, heads: int):
 
 def attention(q, k, v):
     """softmax(q k^T / sqrt(d)) v over [B, H, N, d]: the geometries the fused
-    kernel does not take (head dim != 64, more than 256 tokens).
+    kernels do not take (head dim != 64, more than 4096 tokens, fp32).
 
     The two batched GEMMs are library GEMMs (hipBLASLt via ``torch.matmul``), so
     on the GPU this runs only in the explicit stock oracle mode (``ops._policy``);
@@ -906,7 +922,7 @@ def attention(q, k, v):
     scale = q.shape[-1] ** -0.5
     stock_gpu("attention (torch.matmul / SDPA)", q,
               reason=f"head dim {q.shape[-1]}, {k.shape[-2]} tokens, {q.dtype}: the fused "
-                     "kernel takes head dim 64, <= 256 tokens, bf16")
+                     f"kernels take head dim 64, <= {ATTENTION_MAX_TOKENS} tokens, bf16")
     if q.is_cuda and q.dtype == torch.bfloat16 and k.shape[-2] <= 1024:
         s = torch.matmul(q, k.transpose(-1, -2))
         p = _ScaledSoftmax.apply(s, scale)
