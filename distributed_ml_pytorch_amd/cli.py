@@ -120,6 +120,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "or horizontal flip of the training batches")
     p.add_argument("--crop-pad", type=int, default=4, metavar="P",
                    help="--augment crop: zero padding of the random crop, 0..16")
+    p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
+                   help="--device-data: Mixup of the training batches, lam ~ Beta(ALPHA, ALPHA) "
+                        "per batch, blended in the batch assembler (0 = off)")
+    p.add_argument("--cutmix", type=float, default=0.0, metavar="ALPHA",
+                   help="--device-data: CutMix of the training batches, box area from "
+                        "Beta(ALPHA, ALPHA) per batch (0 = off)")
+    p.add_argument("--mix-prob", type=float, default=1.0,
+                   help="probability that a batch is mixed at all")
+    p.add_argument("--mix-switch-prob", type=float, default=0.5,
+                   help="with --mixup and --cutmix both on: probability of CutMix for a batch")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log-dir", default="log")
     p.add_argument("--no-eval", action="store_true", default=False)
@@ -147,7 +157,8 @@ def config_from_args(a) -> TrainConfig:
         deterministic=a.deterministic, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
         adam_eps=a.adam_eps, clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,
         lr_min=a.lr_min, schedule_steps=a.schedule_steps, device_data=a.device_data,
-        augment=a.augment, crop_pad=a.crop_pad)
+        augment=a.augment, crop_pad=a.crop_pad, mixup=a.mixup, cutmix=a.cutmix,
+        mix_prob=a.mix_prob, mix_switch_prob=a.mix_switch_prob)
 
 
 def main(argv=None):

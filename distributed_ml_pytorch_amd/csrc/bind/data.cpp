@@ -21,9 +21,10 @@ void check_out_x(const Tensor& x, int64_t count, int64_t C, int64_t H, int64_t W
   TORCH_CHECK(aligned(x, 2), "batch_assemble: out_x must be 2-byte aligned");
 }
 
-void batch_assemble(Tensor data, Tensor labels, Tensor lut, Tensor index, int64_t count,
-                    Tensor out_x, Tensor out_y, optional<Tensor> draws, int64_t pad, bool flip,
-                    uint64_t seed, int64_t epoch, int64_t path) {
+// the tensor and range checks both forms of the assembler share
+void check_assemble(const Tensor& data, const Tensor& labels, const Tensor& lut,
+                    const Tensor& index, int64_t count, const Tensor& out_x, const Tensor& out_y,
+                    const optional<Tensor>& draws, int64_t pad, int64_t epoch, int64_t path) {
   TORCH_CHECK(data.is_cuda() && data.scalar_type() == at::kByte && data.dim() == 4 &&
                   data.is_contiguous(),
               "batch_assemble: data must be a contiguous uint8 [N, H, W, C] GPU tensor");
@@ -61,11 +62,48 @@ void batch_assemble(Tensor data, Tensor labels, Tensor lut, Tensor index, int64_
                 data.device(), ", got one on ", t->device());
   TORCH_CHECK(!has(draws) || draws->device() == data.device(),
               "batch_assemble: draws must be on ", data.device());
+}
+
+void batch_assemble(Tensor data, Tensor labels, Tensor lut, Tensor index, int64_t count,
+                    Tensor out_x, Tensor out_y, optional<Tensor> draws, int64_t pad, bool flip,
+                    uint64_t seed, int64_t epoch, int64_t path) {
+  check_assemble(data, labels, lut, index, count, out_x, out_y, draws, pad, epoch, path);
+  const int64_t N = data.size(0), H = data.size(1), W = data.size(2), C = data.size(3);
   dmp::launch_batch_assemble(data.data_ptr<uint8_t>(), i64(labels), bf16(lut),
                              index.data_ptr<int>(), (int)count, (int)N, (int)H, (int)W, (int)C,
                              bf16(out_x), i64(out_y), ptr_or_null<signed char>(draws), (int)pad,
                              flip, (unsigned long long)seed, (uint32_t)epoch, (int)path,
                              cur_stream());
+}
+
+// Mixup / CutMix form: row b blended with row count - 1 - b (data.hip)
+void batch_assemble_mix(Tensor data, Tensor labels, Tensor lut, Tensor index, int64_t count,
+                        Tensor out_x, Tensor out_y, Tensor out_y2, Tensor out_lam,
+                        optional<Tensor> draws, int64_t pad, bool flip, uint64_t seed,
+                        int64_t epoch, double pix_lam, double label_lam, int64_t y0, int64_t y1,
+                        int64_t x0, int64_t x1, int64_t path) {
+  check_assemble(data, labels, lut, index, count, out_x, out_y, draws, pad, epoch, path);
+  const int64_t N = data.size(0), H = data.size(1), W = data.size(2), C = data.size(3);
+  TORCH_CHECK(out_y2.is_cuda() && out_y2.scalar_type() == at::kLong && out_y2.is_contiguous() &&
+                  out_y2.numel() >= count && out_y2.device() == data.device(),
+              "batch_assemble_mix: out_y2 must be a contiguous int64 tensor of >= ", count,
+              " elements on ", data.device());
+  TORCH_CHECK(out_lam.is_cuda() && out_lam.scalar_type() == at::kFloat &&
+                  out_lam.is_contiguous() && out_lam.numel() >= count &&
+                  out_lam.device() == data.device(),
+              "batch_assemble_mix: out_lam must be a contiguous float32 tensor of >= ", count,
+              " elements on ", data.device());
+  TORCH_CHECK(dmp::guard::mix_ok(H, W, y0, y1, x0, x1, pix_lam, label_lam),
+              "batch_assemble_mix: the box must satisfy 0 <= y0 <= y1 <= ", H,
+              " and 0 <= x0 <= x1 <= ", W, " and pix_lam, label_lam must lie in [0, 1]; got box (",
+              y0, ", ", y1, ", ", x0, ", ", x1, "), pix_lam ", pix_lam, ", label_lam ", label_lam);
+  dmp::launch_batch_assemble_mix(data.data_ptr<uint8_t>(), i64(labels), bf16(lut),
+                                 index.data_ptr<int>(), (int)count, (int)N, (int)H, (int)W, (int)C,
+                                 bf16(out_x), i64(out_y), i64(out_y2), out_lam.data_ptr<float>(),
+                                 ptr_or_null<signed char>(draws), (int)pad, flip,
+                                 (unsigned long long)seed, (uint32_t)epoch, (float)pix_lam,
+                                 (float)label_lam, (int)y0, (int)y1, (int)x0, (int)x1, (int)path,
+                                 cur_stream());
 }
 
 bool batch_assemble_is_staged(Tensor data) {
@@ -82,6 +120,14 @@ void bind_data(pybind11::module_& m) {
         py::arg("data_u8"), py::arg("labels"), py::arg("lut"), py::arg("index_i32"),
         py::arg("count"), py::arg("out_x"), py::arg("out_y"), py::arg("draws"), py::arg("pad"),
         py::arg("flip"), py::arg("seed"), py::arg("epoch"), py::arg("path") = -1);
+  m.def("batch_assemble_mix", &batch_assemble_mix,
+        "batch_assemble with Mixup / CutMix of row b and row count - 1 - b; also writes the "
+        "partner's labels and the label weight",
+        py::arg("data_u8"), py::arg("labels"), py::arg("lut"), py::arg("index_i32"),
+        py::arg("count"), py::arg("out_x"), py::arg("out_y"), py::arg("out_y2"),
+        py::arg("out_lam"), py::arg("draws"), py::arg("pad"), py::arg("flip"), py::arg("seed"),
+        py::arg("epoch"), py::arg("pix_lam"), py::arg("label_lam"), py::arg("y0"), py::arg("y1"),
+        py::arg("x0"), py::arg("x1"), py::arg("path") = -1);
   m.def("batch_assemble_is_staged", &batch_assemble_is_staged,
         "whether batch_assemble stages this dataset's images through LDS");
 }

@@ -42,6 +42,47 @@ std::vector<Tensor> softmax_xent(Tensor logits, Tensor labels, bool want_grad, d
   return {loss, hits, dlogits};
 }
 
+// two-target form: per row lam * CE(labels) + (1 - lam) * CE(labels2), the
+// targets and the weight read from memory (one captured graph, any mix)
+std::vector<Tensor> softmax_xent_mix(Tensor logits, Tensor labels, Tensor labels2, Tensor lam,
+                                     bool want_grad, double smoothing, int64_t ignore_index) {
+  check_gpu(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "logits must be contiguous [B, C]");
+  const int B = (int)logits.size(0), C = (int)logits.size(1);
+  for (const Tensor* t : {&labels, &labels2})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kLong && t->is_contiguous() &&
+                    t->numel() == B && t->device() == logits.device(),
+                "softmax_xent_mix: labels and labels2 must be contiguous int64 tensors of ", B,
+                " elements on ", logits.device());
+  TORCH_CHECK(lam.is_cuda() && lam.scalar_type() == at::kFloat && lam.is_contiguous() &&
+                  lam.numel() == B && lam.device() == logits.device(),
+              "softmax_xent_mix: lam must be a contiguous float32 tensor of ", B, " elements on ",
+              logits.device());
+  auto fopt = logits.options().dtype(at::kFloat);
+  auto loss = at::empty({}, fopt);
+  auto hits = at::empty({}, logits.options().dtype(at::kInt));
+  auto row_loss = at::empty({B}, fopt);
+  auto row_hit = at::empty({B}, logits.options().dtype(at::kInt));
+  Tensor dlogits;
+  if (want_grad) dlogits = at::empty_like(logits);
+  const float grad_scale = -1.f;   // 1/#valid, counted on device
+  if (logits.scalar_type() == at::kBFloat16) {
+    dmp::launch_softmax_xent_mix_bf16(
+        bf16(logits), labels.data_ptr<int64_t>(), labels2.data_ptr<int64_t>(),
+        lam.data_ptr<float>(), bf16_or_null(dlogits), row_loss.data_ptr<float>(),
+        row_hit.data_ptr<int>(), loss.data_ptr<float>(), hits.data_ptr<int>(), B, C, grad_scale,
+        (float)smoothing, (int)ignore_index, cur_stream());
+  } else {
+    TORCH_CHECK(logits.scalar_type() == at::kFloat, "logits must be bf16 or f32");
+    dmp::launch_softmax_xent_mix_f32(
+        logits.data_ptr<float>(), labels.data_ptr<int64_t>(), labels2.data_ptr<int64_t>(),
+        lam.data_ptr<float>(), ptr_or_null<float>(dlogits), row_loss.data_ptr<float>(),
+        row_hit.data_ptr<int>(), loss.data_ptr<float>(), hits.data_ptr<int>(), B, C, grad_scale,
+        (float)smoothing, (int)ignore_index, cur_stream());
+  }
+  return {loss, hits, dlogits};
+}
+
 // ------------------------------------------------------- fused attention
 // qkv: [B, N, 3*H*64] bf16 rows of the qkv projection ([B, N, 3, H, 64]).
 // route (attn_plan.h): -1 automatic, 0 resident (N <= 256), 1 streaming
@@ -337,6 +378,8 @@ Tensor dropout_bwd(Tensor dy, Tensor mask, double p, int64_t mode, bool channels
 
 void bind_transformer(pybind11::module_& m) {
   m.def("softmax_xent", &softmax_xent, "fused softmax cross entropy fwd+bwd");
+  m.def("softmax_xent_mix", &softmax_xent_mix,
+        "fused softmax cross entropy fwd+bwd with two targets and a per-row weight");
   m.def("token_row_scatter", &token_row_scatter, "gradient of a per-sample token-row select");
   m.def("vit_embed_fwd", &vit_embed_fwd, "ViT token assembly cat(cls, tok) + pos");
   m.def("vit_embed_bwd", &vit_embed_bwd, "ViT token assembly backward (dtok + fp32 batch sums)");

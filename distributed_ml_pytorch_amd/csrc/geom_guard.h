@@ -88,5 +88,14 @@ inline bool assemble_ok(int64_t count, int64_t h, int64_t w, int64_t c, int64_t 
   return pad >= 0 && pad <= kDatasetMaxPad && fits_int(count) && bf16_bytes_ok(count, h, w, c);
 }
 
+// mixing form of the assembler: the CutMix box [y0, y1) x [x0, x1) inside the
+// h x w output (empty allowed), both weights finite and in [0, 1] (a NaN fails
+// every comparison)
+inline bool mix_ok(int64_t h, int64_t w, int64_t y0, int64_t y1, int64_t x0, int64_t x1,
+                   double pix_lam, double label_lam) {
+  if (!(0 <= y0 && y0 <= y1 && y1 <= h && 0 <= x0 && x0 <= x1 && x1 <= w)) return false;
+  return pix_lam >= 0.0 && pix_lam <= 1.0 && label_lam >= 0.0 && label_lam <= 1.0;
+}
+
 }  // namespace guard
 }  // namespace dmp

@@ -12,6 +12,7 @@
 // Every accepted tile plan of the four 3x3 halo-tile families (halo_plan.h) is
 // checked against the tile invariants on the way; `host_check --plans` prints
 // the plans of a fixed shape list instead (one line each, every field).
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -367,6 +368,23 @@ void check_dataset_guard() {
   EXPECT(!assemble_ok(512, 32, 32, 3, 17) && !assemble_ok(512, 32, 32, 3, -1) &&
              !assemble_ok(int64_t(1) << 20, 32, 32, 3, 4) && !assemble_ok(-1, 32, 32, 3, 4),
          "assemble bad pad / oversize batch");
+  // the mixing form: box inside the image (empty allowed), weights in [0, 1]
+  const double nan = std::nan(""), inf = HUGE_VAL;
+  EXPECT(mix_ok(32, 32, 0, 0, 0, 0, 1.0, 1.0) && mix_ok(32, 32, 0, 32, 0, 32, 1.0, 0.0) &&
+             mix_ok(32, 32, 31, 32, 0, 1, 1.0, 0.999) && mix_ok(5, 7, 2, 2, 3, 7, 0.0, 0.0) &&
+             mix_ok(224, 224, 0, 0, 0, 0, 0.3172, 0.3172) && mix_ok(1, 1, 0, 1, 0, 1, 1e-8, 0.5),
+         "mix boxes and weights in range");
+  EXPECT(!mix_ok(32, 32, 0, 33, 0, 32, 1.0, 1.0) && !mix_ok(32, 32, 0, 32, 0, 33, 1.0, 1.0) &&
+             !mix_ok(32, 32, -1, 4, 0, 4, 1.0, 1.0) && !mix_ok(32, 32, 0, 4, -1, 4, 1.0, 1.0) &&
+             !mix_ok(32, 32, 5, 4, 0, 4, 1.0, 1.0) && !mix_ok(32, 32, 0, 4, 9, 8, 1.0, 1.0) &&
+             !mix_ok(32, 32, 0, int64_t(1) << 40, 0, 4, 1.0, 1.0) &&
+             !mix_ok(32, 32, INT64_MIN, 4, 0, INT64_MAX, 1.0, 1.0),
+         "mix box outside the image or reversed");
+  EXPECT(!mix_ok(32, 32, 0, 0, 0, 0, 1.5, 1.0) && !mix_ok(32, 32, 0, 0, 0, 0, 1.0, 1.5) &&
+             !mix_ok(32, 32, 0, 0, 0, 0, -1e-9, 1.0) && !mix_ok(32, 32, 0, 0, 0, 0, 1.0, -0.5) &&
+             !mix_ok(32, 32, 0, 0, 0, 0, nan, 1.0) && !mix_ok(32, 32, 0, 0, 0, 0, 1.0, nan) &&
+             !mix_ok(32, 32, 0, 0, 0, 0, inf, 1.0) && !mix_ok(32, 32, 0, 0, 0, 0, 1.0, -inf),
+         "mix weights outside [0, 1], NaN or infinite");
 }
 
 // attention plans (attn_plan.h) over every token count either route takes, the

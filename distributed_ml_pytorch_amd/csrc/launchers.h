@@ -81,6 +81,18 @@ void launch_softmax_xent_f32(const float* logits, const int64_t* labels, float* 
                              float* row_loss, int* row_hit, float* loss_out, int* hits_out, int B,
                              int C, float grad_scale, float smoothing, int ignore_index,
                              hipStream_t s);
+// two-target form: labels2 [B] int64 and lam [B] fp32 in memory, per row
+// lam * CE(y) + (1 - lam) * CE(y2); a row is valid iff both labels are
+void launch_softmax_xent_mix_bf16(const uint16_t* logits, const int64_t* labels,
+                                  const int64_t* labels2, const float* lam, uint16_t* dlogits,
+                                  float* row_loss, int* row_hit, float* loss_out, int* hits_out,
+                                  int B, int C, float grad_scale, float smoothing,
+                                  int ignore_index, hipStream_t s);
+void launch_softmax_xent_mix_f32(const float* logits, const int64_t* labels,
+                                 const int64_t* labels2, const float* lam, float* dlogits,
+                                 float* row_loss, int* row_hit, float* loss_out, int* hits_out,
+                                 int B, int C, float grad_scale, float smoothing,
+                                 int ignore_index, hipStream_t s);
 
 // data.hip: batch assembler of a device-resident uint8 NHWC dataset
 // (utils/device_data.py): count samples data[index[b]] -> bf16 NHWC out_x through
@@ -94,6 +106,18 @@ void launch_batch_assemble(const uint8_t* data, const long long* labels, const u
                            uint16_t* out_x, long long* out_y, signed char* draws, int pad,
                            bool flip, unsigned long long seed, uint32_t epoch, int path,
                            hipStream_t s);
+// the mixing form (Mixup / CutMix): row b blends its own view with the view of
+// index[count - 1 - b]: the partner's inside the box [y0, y1) x [x0, x1), else
+// a * pix_lam + p * (1 - pix_lam) in separately rounded fp32 (a alone at
+// pix_lam == 1); out_y2 receives the partner's label, out_lam label_lam.
+// guard::mix_ok is the caller's check of the box and the weights.
+void launch_batch_assemble_mix(const uint8_t* data, const long long* labels, const uint16_t* lut,
+                               const int* index, int count, int N, int H, int W, int C,
+                               uint16_t* out_x, long long* out_y, long long* out_y2,
+                               float* out_lam, signed char* draws, int pad, bool flip,
+                               unsigned long long seed, uint32_t epoch, float pix_lam,
+                               float label_lam, int y0, int y1, int x0, int x1, int path,
+                               hipStream_t s);
 
 // bn.hip
 int bn_num_partials(long long M, int C);

@@ -214,6 +214,66 @@ def softmax_cross_entropy(logits, labels, label_smoothing: float = 0.0, ignore_i
     return loss, hits
 
 
+class _SoftmaxXentMix(Function):
+    @staticmethod
+    def forward(ctx, logits, labels, labels2, lam, smoothing, ignore_index):
+        ctx.set_materialize_grads(False)
+        loss, hits, dlogits = native().softmax_xent_mix(
+            logits.contiguous(), labels.contiguous(), labels2.contiguous(), lam.contiguous(), True,
+            float(smoothing), int(ignore_index))
+        ctx.save_for_backward(dlogits)
+        ctx.mark_non_differentiable(hits)
+        return loss, hits
+
+    @staticmethod
+    def backward(ctx, gloss, ghits):
+        (dlogits,) = ctx.saved_tensors
+        if gloss is None:
+            return (None,) * 6
+        if _is_unit(gloss):
+            return (dlogits,) + (None,) * 5
+        return (dlogits * gloss.to(dlogits.dtype),) + (None,) * 5
+
+
+def softmax_cross_entropy_mix(logits, y, y2, lam, label_smoothing: float = 0.0,
+                              ignore_index: int = -100):
+    """Mean two-target cross-entropy of the mixed batches (Mixup / CutMix,
+    utils/device_data.py); returns ``(loss, hits)``.  Per row::
+
+        loss_r = (1 - eps) (lam_r (lse - x_y) + (1 - lam_r) (lse - x_y2)) + eps (lse - mean x)
+
+    with ``lam`` float32 [B].  A row is valid iff both labels are (not
+    ``ignore_index``, inside ``[0, C)``); invalid rows add no loss, no gradient
+    and no hit and are left out of the mean.  A target of weight exactly 0 is not
+    formed.  Hits compare the argmax with ``y`` where ``lam >= 0.5``, else ``y2``.
+    At ``lam == 1`` everywhere this is :func:`softmax_cross_entropy` bit for bit."""
+    if logits.is_cuda:
+        return _SoftmaxXentMix.apply(logits, y, y2, lam, label_smoothing, ignore_index)
+    x = logits.float()
+    c = x.shape[1]
+    ok1 = (y != ignore_index) & (y >= 0) & (y < c)
+    ok2 = (y2 != ignore_index) & (y2 >= 0) & (y2 < c)
+    valid = ok1 & ok2
+    t1 = torch.where(valid, y, torch.full_like(y, ignore_index))
+    t2 = torch.where(valid, y2, torch.full_like(y2, ignore_index))
+    lam = lam.to(x.dtype)
+    wl = 1 - lam
+    # label_smoothing is applied once, outside the two target terms
+    nll1 = F.cross_entropy(x, t1, ignore_index=ignore_index, reduction="none")
+    nll2 = F.cross_entropy(x, t2, ignore_index=ignore_index, reduction="none")
+    zero = torch.zeros_like(nll1)
+    rows = torch.where(lam != 0, lam * nll1, zero) + torch.where(wl != 0, wl * nll2, zero)
+    if label_smoothing > 0:
+        smooth = torch.logsumexp(x, 1) - x.mean(1)
+        rows = (1 - label_smoothing) * rows + label_smoothing * smooth
+    rows = torch.where(valid, rows, zero)
+    loss = rows.sum() / valid.sum().clamp(min=1).to(x.dtype)
+    with torch.no_grad():
+        tgt = torch.where(lam >= 0.5, y, y2)
+        hits = ((logits.argmax(1) == tgt) & valid).sum().to(torch.int32)
+    return loss, hits
+
+
 # ------------------------------------------------------------------ batchnorm
 # (running the backward reduce inside the consuming conv's dgrad epilogue was
 # tried and measured a loss: profiles/bn_bwd_fusion_r2.txt)

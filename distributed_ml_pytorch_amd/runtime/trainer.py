@@ -31,7 +31,7 @@ import torch.distributed as dist
 
 from ..models import build_model
 from ..ops.eval_fold import fold_session
-from ..ops.functional import softmax_cross_entropy, unit_grad
+from ..ops.functional import softmax_cross_entropy, softmax_cross_entropy_mix, unit_grad
 from ..parallel.arena import attach_arena
 from ..parallel.asgd import Asynchronous
 from ..parallel.async_sharded import AsyncShardedPSClient
@@ -43,7 +43,8 @@ from ..parallel.server import ParameterServer, make_ps_groups
 from ..parallel.staleness import check_policy
 from ..utils import checkpoint as ckpt
 from ..utils.data import get_datasets, make_loaders
-from ..utils.device_data import AUGMENTS, MAX_PAD, DeviceLoader, get_device_datasets
+from ..utils.device_data import (AUGMENTS, MAX_PAD, DeviceLoader, MixConfig, check_mix_config,
+                                 get_device_datasets)
 from ..utils.metrics import IterationLog, StepTimer, Throughput, classification_report
 from .determinism import enable_determinism
 from .dist import DistInfo, preflight
@@ -114,6 +115,10 @@ class TrainConfig:
                                       # by one native kernel per step (utils/device_data.py)
     augment: str = "none"             # none | crop | flip | crop_flip (device_data only)
     crop_pad: int = 4                 # zero padding of the random crop
+    mixup: float = 0.0                # Mixup alpha, 0 = off (device_data only)
+    cutmix: float = 0.0               # CutMix alpha, 0 = off (device_data only)
+    mix_prob: float = 1.0             # probability that a batch is mixed at all
+    mix_switch_prob: float = 0.5      # with both on: probability of CutMix over Mixup
     verbose: bool = True
     extra: dict = field(default_factory=dict)
 
@@ -278,21 +283,42 @@ class Worker:
         self.graph = None
         return self.use_graph
 
+    @property
+    def mixes(self) -> bool:
+        """Whether the training batches carry two targets (Mixup / CutMix)."""
+        return self.cfg.mixup > 0 or self.cfg.cutmix > 0
+
+    def _need_mix(self, mix):
+        if mix is None:
+            raise ValueError("this run mixes (--mixup / --cutmix): train_step needs "
+                             "mix=(y2, lam) of the batch")
+        return mix
+
+    def _loss(self, logits, y, mix):
+        if not self.mixes:
+            return softmax_cross_entropy(logits, y, self.cfg.label_smoothing)
+        y2, lam = self._need_mix(mix)
+        return softmax_cross_entropy_mix(logits, y, y2, lam, self.cfg.label_smoothing)
+
     def _graph_body(self):
         self.opt.zero_grad()
         logits = self.model(self._gx)
-        loss, hits = softmax_cross_entropy(logits, self._gy, self.cfg.label_smoothing)
+        loss, hits = self._loss(logits, self._gy, (self._gy2, self._glam))
         loss.backward(unit_grad(loss))
         if self.ddp is not None:
             self.ddp.synchronize()
         self.opt.local_step()
         return loss.detach(), hits
 
-    def _capture(self, x, y):
+    def _capture(self, x, y, mix=None):
         """Run this step eagerly on a side stream (tunes kernels, warms the
         allocator and libraries), then capture the step body for later replays."""
         self._gx = x.detach().clone()
         self._gy = y.detach().clone()
+        self._gy2 = self._glam = None
+        if self.mixes:
+            y2, lam = self._need_mix(mix)
+            self._gy2, self._glam = y2.detach().clone(), lam.detach().clone()
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
@@ -352,15 +378,36 @@ class Worker:
             return self._gx, self._gy
         return None
 
-    def _graph_step(self, x, y, keep: bool = True):
+    def static_mix_inputs(self):
+        """The captured step's own ``(y2, lam)`` buffers of a mixing run, next to
+        :meth:`static_inputs`; ``None`` while no graph is captured or without mixing."""
+        if getattr(self, "use_graph", False) and self.graph is not None and self.mixes:
+            return self._gy2, self._glam
+        return None
+
+    def static_batch_buffers(self):
+        """What a :class:`DeviceLoader` writes the next batch into: ``(x, y)``, or
+        ``(x, y, y2, lam)`` in a mixing run; ``None`` while no graph is captured."""
+        xy = self.static_inputs()
+        if xy is None or not self.mixes:
+            return xy
+        return (*xy, *self.static_mix_inputs())
+
+    def _graph_step(self, x, y, keep: bool = True, mix=None):
         key = self._make_graph_key(x)
         if self.graph is None or key != self._graph_key:
-            return self._capture(x, y)
+            return self._capture(x, y, mix)
         with self.timer.time("compute_launch"):
             if x is not self._gx:
                 self._gx.copy_(x, non_blocking=True)
             if y is not self._gy:
                 self._gy.copy_(y, non_blocking=True)
+            if self.mixes:
+                y2, lam = self._need_mix(mix)
+                if y2 is not self._gy2:
+                    self._gy2.copy_(y2, non_blocking=True)
+                if lam is not self._glam:
+                    self._glam.copy_(lam, non_blocking=True)
             self.graph.replay()
         self.opt.comm_step()
         self.step_idx += 1
@@ -381,16 +428,18 @@ class Worker:
             return math.sqrt(float(native().sumsq(flat)))
         return float(flat.double().norm())
 
-    def train_step(self, x, y, keep: bool = True):
+    def train_step(self, x, y, keep: bool = True, mix=None):
         """One fwd+bwd+update. Returns (loss, hits) as device tensors (no sync).
         ``keep=False``: with hipGraph replay the returned tensors are the graph's
-        own outputs, valid until the next step (no per-step copy kernels)."""
+        own outputs, valid until the next step (no per-step copy kernels).
+        ``mix``: ``(y2, lam)`` of a mixed batch (utils/device_data.py), required
+        when the config mixes: the loss is the two-target cross-entropy."""
         if getattr(self, "use_graph", False):
-            return self._graph_step(x, y, keep)
+            return self._graph_step(x, y, keep, mix)
         with self.timer.time("compute_launch"):
             self.opt.zero_grad()
             logits = self.model(x)
-            loss, hits = softmax_cross_entropy(logits, y, self.cfg.label_smoothing)
+            loss, hits = self._loss(logits, y, mix)
             loss.backward(unit_grad(loss))
         if self.ddp is not None:
             with self.timer.time("allreduce_wait"):
@@ -485,6 +534,10 @@ def check_device_data_config(cfg: TrainConfig, info: DistInfo):
     if cfg.augment != "none" and not cfg.device_data:
         raise ValueError(f"--augment {cfg.augment} needs --device-data: the host loader applies "
                          "no augmentation (random crop and flip run in the batch assembler)")
+    check_mix_config(cfg.mixup, cfg.cutmix, cfg.mix_prob, cfg.mix_switch_prob)
+    if (cfg.mixup > 0 or cfg.cutmix > 0) and not cfg.device_data:
+        raise ValueError("--mixup / --cutmix need --device-data: the host loader mixes nothing "
+                         "(both samples are blended in the batch assembler)")
     if not cfg.device_data:
         return
     if not 0 <= cfg.crop_pad <= MAX_PAD:
@@ -498,17 +551,19 @@ def check_device_data_config(cfg: TrainConfig, info: DistInfo):
 
 def make_device_loaders(cfg: TrainConfig, info: DistInfo, w: "Worker"):
     """Train and test :class:`DeviceLoader` of a run with ``device_data``: the
-    train loader augments as configured and shards as the host path does (sync DP
-    by rank, every other mode the whole set in the rank's own order); the test
-    loader serves the test set in order, unaugmented."""
+    train loader augments and mixes as configured and shards as the host path does
+    (sync DP by rank, every other mode the whole set in the rank's own order); the
+    test loader serves the test set in order, unaugmented and unmixed."""
     tr, te, source = get_device_datasets(cfg.dataset, cfg.data_dir, w.input_shape, w.num_classes,
                                          cfg.n_train, cfg.n_test, cfg.seed, w.device)
     crop, flip = AUGMENTS[cfg.augment]
     shard = cfg.mode == "sync" and info.is_distributed
+    mix = MixConfig(cfg.mixup, cfg.cutmix, cfg.mix_prob, cfg.mix_switch_prob) \
+        if cfg.mixup > 0 or cfg.cutmix > 0 else None
     train = DeviceLoader(tr, cfg.batch_size, shuffle=True, drop_last=True,
                          pad=cfg.crop_pad if crop else 0, flip=flip, seed=cfg.seed + info.rank,
                          rank=info.rank if shard else 0, world=info.world_size if shard else 1,
-                         out_dtype=w.compute_dtype)
+                         out_dtype=w.compute_dtype, mix=mix)
     test = DeviceLoader(te, cfg.test_batch_size, shuffle=False, drop_last=False,
                         out_dtype=w.compute_dtype)
     return train, test, source + "+device"
@@ -654,11 +709,12 @@ def run_training(cfg: TrainConfig, info: DistInfo):
             w.set_lr(base_lr / (epoch + 1))
         if cfg.verbose and info.rank <= 1:
             print(f"Training for epoch {epoch}", flush=True)
-        batches = train_loader.iter_into(w.static_inputs) if cfg.device_data else train_loader
+        batches = train_loader.iter_into(w.static_batch_buffers) if cfg.device_data \
+            else train_loader
         for i, (xb, yb) in enumerate(batches):
             if not cfg.device_data:
                 xb, yb = w.prepare(xb, yb)
-            loss, hits = w.train_step(xb, yb)
+            loss, hits = w.train_step(xb, yb, mix=train_loader.last_mix if w.mixes else None)
             meter.add(yb.numel())
             row = log.append(epoch, i, loss)
             if cfg.log_interval and i % cfg.log_interval == 0 and i > 0:

@@ -29,8 +29,41 @@ then flip: output pixel ``(h, w)`` reads source row ``h + dy - pad`` and column
 byte 0 *before* normalisation (black padding, normalised like any pixel).  An
 index outside ``[0, N)`` reads nothing: its image is all padding and its label
 is -100, the ``ignore_index`` of ``softmax_cross_entropy``.
+
+**Mixup and CutMix** (Zhang et al. 2018, Yun et al. 2019) build a training image
+from two samples inside the same launch.  One draw per batch, on the host
+(:func:`mix_draw`), a pure function of (seed, epoch, batch number in the epoch)
+from a CPU generator of its own, so a resumed run mixes as the uninterrupted one
+did and the epoch's order does not move::
+
+    apply = u0 < prob
+    mode  = cutmix if cutmix_alpha > 0 and (mixup_alpha == 0 or u1 < switch_prob) else mixup
+    lam   = g1 / (g1 + g2),  g1, g2 ~ Gamma(alpha, 1) in fp64        # Beta(alpha, alpha)
+    mixup:  pix_lam = label_lam = float32(lam), no box
+    cutmix: r = sqrt(1 - lam), ch = int(H r), cw = int(W r), cy ~ randint(H), cx ~ randint(W)
+            y0, y1 = clamp(cy - ch // 2, 0, H), clamp(cy + ch // 2, 0, H)   (x likewise)
+            pix_lam = 1, label_lam = float32(1 - (y1 - y0)(x1 - x0) / (H W))
+
+The **view** of a sample is the image defined above (its own crop, flip and
+normalisation).  The partner of batch row ``b`` is row ``count - 1 - b`` (the
+middle row of an odd batch pairs with itself).  With ``a`` row b's view and ``p``
+its partner's, output pixel ``(h, w)`` -- output coordinates, after each
+sample's own crop and flip -- is ``p`` inside the box ``y0 <= h < y1, x0 <= w <
+x1``, else ``a`` when ``pix_lam == 1``, else::
+
+    bf16_rne(fl32(fl32(a * lam) + fl32(p * fl32(1 - lam))))     lam = float32(pix_lam)
+
+four fp32 operations each rounded on its own (no fused multiply-add), so the
+kernel and ``(a.float() * lam + p.float() * (1 - lam)).to(bfloat16)`` agree bit
+for bit.  The step receives ``y`` (row b's label), ``y2`` (the partner's) and
+``lam = label_lam`` per row for the two-target loss
+(``ops.functional.softmax_cross_entropy_mix``).
 """
 from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import NamedTuple
 
 import torch
 
@@ -46,6 +79,8 @@ MNIST_MEAN, MNIST_STD = (0.1307,), (0.3081,)
 SYNTH_MEAN, SYNTH_STD = 128.0 / 255.0, 32.0 / 255.0
 AUGMENTS = {"none": (False, False), "crop": (True, False), "flip": (False, True),
             "crop_flip": (True, True)}
+
+MIX_DOMAIN = 0x6D697875     # "mixu": the mix generator's seed, apart from epoch_order's
 
 _M32 = 0xFFFFFFFF
 
@@ -235,6 +270,134 @@ def assemble(ds: DeviceDataset, index: torch.Tensor, count: int, out_x: torch.Te
         draws[:count].copy_(d)
 
 
+# ---------------------------------------------------------------- mixup / cutmix
+@dataclass(frozen=True)
+class MixConfig:
+    """Mixup / CutMix of the training batches (module docstring)."""
+    mixup_alpha: float = 0.0
+    cutmix_alpha: float = 0.0
+    prob: float = 1.0
+    switch_prob: float = 0.5
+
+    def __post_init__(self):
+        check_mix_config(self.mixup_alpha, self.cutmix_alpha, self.prob, self.switch_prob)
+
+
+class MixParams(NamedTuple):
+    mode: str               # none | mixup | cutmix
+    pix_lam: float          # a float32 value: weight of row b's own view outside the box
+    label_lam: float        # a float32 value: weight of row b's own label
+    box: tuple              # (y0, y1, x0, x1) in output coordinates; empty: (0, 0, 0, 0)
+
+
+NO_MIX = MixParams("none", 1.0, 1.0, (0, 0, 0, 0))
+
+
+def check_mix_config(mixup_alpha, cutmix_alpha, prob, switch_prob):
+    for name, a in (("mixup", mixup_alpha), ("cutmix", cutmix_alpha)):
+        if not (math.isfinite(a) and a >= 0):
+            raise ValueError(f"the {name} alpha must be >= 0, got {a}")
+    for name, q in (("mix probability", prob), ("mix switch probability", switch_prob)):
+        if not 0 <= q <= 1:
+            raise ValueError(f"the {name} must be in [0, 1], got {q}")
+
+
+def _f32(v: float) -> float:
+    return float(torch.tensor(v, dtype=torch.float64).to(torch.float32))
+
+
+def mix_generator(seed: int, epoch: int, batch_no: int) -> torch.Generator:
+    """The CPU generator of one batch's mix draw: seeded by (seed, epoch, batch
+    number) and a domain constant, never the generator of ``epoch_order``."""
+    s = (seed * 0x9E3779B97F4A7C15 + epoch * 0xC2B2AE3D27D4EB4F + batch_no * 0x165667B19E3779F9
+         + MIX_DOMAIN) & ((1 << 63) - 1)
+    return torch.Generator().manual_seed(s)
+
+
+def beta_draw(alpha: float, g: torch.Generator, n: int = 1) -> torch.Tensor:
+    """``n`` fp64 draws of Beta(alpha, alpha) as ``g1 / (g1 + g2)`` of two gamma draws."""
+    gam = torch._standard_gamma(torch.full((2, n), float(alpha), dtype=torch.float64), generator=g)
+    return gam[0] / (gam[0] + gam[1])
+
+
+def mix_draw(seed: int, epoch: int, batch_no: int, H: int, W: int, mixup_alpha: float = 0.0,
+             cutmix_alpha: float = 0.0, prob: float = 1.0, switch_prob: float = 0.5) -> MixParams:
+    """The mix of one batch (module docstring): timm's mode rule and ``rand_bbox``."""
+    check_mix_config(mixup_alpha, cutmix_alpha, prob, switch_prob)
+    g = mix_generator(seed, epoch, batch_no)
+    u0, u1 = torch.rand(2, generator=g, dtype=torch.float64).tolist()
+    if not (u0 < prob and (mixup_alpha > 0 or cutmix_alpha > 0)):
+        return NO_MIX
+    cut = cutmix_alpha > 0 and (mixup_alpha == 0 or u1 < switch_prob)
+    lam = float(beta_draw(cutmix_alpha if cut else mixup_alpha, g)[0])
+    if not 0.0 <= lam <= 1.0:           # both gamma draws underflowed to 0
+        return NO_MIX
+    if not cut:
+        return MixParams("mixup", _f32(lam), _f32(lam), (0, 0, 0, 0))
+    r = math.sqrt(1.0 - lam)
+    ch, cw = int(H * r), int(W * r)
+    cy = int(torch.randint(H, (1,), generator=g))
+    cx = int(torch.randint(W, (1,), generator=g))
+    y0, y1 = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
+    x0, x1 = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
+    return MixParams("cutmix", 1.0, _f32(1.0 - (y1 - y0) * (x1 - x0) / (H * W)), (y0, y1, x0, x1))
+
+
+def _check_mix_params(params: MixParams, h: int, w: int):
+    y0, y1, x0, x1 = params.box
+    ok = 0 <= y0 <= y1 <= h and 0 <= x0 <= x1 <= w and 0 <= params.pix_lam <= 1 and \
+        0 <= params.label_lam <= 1          # the guard of csrc/geom_guard.h (mix_ok)
+    if not ok:
+        raise ValueError(f"mix parameters out of range for a {h} x {w} image: {params}")
+
+
+def assemble_mix_reference(ds: DeviceDataset, index: torch.Tensor, params: MixParams,
+                           pad: int = 0, flip: bool = False, seed: int = 0, epoch: int = 0):
+    """The definition of a mixed batch (module docstring), in torch on the CPU.
+
+    Returns ``x`` bf16 [B, C, H, W], ``y`` and ``y2`` int64 [B] (row b's and its
+    partner's label), ``lam`` float32 [B] (``label_lam``) and row b's ``draws``."""
+    _check_mix_params(params, ds.height, ds.width)
+    a, y, draws = assemble_reference(ds, index, pad, flip, seed, epoch)
+    p, y2 = a.flip(0), y.flip(0)                 # row count - 1 - b
+    y0, y1, x0, x1 = params.box
+    if params.pix_lam == 1:
+        x = a
+    else:
+        lam = torch.tensor(params.pix_lam, dtype=torch.float32)
+        x = (a.float() * lam + p.float() * (1 - lam)).to(torch.bfloat16)
+    box = torch.zeros((ds.height, ds.width), dtype=torch.bool)
+    box[y0:y1, x0:x1] = True
+    x = torch.where(box, p, x)
+    lam_rows = torch.full((len(y),), params.label_lam, dtype=torch.float32)
+    return x, y, y2, lam_rows, draws
+
+
+def assemble_mix(ds: DeviceDataset, index: torch.Tensor, count: int, out_x: torch.Tensor,
+                 out_y: torch.Tensor, out_y2: torch.Tensor, out_lam: torch.Tensor, draws=None,
+                 params: MixParams = NO_MIX, pad: int = 0, flip: bool = False, seed: int = 0,
+                 epoch: int = 0, path: int = -1):
+    """:func:`assemble` with the mix ``params``: also writes rows ``[0, count)`` of
+    ``out_y2`` and ``out_lam``.  The native kernel on a GPU dataset -- a missing
+    extension is an error -- and :func:`assemble_mix_reference` on a CPU one."""
+    _check_args(pad, seed, epoch)
+    _check_mix_params(params, ds.height, ds.width)
+    if ds.device.type == "cuda":
+        from ..ops._ext import native
+
+        native().batch_assemble_mix(ds.data, ds.labels, ds.lut, index, count, out_x, out_y, out_y2,
+                                    out_lam, draws, pad, flip, seed, epoch, params.pix_lam,
+                                    params.label_lam, *params.box, path)
+        return
+    x, y, y2, lam, d = assemble_mix_reference(ds, index[:count], params, pad, flip, seed, epoch)
+    out_x[:count].copy_(x)
+    out_y[:count].copy_(y)
+    out_y2[:count].copy_(y2)
+    out_lam[:count].copy_(lam)
+    if draws is not None:
+        draws[:count].copy_(d)
+
+
 class DeviceLoader:
     """Batches of a :class:`DeviceDataset`, iterable once per epoch.
 
@@ -244,11 +407,18 @@ class DeviceLoader:
     tensor is created per step.  ``shuffle=False`` (evaluation) serves the shard
     in order, the last, shorter batch at its true length.  ``out_dtype``: what a
     CPU loader casts its batches to (a CPU run computes in fp32); a GPU loader
-    writes bf16 only."""
+    writes bf16 only.
+
+    ``mix``: a :class:`MixConfig` sends every batch through :func:`assemble_mix`
+    with the draw of ``(seed, epoch, batch number)`` -- the unmixed batches too,
+    with ``lam = 1``.  ``next`` still returns ``(x, y)``; the partner labels and
+    the weights of that batch are ``last_mix = (y2, lam)``, written into the
+    third and fourth buffer of ``out`` when it has them."""
 
     def __init__(self, ds: DeviceDataset, batch: int, shuffle: bool = True,
                  drop_last: bool = True, pad: int = 0, flip: bool = False, seed: int = 0,
-                 rank: int = 0, world: int = 1, out_dtype: torch.dtype = torch.bfloat16):
+                 rank: int = 0, world: int = 1, out_dtype: torch.dtype = torch.bfloat16,
+                 mix: MixConfig | None = None):
         if batch < 1:
             raise ValueError(f"batch must be >= 1, got {batch}")
         if not 0 <= rank < world:
@@ -258,6 +428,9 @@ class DeviceLoader:
             raise ValueError("a GPU DeviceLoader writes bf16 batches only")
         self.ds, self.batch, self.shuffle, self.drop_last = ds, batch, shuffle, drop_last
         self.pad, self.flip, self.seed, self.out_dtype = pad, flip, seed, out_dtype
+        self.mix = mix
+        self.last_mix = None        # (y2, lam) of the batch next() returned last
+        self.last_params = None     # its MixParams
         self.shard = torch.arange(rank, ds.n, world, dtype=torch.int64)
         self.epoch = 0              # the epoch the next start_epoch() opens
         self._perm = None           # this epoch's order, int32 on the dataset's device
@@ -301,7 +474,10 @@ class DeviceLoader:
         ds = self.ds
         count = min(self.batch, len(self.shard) - self._pos)
         index = self._perm[self._pos:self._pos + count]
+        batch_no = self._pos // self.batch
         self._pos += count
+        if self.mix is not None:
+            return self._next_mixed(index, count, batch_no, out)
         if out is not None:
             x, y = out
         else:
@@ -315,9 +491,35 @@ class DeviceLoader:
             x = x.to(self.out_dtype)
         return x, y
 
+    def _next_mixed(self, index, count, batch_no, out):
+        ds, m = self.ds, self.mix
+        out = tuple(out) if out is not None else ()
+        if len(out) >= 2:
+            x, y = out[:2]
+        else:
+            x = torch.empty((count, ds.channels, ds.height, ds.width), dtype=torch.bfloat16,
+                            device=ds.device, memory_format=torch.channels_last)
+            y = torch.empty(count, dtype=torch.int64, device=ds.device)
+        if len(out) >= 4:
+            y2, lam = out[2:4]
+        else:
+            y2 = torch.empty(x.shape[0], dtype=torch.int64, device=ds.device)
+            lam = torch.empty(x.shape[0], dtype=torch.float32, device=ds.device)
+        params = mix_draw(self.seed, self._cur_epoch, batch_no, ds.height, ds.width,
+                          m.mixup_alpha, m.cutmix_alpha, m.prob, m.switch_prob)
+        assemble_mix(ds, index, count, x, y, y2, lam, None, params, self.pad, self.flip, self.seed,
+                     self._cur_epoch)
+        if x.shape[0] != count:
+            x, y, y2, lam = x[:count], y[:count], y2[:count], lam[:count]
+        if x.dtype != self.out_dtype:
+            x = x.to(self.out_dtype)
+        self.last_mix, self.last_params = (y2, lam), params
+        return x, y
+
     def iter_into(self, provider=None):
         """One epoch of batches; ``provider()`` returns the ``(x, y)`` buffers the
-        next batch is written into, or ``None`` for fresh tensors."""
+        next batch is written into (``(x, y, y2, lam)`` for a mixing loader), or
+        ``None`` for fresh tensors."""
         self.start_epoch()
         while self.remaining():
             yield self.next(provider() if provider is not None else None)
