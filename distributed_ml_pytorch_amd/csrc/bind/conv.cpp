@@ -14,7 +14,17 @@ ConvGeom geom_of(const Tensor& x, const Tensor& w, int64_t OH, int64_t OW) {
           (int)w.size(2), (int)w.size(3), (int)OH, (int)OW};
 }
 
-ConvGeom conv_geom(const Tensor& x, const Tensor& w, int64_t stride, int64_t pad) {
+// cfg is a halo-tile id whose plan applies to this 3x3 geometry over C channels
+bool halo_takes(int64_t cfg, int H, int W, int C, int R, int S, int64_t stride, int64_t pad) {
+  return cfg >= dmp::conv_halo_base() && cfg < dmp::conv_halo_base() + dmp::conv_num_halo_configs() &&
+         stride == 1 && pad == 1 &&
+         dmp::conv_halo_ok((int)cfg, H, W, C, R, S, (int)stride, (int)pad);
+}
+
+// halo_cfg: the cfg id of a call that a halo tile certainly takes when it applies
+// (-1: none).  Those tiles step 32 input channels at a time: CI % 32 == 0 will do.
+ConvGeom conv_geom(const Tensor& x, const Tensor& w, int64_t stride, int64_t pad,
+                   int64_t halo_cfg = -1) {
   TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "conv: 4-D tensors expected");
   TORCH_CHECK(w.size(1) == x.size(1), "conv: weight/input channel mismatch");
   TORCH_CHECK(stride >= 1 && pad >= 0, "conv: bad stride/pad");
@@ -27,7 +37,8 @@ ConvGeom conv_geom(const Tensor& x, const Tensor& w, int64_t stride, int64_t pad
                                           w.size(0), w.size(2), w.size(3)),
               "native conv: tensor too large for 32-bit byte offsets");
   auto g = geom_of(x, w, OH, OW);
-  TORCH_CHECK(g.CI % 64 == 0 && g.CO % 64 == 0,
+  const bool ci32 = g.CI % 32 == 0 && halo_takes(halo_cfg, g.H, g.W, g.CI, g.R, g.S, stride, pad);
+  TORCH_CHECK((g.CI % 64 == 0 || ci32) && g.CO % 64 == 0,
               "native conv needs CI % 64 == 0 and CO % 64 == 0 (got ", g.CI, ", ", g.CO, ")");
   return g;
 }
@@ -49,7 +60,9 @@ std::vector<Tensor> conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad, bo
                              bool relu, optional<Tensor> addend) {
   check_nhwc_bf16(x, "x");
   check_weight_cl(w, at::kBFloat16, "conv weight");
-  auto g = conv_geom(x, w, stride, pad);
+  // (a statistics forward with a bias / ReLU / addend leaves the halo tiles: launch_halo)
+  const bool plain = !(want_stats && (has(bias) || relu || has(addend)));
+  auto g = conv_geom(x, w, stride, pad, plain ? cfg : -1);
   auto y = at::empty({g.B, g.CO, g.OH, g.OW}, x.options().memory_format(kCL));
   check_vecs({&bias}, at::kFloat, g.CO, "conv bias");
   Tensor part;
@@ -95,7 +108,10 @@ Tensor conv_dgrad(Tensor dy, Tensor w, int64_t H, int64_t W, int64_t stride, int
   TORCH_CHECK(dy.size(1) == g.CO, "dgrad: dy channels mismatch");
   TORCH_CHECK((g.H + 2 * pad - g.R) / stride + 1 == g.OH && (g.W + 2 * pad - g.S) / stride + 1 == g.OW,
               "dgrad: geometry mismatch");
-  TORCH_CHECK(g.CI % 64 == 0 && g.CO % 64 == 0, "native dgrad needs CI, CO % 64 == 0");
+  // (the halo tiles reduce over dY's channels 32 at a time)
+  const bool co32 =
+      g.CO % 32 == 0 && halo_takes(cfg, g.H, g.W, g.CO, g.R, g.S, stride, pad);
+  TORCH_CHECK(g.CI % 64 == 0 && (g.CO % 64 == 0 || co32), "native dgrad needs CI, CO % 64 == 0");
   Tensor wt;
   if (has(wt_pre)) {
     wt = *wt_pre;   // pre-transposed [CI][R][S][CO] (batched per step by the arena)
@@ -467,6 +483,16 @@ void bind_conv(pybind11::module_& m) {
         "3x3/stride-2 halo data-gradient cfg ids for (H, W, OH, OW, CO, CI, R, S, stride, pad)");
   m.def("conv_halo_configs", &conv_halo_configs,
         "3x3/stride-1 halo-tile cfg ids applicable to (H, W, C, R, S, stride, pad)");
+  m.def("conv_halo_pm", [](bool on) { return dmp::conv_halo_pm(on); },
+        "position-major halo tiles on 4 x 4 maps: set the process-wide switch, return the "
+        "previous value (never inside a graph capture)", py::arg("on"));
+  m.def("conv_halo_pm_ok",
+        [](int64_t cfg, int64_t H, int64_t W, int64_t C, int64_t R, int64_t S, int64_t stride,
+           int64_t pad) {
+          return dmp::conv_halo_pm_ok((int)cfg, (int)H, (int)W, (int)C, (int)R, (int)S, (int)stride,
+                                      (int)pad);
+        },
+        "halo cfg id runs position-major on (H, W, C, R, S, stride, pad) when the switch is on");
   m.def("stem_supported", [](int64_t H, int64_t W) { return dmp::stem_supported((int)H, (int)W); },
         "ImageNet 7x7/2 stem kernel applies to an H x W input");
   m.def("stem_fwd", &stem_fwd, "ImageNet stem conv forward (+BN partials) via space-to-depth",

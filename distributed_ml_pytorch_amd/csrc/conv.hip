@@ -220,7 +220,7 @@ __device__ __forceinline__ void frag_epilogue(const ConvArgs& a, f32x4 (&acc)[TM
 // NS-stage LDS-DMA ring: NS-1 k-tiles in flight while one is consumed.  (A
 // register-staged variant -- global_load into VGPRs, ds_write_b128 -- measured
 // 2-4x slower on every ResNet-18 shape: profiles/igemm_ablate_r1.txt.)
-template <int BM, int BN, int WM, int WN, bool FLIP, bool STATS, int TM, int TN>
+template <int BM, int BN, int WM, int WN, bool FLIP, bool STATS, int TM, int TN, bool PM = false>
 __device__ __forceinline__ void halo_epilogue_rows(const ConvArgs& a, f32x4 (&acc)[TM][TN],
                                                    long long m0, int n0, int wm, int wn, int tid,
                                                    int lane, u16* lds_h, int mv);
@@ -467,7 +467,10 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_igemm_kernel(ConvArgs a) {
 // subsampled addend (addend_sub) lands on class 0 only, indexed by m.  (It
 // scatters every other pixel: default store policy, its half-line writes merge
 // in L2.)
-template <int BM, int BN, int WM, int WN, bool FLIP, bool STATS, int TM, int TN, bool S2 = false>
+// PM: position-major fragments (halo_pm.h): tile row ml is image (ml & 15) at the
+// pixel position of fragment (ml >> 4), output pixel m0 + pm::out_pixel(ml).
+template <int BM, int BN, int WM, int WN, bool FLIP, bool STATS, int TM, int TN, bool S2 = false,
+          bool PM = false>
 __device__ __forceinline__ void halo_epilogue(const ConvArgs& a, f32x4 (&acc)[TM][TN], long long m0,
                                               int n0, int wm, int wn, int tid, int lane,
                                               u16* lds_h, int cls = 0, int mv = BM) {
@@ -476,6 +479,11 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs& a, f32x4 (&acc)[TM
   const bool add_in = !PLAIN && (S2 ? (a.addend != nullptr && (!a.addend_sub || cls == 0))
                                     : (a.addend != nullptr));   // dgrad residual grad / fwd BN-fold residual
   auto row_of = [&](int ml, long long& m, long long& pix) {
+    if constexpr (PM) {
+      m = m0 + pm::out_pixel(ml);
+      pix = m;
+      return m < Mrows;
+    }
     m = m0 + ml;
     pix = m;
     if constexpr (S2) {
@@ -505,7 +513,11 @@ __device__ __forceinline__ void halo_epilogue(const ConvArgs& a, f32x4 (&acc)[TM
 // row phase.  BN partial sums (STATS) of the stored values: per lane over its
 // rows, shuffle-reduced over the lanes of one channel chunk, LDS across waves,
 // one atomic pair per channel per block (slot blockIdx % kBnSlots).
-template <int BM, int BN, int WM, int WN, bool FLIP, bool STATS, int TM, int TN>
+// PM (position-major fragments, halo_pm.h): phase 1 writes fragment row ml at the
+// tile row of its output pixel, pm::out_pixel(ml), so phase 2 moves the same row
+// segments as ever; both phases add pm::kEpiSkew elements per image to the row
+// address (a fragment's rows are 16 pixels apart there).
+template <int BM, int BN, int WM, int WN, bool FLIP, bool STATS, int TM, int TN, bool PM>
 __device__ __forceinline__ void halo_epilogue_rows(const ConvArgs& a, f32x4 (&acc)[TM][TN],
                                                    long long m0, int n0, int wm, int wn, int tid,
                                                    int lane, u16* lds_h, int mv) {
@@ -537,7 +549,12 @@ __device__ __forceinline__ void halo_epilogue_rows(const ConvArgs& a, f32x4 (&ac
       uint2 pk;
       pk.x = (u32)f2bf(t[0]) | ((u32)f2bf(t[1]) << 16);
       pk.y = (u32)f2bf(t[2]) | ((u32)f2bf(t[3]) << 16);
-      *reinterpret_cast<uint2*>(lds_h + ml * PITCH + nl) = pk;
+      if constexpr (PM) {
+        const int mr = pm::out_pixel(ml);
+        *reinterpret_cast<uint2*>(lds_h + mr * PITCH + (mr >> 4) * pm::kEpiSkew + nl) = pk;
+      } else {
+        *reinterpret_cast<uint2*>(lds_h + ml * PITCH + nl) = pk;
+      }
     }
   }
   __syncthreads();
@@ -573,7 +590,8 @@ __device__ __forceinline__ void halo_epilogue_rows(const ConvArgs& a, f32x4 (&ac
 #pragma unroll
   for (int q = 0; q < NR; ++q) {
     const int ml = min((q * NW + wid) * RPI + lr, BM - 1);
-    bf16x8 v = *reinterpret_cast<const bf16x8*>(lds_h + ml * PITCH + ch * 8);
+    bf16x8 v = *reinterpret_cast<const bf16x8*>(lds_h + ml * PITCH +
+                                                (PM ? (ml >> 4) * pm::kEpiSkew : 0) + ch * 8);
     if (add_in) {
       const bf16x8 xv = __builtin_bit_cast(bf16x8, xa[q]);
 #pragma unroll
@@ -625,15 +643,39 @@ __device__ __forceinline__ void halo_epilogue_rows(const ConvArgs& a, f32x4 (&ac
   }
 }
 
-template <int BM, int BN, int BK, int WM, int WN, int NS, bool FLIP, bool STATS>
+// compile-time loop index: f(IntC<0>{}) ... f(IntC<N - 1>{}) in order (a step
+// whose sched_group_barrier counts are constants of the index)
+template <int N>
+struct IntC {
+  static constexpr int value = N;
+};
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void static_steps(F&& f) {
+  if constexpr (I < N) {
+    f(IntC<I>{});
+    static_steps<N, I + 1>(f);
+  }
+}
+
+// PM: the position-major form for whole-image tiles of 4 x 4 maps (halo_pm.h,
+// plan_halo_pm).  A fragment is one pixel position across the tile's 16 images,
+// so a tap lies in the image for a whole fragment or for none of it: the compute
+// loop, specialised per wave row, issues only the live fragments' reads and
+// MFMAs (100 of 144), and only the images' real pixels are staged (17 DMA pieces
+// per chunk instead of 36).  The skipped products are exact zeros and the order
+// of the others is unchanged: the outputs equal the dense kernel's bit for bit.
+template <int BM, int BN, int BK, int WM, int WN, int NS, bool FLIP, bool STATS, bool PM = false>
 __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, HaloGeom hg) {
   constexpr int NW = WM * WN;
   constexpr int CPR = BK / 8, RPI = 64 / CPR;
   constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
   constexpr int B_ROWS = 9 * BN, B_INS = B_ROWS / RPI, B_PW = (B_INS + NW - 1) / NW;
   static_assert(B_ROWS % RPI == 0, "weight tile rows");
+  static_assert(!PM || (BM == pm::kBM && WM == pm::kWM && TM == pm::kTM && BK == 32),
+                "position-major tiles: 16 images of 4 x 4, four wave rows of four fragments");
   extern __shared__ __attribute__((aligned(16))) u16 lds_h[];
-  const int A_EL = hg.A_INS * RPI * BK;
+  const int A_INS = PM ? pm::kPieces : hg.A_INS;
+  const int A_EL = A_INS * RPI * BK;
   const int STAGE = A_EL + B_ROWS * BK;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -677,11 +719,23 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
   };
   // halo DMA slots: lane's row of each 1-KiB piece -> (image, h, w) of the
   // source pixel; positions outside the image (or past the batch) read zeros
-  unsigned a_base[kHaloAPW];
+  // (PM: staged row -> image tb of the tile and pixel p, pm::row_tb / row_p; the
+  // pad row of every image block and images past the batch read zeros)
+  constexpr int A_PW = PM ? (pm::kPieces + NW - 1) / NW : kHaloAPW;
+  unsigned a_base[A_PW];
 #pragma unroll
-  for (int j = 0; j < kHaloAPW; ++j) {
+  for (int j = 0; j < A_PW; ++j) {
     const int ins = wid + j * NW;
     const int row = ins * RPI + lane / CPR;
+    if constexpr (PM) {
+      int tb, p;
+      small_divmod(row, pm::kPI, 1.f / (float)pm::kPI, tb, p);
+      const bool ok = ins < pm::kPieces && p < pm::kImg && b0 + tb < a.B;
+      a_base[j] = ok ? 2u * (unsigned)(((b0 + tb) * pm::kImg + p) * C +
+                                       pm::swz(tb, lane % CPR) * 8)
+                     : kOOB;
+      continue;
+    }
     int tb, rem, hh, ww;
     small_divmod(row, per_img, rcp_pi, tb, rem);
     small_divmod(rem, HW2, rcp_w2, hh, ww);
@@ -713,9 +767,9 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
     u16* Bs = As + A_EL;
     const unsigned cd = 2u * (unsigned)(c * BK);
 #pragma unroll
-    for (int j = 0; j < kHaloAPW; ++j) {
+    for (int j = 0; j < A_PW; ++j) {
       const int ins = wid + j * NW;
-      if (ins < hg.A_INS)
+      if (ins < A_INS)
         dma16(rsA, a_base[j] == kOOB ? kOOB : a_base[j] + cd, As + ins * (RPI * BK));
     }
 #pragma unroll
@@ -736,9 +790,9 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
   // once (k-step 0; BK = 32 has one): the staged row of the lane's output pixel
   // at tap (0, 0) plus the tap's row / column shift, swizzled (hswz)
   static_assert(BK == 32, "conv_halo_kernel: one 32-deep k-step per tap");
-  int aoff[TM][9];
+  int aoff[PM ? 1 : TM][9];
 #pragma unroll
-  for (int i = 0; i < TM; ++i) {
+  for (int i = 0; i < (PM ? 0 : TM); ++i) {
     int ml = wm * (BM / WM) + i * 16 + (lane & 15);
     if (ml >= MV) ml = 0;   // padded tile: a valid staged row, the epilogue drops it
     int tb, r2, th, tw;
@@ -801,6 +855,79 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
     }
   };
 
+  // PM: the same steps for wave row WMC with only the live (fragment, tap) pairs
+  // (pm::live, compile-time per step): a dead fragment's ds_read_b128 and its TN
+  // MFMAs are not issued, and the interleave is pinned to each step's real
+  // counts.  The fragment of lane (tb, k-chunk) at the centre tap is staged row
+  // tb * 17 + position, chunk swizzled on tb; a tap adds a constant row shift.
+  // Taps stay in order per accumulator, FLIP mirrors the weight tap only.
+  int apm[TM];
+  if constexpr (PM) {
+    const int tb = lane & 15;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+      apm[i] = pm::staged_row(tb, pm::frag_pos(wm, i)) * BK + pm::swz(tb, lane >> 4) * 8;
+  }
+  auto compute_pm = [&](int buf, auto wmc) __attribute__((always_inline)) {
+    constexpr int WMC = decltype(wmc)::value;
+    const u16* As = lds_h + buf * STAGE;
+    const u16* Bs = As + A_EL;
+    bf16x8 af[2][TM], bw[2][TN];
+    auto load = [&](auto tc, int slot) __attribute__((always_inline)) {
+      constexpr int t = decltype(tc)::value;
+      if (DMP_ABLATE == 4 && t >= 2) return;
+      constexpr int wt = FLIP ? 8 - t : t;
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+        if (pm::live(WMC, i, t))
+          af[slot][i] = *reinterpret_cast<const bf16x8*>(As + apm[i] + pm::tap_shift(t) * BK);
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+        bw[slot][j] = *reinterpret_cast<const bf16x8*>(Bs + wt * BN * BK + offB[0] + j * 16 * BK);
+    };
+    load(IntC<0>{}, 0);
+    __builtin_amdgcn_sched_group_barrier(0x100, pm::live_count(WMC, 0) + TN, 0);
+    static_steps<9>([&](auto tc) __attribute__((always_inline)) {
+      constexpr int t = decltype(tc)::value;
+      if constexpr (t + 1 < 9) load(IntC<t + 1>{}, (t + 1) & 1);
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+        if (pm::live(WMC, i, t)) {
+#pragma unroll
+          for (int j = 0; j < TN; ++j) acc[i][j] = mfma16(bw[t & 1][j], af[t & 1][i], acc[i][j]);
+        }
+      // step t + 1's reads interleaved one per MFMA of step t, the rest of either after
+      constexpr int NM = pm::live_count(WMC, t) * TN;
+      if constexpr (t + 1 < 9) {
+        constexpr int NR = pm::live_count(WMC, t + 1) + TN;
+        constexpr int NP = NR < NM ? NR : NM;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        }
+        if constexpr (NM > NP) __builtin_amdgcn_sched_group_barrier(0x008, NM - NP, 0);
+        if constexpr (NR > NP) __builtin_amdgcn_sched_group_barrier(0x100, NR - NP, 0);
+      } else {
+        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
+      }
+    });
+  };
+  // liveness is a property of the wave row: one straight-line arm each (wm is
+  // wave-uniform, a scalar branch)
+  auto run = [&](int buf) {
+    if constexpr (PM) {
+      switch (wm) {
+        case 0: compute_pm(buf, IntC<0>{}); break;
+        case 1: compute_pm(buf, IntC<1>{}); break;
+        case 2: compute_pm(buf, IntC<2>{}); break;
+        default: compute_pm(buf, IntC<3>{}); break;
+      }
+    } else {
+      compute(buf);
+    }
+  };
+
   // 8-wave tiles: waves 4-7 at priority 1 (s4 fwd / dgrad -1.8 / -2.1 %,
   // profiles/prio_young_half_r5.txt)
   if (NW == 8) prio_young_half(wid);
@@ -812,7 +939,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
       __builtin_amdgcn_s_barrier();       // ... for every wave; chunk c-1's slot is free
       asm volatile("" ::: "memory");
       if (c + 1 < KC && DMP_ABLATE != 2) stage((c + 1) & 1, c + 1);
-      if (DMP_ABLATE != 1) compute(DMP_ABLATE == 2 ? 0 : c & 1);
+      if (DMP_ABLATE != 1) run(DMP_ABLATE == 2 ? 0 : c & 1);
     }
   } else {
     // one stage: half the LDS, so two or three blocks share a CU and one
@@ -823,7 +950,7 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
       wait_vm<0>();
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-      if (DMP_ABLATE != 1) compute(0);
+      if (DMP_ABLATE != 1) run(0);
     }
   }
   __syncthreads();   // all stage reads done before the epilogue reuses LDS
@@ -838,10 +965,11 @@ __global__ void __launch_bounds__(64 * WM * WN) conv_halo_kernel(ConvArgs a, Hal
   // 128 / 256-channel layers, no change on the forward, whose BN sums cost
   // more in the row layout: profiles/conv_roofline_r4.txt)
   if constexpr (DMP_HALO_EPI_LDS || FLIP)
-    halo_epilogue_rows<BM, BN, WM, WN, FLIP, STATS, TM, TN>(a, acc, m0, n0, wm, wn, tid, lane, lds_h,
-                                                            MV);
+    halo_epilogue_rows<BM, BN, WM, WN, FLIP, STATS, TM, TN, PM>(a, acc, m0, n0, wm, wn, tid, lane,
+                                                                lds_h, MV);
   else
-    halo_epilogue<BM, BN, WM, WN, FLIP, STATS>(a, acc, m0, n0, wm, wn, tid, lane, lds_h, 0, MV);
+    halo_epilogue<BM, BN, WM, WN, FLIP, STATS, TM, TN, false, PM>(a, acc, m0, n0, wm, wn, tid, lane,
+                                                                  lds_h, 0, MV);
 }
 
 // ------------------------------- 3x3 stride-2 data gradient, halo tiles
@@ -1520,9 +1648,30 @@ bool conv_halo_ok(int cfg, int H, int W, int C, int R, int S, int stride, int pa
 int conv_num_halo_configs() { return kNumHaloConfigs; }
 int conv_halo_base() { return kHaloBase; }
 
-template <int BM, int BN, int BK, int WM, int WN, int NS, bool FLIP, bool STATS>
+// position-major tiles (halo_pm.h) under the same cfg ids: DMP_HALO_PM=0 keeps the
+// dense kernel; read once, then only conv_halo_pm() changes it (A/B in one process)
+static bool& halo_pm_switch() {
+  static bool on = [] {
+    const char* e = std::getenv("DMP_HALO_PM");
+    return e == nullptr || e[0] != '0';
+  }();
+  return on;
+}
+
+bool conv_halo_pm(bool on) {
+  bool& sw = halo_pm_switch();
+  const bool prev = sw;
+  sw = on;
+  return prev;
+}
+
+bool conv_halo_pm_ok(int cfg, int H, int W, int C, int R, int S, int stride, int pad) {
+  return plan_halo_pm(cfg, H, W, C, R, S, stride, pad).ok;
+}
+
+template <int BM, int BN, int BK, int WM, int WN, int NS, bool FLIP, bool STATS, bool PM = false>
 static void launch_halo_t(const ConvArgs& a, const HaloGeom& g, size_t lds, hipStream_t s) {
-  constexpr auto kern = conv_halo_kernel<BM, BN, BK, WM, WN, NS, FLIP, STATS>;
+  constexpr auto kern = conv_halo_kernel<BM, BN, BK, WM, WN, NS, FLIP, STATS, PM>;
   allow_max_dynamic_lds<kern>();
   const long long M = (long long)a.B * a.OH * a.OW;
   const dim3 grid((unsigned)((M + g.MV - 1) / g.MV), (unsigned)((a.CO + BN - 1) / BN));
@@ -1588,6 +1737,14 @@ static bool launch_halo(const ConvArgs& a, int cfg, hipStream_t s) {
   // the statistics forward's epilogue has no bias / ReLU / addend (PLAIN in
   // halo_epilogue): such a conv takes the implicit GEMM instead
   if (!FLIP && STATS && (a.bias != nullptr || a.relu || a.addend != nullptr)) return false;
+  // 4 x 4 maps: the position-major form of the same tile (only id kHaloBase has one)
+  if (halo_pm_switch()) {
+    if (const HaloPlan q = plan_halo_pm(cfg, a.GH, a.GW, a.CI, a.R, a.S, a.stride, a.pad); q.ok) {
+      static_assert(halo_pm_cfg(kHaloBase) && !halo_pm_cfg(kHaloBase + 1), "PM dispatch");
+      launch_halo_t<256, 64, 32, 4, 2, 2, FLIP, STATS, true>(a, q.g, q.lds, s);
+      return true;
+    }
+  }
   switch (cfg - kHaloBase) {
 #define X(i, BM, BN, BK, WM, WN, NS) \
   case i: launch_halo_t<BM, BN, BK, WM, WN, NS, FLIP, STATS>(a, p.g, p.lds, s); return true;

@@ -11,6 +11,8 @@
 
 #include <cstddef>
 
+#include "halo_pm.h"
+
 namespace dmp {
 
 // dynamic LDS a block may ask for (of the CU's 160 KiB)
@@ -178,6 +180,40 @@ inline HaloPlan plan_halo(int cfg, int H, int W, int C, int R, int S, int stride
   const size_t stage = (size_t)h.A_INS * rpi * bk + (size_t)9 * bn * bk;
   p.lds = (size_t)p.c.ns * stage * 2;
   if (p.lds < (size_t)bm * (bn + 8) * 2) p.lds = (size_t)bm * (bn + 8) * 2;   // row epilogue tile
+  p.ok = p.lds <= (size_t)kMaxDynamicLds;
+  return p;
+}
+
+// Position-major plan (halo_pm.h) of a halo config: 4 x 4 maps in whole-image
+// tiles of 16 images, one fragment = one pixel position across them, padding
+// taps not issued.  Taken by launch_halo instead of plan_halo's dense plan under
+// the same cfg id; !ok: the config keeps the dense kernel.  Covers the 256 x 64
+// two-stage tile of 4 x 2 waves (id kHaloBase), the pick of ResNet-18's stage 4.
+constexpr bool halo_pm_cfg(int cfg) { return cfg == kHaloBase; }
+
+inline HaloPlan plan_halo_pm(int cfg, int H, int W, int C, int R, int S, int stride, int pad) {
+  HaloPlan p{};
+  if (!halo_pm_cfg(cfg)) return p;
+  p.c = halo_cfg(cfg);
+  if (!p.c.ok || p.c.bm != pm::kBM || p.c.bk != 32) return p;
+  if (R != 3 || S != 3 || stride != 1 || pad != 1 || C % p.c.bk != 0) return p;
+  if (H != pm::kH || W != pm::kW) return p;
+  const HaloTiling t = halo_tiling(p.c.bm, H, W, false);
+  if (!t.ok || t.TH != H || t.TB != pm::kTB) return p;
+  HaloGeom& h = p.g;
+  h.TH = t.TH;
+  h.TB = t.TB;
+  h.MV = t.MV;
+  h.PSW = 0;
+  h.W2 = W;          // no halo columns
+  h.PI = pm::kPI;
+  h.HROWS = pm::kRows;
+  h.A_INS = pm::kPieces;
+  if (h.A_INS > kHaloAPW * p.c.nw) return p;
+  const size_t stage = (size_t)pm::kRows * p.c.bk + (size_t)9 * p.c.bn * p.c.bk;
+  p.lds = (size_t)p.c.ns * stage * 2;
+  const size_t epi = (size_t)pm::epi_elems(p.c.bn) * 2;   // row epilogue tile
+  if (p.lds < epi) p.lds = epi;
   p.ok = p.lds <= (size_t)kMaxDynamicLds;
   return p;
 }

@@ -227,6 +227,13 @@ int conv_dgrad_s2_base();
 int conv_dgrad_s2_num_configs();
 int conv_halo_base();
 bool conv_halo_ok(int cfg, int H, int W, int C, int R, int S, int stride, int pad);
+// Position-major tiles of the halo kernels on 4 x 4 maps (halo_pm.h), taken under
+// the same cfg ids where they apply.  Process-wide switch, initialised once from
+// DMP_HALO_PM (default on, 0 = dense); sets it and returns the previous value.
+// Not to be toggled while a graph is being captured.
+bool conv_halo_pm(bool on);
+// true if cfg runs position-major on this geometry when the switch is on
+bool conv_halo_pm_ok(int cfg, int H, int W, int C, int R, int S, int stride, int pad);
 // 3x3 / stride-1 halo wgrad: cfg ids conv_wgrad_halo_base() + [0, conv_wgrad_num_halo_configs())
 int conv_wgrad_halo_base();
 int conv_wgrad_num_halo_configs();
