@@ -130,6 +130,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="probability that a batch is mixed at all")
     p.add_argument("--mix-switch-prob", type=float, default=0.5,
                    help="with --mixup and --cutmix both on: probability of CutMix for a batch")
+    p.add_argument("--drop-path", type=float, default=0.0, metavar="RATE",
+                   help="ViT models: stochastic depth (drop path), per sample; RATE in [0, 1) is "
+                        "the last block's, the blocks ramp up to it linearly (0 = off)")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log-dir", default="log")
     p.add_argument("--no-eval", action="store_true", default=False)
@@ -158,7 +161,7 @@ def config_from_args(a) -> TrainConfig:
         adam_eps=a.adam_eps, clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,
         lr_min=a.lr_min, schedule_steps=a.schedule_steps, device_data=a.device_data,
         augment=a.augment, crop_pad=a.crop_pad, mixup=a.mixup, cutmix=a.cutmix,
-        mix_prob=a.mix_prob, mix_switch_prob=a.mix_switch_prob)
+        mix_prob=a.mix_prob, mix_switch_prob=a.mix_switch_prob, drop_path=a.drop_path)
 
 
 def main(argv=None):

@@ -149,8 +149,19 @@ int64_t ln_dim(const Tensor& x, const char* fn) {
   return D;
 }
 
+// the per-sample scale row of a row-scaled add (stochastic depth): `rows` rows in
+// samples of `tokens` rows each, one fp32 scale per sample
+void check_rscale(const optional<Tensor>& rscale, int64_t tokens, int64_t rows, const Tensor& x,
+                  const char* fn) {
+  TORCH_CHECK(tokens >= 1 && tokens <= INT32_MAX && rows % tokens == 0, fn,
+              ": rscale needs tokens >= 1 dividing the ", rows, " rows, got ", tokens);
+  check_vec(*rscale, at::kFloat, rows / tokens, "rscale (one scale per sample)");
+  TORCH_CHECK(rscale->device() == x.device(), fn, ": rscale must be on ", x.device());
+}
+
 std::vector<Tensor> layernorm_fwd(Tensor x, optional<Tensor> gamma, optional<Tensor> beta,
-                                  double eps, optional<Tensor> residual) {
+                                  double eps, optional<Tensor> residual, optional<Tensor> rscale,
+                                  int64_t tokens) {
   check_rows_bf16(x, "x");
   const int64_t D = ln_dim(x, "layernorm");
   const int64_t rows = x.numel() / D;
@@ -165,16 +176,22 @@ std::vector<Tensor> layernorm_fwd(Tensor x, optional<Tensor> gamma, optional<Ten
     same_shape(r, x, "layernorm: residual");
     h = at::empty_like(x);
   }
+  if (has(rscale)) {
+    TORCH_CHECK(has(residual), "layernorm: rscale scales the residual, which is missing");
+    check_rscale(rscale, tokens, rows, x, "layernorm");
+  }
   dmp::launch_layernorm_fwd(bf16(x), ptr_or_null<float>(gamma), ptr_or_null<float>(beta), bf16(y),
                             mean.data_ptr<float>(), rstd.data_ptr<float>(), rows, (int)D,
-                            (float)eps, cur_stream(), bf16_or_null(r), bf16_or_null(h));
+                            (float)eps, cur_stream(), bf16_or_null(r), bf16_or_null(h),
+                            ptr_or_null<float>(rscale), (int)tokens);
   if (h.defined()) return {y, mean, rstd, h};
   return {y, mean, rstd};
 }
 
-Tensor layernorm_bwd(Tensor x, Tensor dy, optional<Tensor> gamma, Tensor mean, Tensor rstd,
-                     optional<Tensor> dgamma, optional<Tensor> dbeta, optional<Tensor> slots,
-                     optional<Tensor> dres) {
+// returns dx, or (dx, dr) with rscale: dr = the scaled branch's gradient
+py::object layernorm_bwd(Tensor x, Tensor dy, optional<Tensor> gamma, Tensor mean, Tensor rstd,
+                         optional<Tensor> dgamma, optional<Tensor> dbeta, optional<Tensor> slots,
+                         optional<Tensor> dres, optional<Tensor> rscale, int64_t tokens) {
   check_rows_bf16(x, "x");
   dy = dy.contiguous();
   check_rows_bf16(dy, "dy");
@@ -202,11 +219,56 @@ Tensor layernorm_bwd(Tensor x, Tensor dy, optional<Tensor> gamma, Tensor mean, T
     check_rows_bf16(dr, "dres");
     same_shape(dr, x, "layernorm_bwd: dres");
   }
+  Tensor dbranch;
+  if (has(rscale)) {
+    check_rscale(rscale, tokens, rows, x, "layernorm_bwd");
+    dbranch = at::empty_like(x);
+  }
   dmp::launch_layernorm_bwd(bf16(x), bf16(dy), ptr_or_null<float>(gamma), mean.data_ptr<float>(),
                             rstd.data_ptr<float>(), bf16(dx), ptr_or_null<float>(dgamma),
                             ptr_or_null<float>(dbeta), ptr_or_null<float>(sl), rows, (int)D,
-                            cur_stream(), bf16_or_null(dr));
-  return dx;
+                            cur_stream(), bf16_or_null(dr), ptr_or_null<float>(rscale),
+                            (int)tokens, bf16_or_null(dbranch));
+  if (dbranch.defined()) return py::cast(std::make_tuple(dx, dbranch));
+  return py::cast(dx);
+}
+
+// ------------------------------------------------------------ stochastic depth
+// One draw launch: table [branches, B] of per-sample branch scales for step
+// state[0], which the launch advances.  thresholds (int64 holding uint32 values)
+// and scales (fp32) are the per-branch constants built once on the host.
+Tensor drop_path_draw(Tensor state, Tensor thresholds, Tensor scales, int64_t B, int64_t seed) {
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kLong && state.is_contiguous() &&
+                  state.numel() >= 1,
+              "drop_path_draw: state must be a contiguous int64 GPU tensor (the step counter)");
+  const int64_t nb = scales.numel();
+  TORCH_CHECK(nb >= 1 && B >= 1 && nb * ((B + 3) / 4) <= (1 << 24),
+              "drop_path_draw: needs >= 1 branch and sample, and at most 2^24 draws");
+  check_vec(thresholds, at::kLong, nb, "drop_path_draw: thresholds");
+  check_vec(scales, at::kFloat, nb, "drop_path_draw: scales");
+  TORCH_CHECK(thresholds.device() == state.device() && scales.device() == state.device(),
+              "drop_path_draw: state, thresholds and scales must share a device");
+  Tensor table = at::empty({nb, B}, scales.options());
+  dmp::launch_drop_path_draw(table.data_ptr<float>(), i64(state), i64(thresholds),
+                             scales.data_ptr<float>(), (int)nb, (int)B, (unsigned long long)seed,
+                             cur_stream());
+  return table;
+}
+
+// y = x * rscale[sample]: x's leading dim holds rscale.numel() samples
+Tensor drop_path_rows(Tensor x, Tensor rscale) {
+  x = x.contiguous();
+  check_rows_bf16(x, "x");
+  const int64_t B = rscale.numel();
+  TORCH_CHECK(B >= 1 && x.numel() % B == 0 && (x.numel() / B) % 8 == 0,
+              "drop_path_rows: x must hold rscale.numel() = ", B,
+              " samples of a multiple of 8 elements, got ", x.numel(), " elements");
+  check_vec(rscale, at::kFloat, B, "drop_path_rows: rscale");
+  TORCH_CHECK(rscale.device() == x.device(), "drop_path_rows: rscale must be on ", x.device());
+  auto y = at::empty_like(x);
+  dmp::launch_drop_path_rows(bf16(x), rscale.data_ptr<float>(), bf16(y), x.numel() / B / 8,
+                             x.numel() / 8, cur_stream());
+  return y;
 }
 
 // [B, D] gradient of the token-`tok` rows -> the [B, N, D] stream gradient
@@ -385,11 +447,17 @@ void bind_transformer(pybind11::module_& m) {
   m.def("vit_embed_bwd", &vit_embed_bwd, "ViT token assembly backward (dtok + fp32 batch sums)");
   m.def("layernorm_fwd", &layernorm_fwd,
         "row LayerNorm forward -> (y, mean, rstd[, h = x + residual])", py::arg("x"),
-        py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("residual") = py::none());
-  m.def("layernorm_bwd", &layernorm_bwd, "row LayerNorm backward (dgamma/dbeta accumulated)",
+        py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("residual") = py::none(),
+        py::arg("rscale") = py::none(), py::arg("tokens") = 0);
+  m.def("layernorm_bwd", &layernorm_bwd,
+        "row LayerNorm backward (dgamma/dbeta accumulated) -> dx, or (dx, dr) with rscale",
         py::arg("x"), py::arg("dy"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
         py::arg("dgamma"), py::arg("dbeta"), py::arg("slots") = py::none(),
-        py::arg("dres") = py::none());
+        py::arg("dres") = py::none(), py::arg("rscale") = py::none(), py::arg("tokens") = 0);
+  m.def("drop_path_draw", &drop_path_draw,
+        "stochastic depth: draw the [branches, B] scale table of the next step", py::arg("state"),
+        py::arg("thresholds"), py::arg("scales"), py::arg("B"), py::arg("seed"));
+  m.def("drop_path_rows", &drop_path_rows, "x * rscale[sample] (bf16 rows, fp32 scales)");
   m.def("attention_fwd", &attention_fwd, "fused MHSA forward on qkv rows -> (out, lse2)",
         py::arg("qkv"), py::arg("heads"), py::arg("route") = -1);
   m.def("attention_bwd", &attention_bwd, "fused MHSA backward -> dqkv (qkv layout)",

@@ -179,14 +179,19 @@ void launch_maxpool_bwd(const uint16_t* dy, const uint8_t* idx, uint16_t* dx, in
 bool layernorm_supported(int D);
 int layernorm_num_slots();
 // radd/hout: fused residual add (h = x + radd written to hout, LayerNorm of h)
+// rscale [rows / tokens]: the add is scaled per sample (h = x + radd * rscale[row / tokens],
+// stochastic depth); needs radd and hout
 void launch_layernorm_fwd(const uint16_t* x, const float* gamma, const float* beta, uint16_t* y,
                           float* mean, float* rstd, long long rows, int D, float eps,
-                          hipStream_t s, const uint16_t* radd = nullptr, uint16_t* hout = nullptr);
+                          hipStream_t s, const uint16_t* radd = nullptr, uint16_t* hout = nullptr,
+                          const float* rscale = nullptr, int tokens = 0);
 // dadd: gradient added to dx (the residual stream's direct gradient)
+// rscale / tokens / dr: the scaled branch's gradient dr = dx_total * rscale[row / tokens]
 void launch_layernorm_bwd(const uint16_t* x, const uint16_t* dy, const float* gamma,
                           const float* mean, const float* rstd, uint16_t* dx, float* dgamma,
                           float* dbeta, float* slots, long long rows, int D, hipStream_t s,
-                          const uint16_t* dadd = nullptr);
+                          const uint16_t* dadd = nullptr, const float* rscale = nullptr,
+                          int tokens = 0, uint16_t* dr = nullptr);
 void launch_gelu_fwd(const uint16_t* x, uint16_t* y, long long n, hipStream_t s);
 void launch_gelu_bwd(const uint16_t* x, const uint16_t* dy, uint16_t* dx, long long n,
                      hipStream_t s);
@@ -212,6 +217,16 @@ void launch_dropout_apply_bf16(const uint16_t* x, const uint8_t* mask, uint16_t*
                                float scale, int mode, long long inner, int C, hipStream_t s);
 void launch_dropout_apply_f32(const float* x, const uint8_t* mask, float* y, long long n,
                               float scale, int mode, long long inner, int C, hipStream_t s);
+
+// drop_path.hip: stochastic depth.  The draw fills table [branches][B] with the
+// per-sample branch scales of step state[0] and advances state[0]; thr / scale
+// [branches] are the per-branch keep thresholds (uint32 values) and 1 / (1 - p).
+void launch_drop_path_draw(float* table, long long* state, const long long* thr,
+                           const float* scale, int branches, int B, unsigned long long seed,
+                           hipStream_t s);
+// y = x * rscale[v / per] over nvec 16-byte vectors, `per` vectors per sample
+void launch_drop_path_rows(const uint16_t* x, const float* rscale, uint16_t* y, long long per,
+                           long long nvec, hipStream_t s);
 
 // conv.hip
 int conv_num_configs();

@@ -1,0 +1,23 @@
+// Counter-based Philox4x32-10 generator (Salmon et al., SC'11) shared by the
+// dropout and drop-path kernels: one call yields four 32-bit draws that are a
+// pure function of (counter, key).
+#pragma once
+
+#include "common.h"
+
+namespace dmp {
+
+__device__ __forceinline__ uint4 philox4x32_10(uint4 ctr, uint2 key) {
+  constexpr u32 M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const u32 hi0 = __umulhi(M0, ctr.x), lo0 = M0 * ctr.x;
+    const u32 hi1 = __umulhi(M1, ctr.z), lo1 = M1 * ctr.z;
+    ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
+    key.x += W0;
+    key.y += W1;
+  }
+  return ctr;
+}
+
+}  // namespace dmp

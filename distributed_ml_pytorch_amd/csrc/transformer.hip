@@ -49,29 +49,59 @@ __device__ __forceinline__ void ld8f(const float* p, float v[8]) {
 // With radd: the residual add of a pre-norm transformer block is fused in --
 // h = bf16(x + radd) is written to hout and normalised (one pass over the
 // stream instead of an add kernel plus a LayerNorm read).
-template <int LR, int MAXC>
+//
+// RS (row-scaled add, stochastic depth: drop_path.hip): row r of sample
+// r / tokens adds radd * s with s = rscale[r / tokens], product and sum rounded
+// separately; a dropped sample (s == 0) copies x bit for bit and never reads
+// radd.  RS is a template parameter: the unscaled instantiations are the code
+// they were (rscale / tokens unused there).
+__device__ __forceinline__ float scaled_add(float x, float r, float s) {
+#pragma clang fp contract(off)
+  const float t = r * s;
+  return x + t;
+}
+
+template <int LR, int MAXC, bool RS>
 __global__ void __launch_bounds__(256) layernorm_fwd_kernel(
     const u16* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
     u16* __restrict__ y, float* __restrict__ mean_out, float* __restrict__ rstd_out, long long rows,
-    int D, float eps, const u16* __restrict__ radd, u16* __restrict__ hout) {
+    int D, float eps, const u16* __restrict__ radd, u16* __restrict__ hout,
+    const float* __restrict__ rscale, int tokens) {
   constexpr int RPW = 64 / LR;
   const int lane = threadIdx.x & 63, sub = lane % LR;
   const long long row = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LR;
   const int nc = D / (8 * LR);
   const bool ok = row < rows;
   const u16* xr = x + (ok ? row : 0) * D;
+  float rs = 0.f;
+  if constexpr (RS) rs = rscale[(ok ? row : 0) / tokens];
   float v[MAXC][8];
   float s = 0.f;
 #pragma unroll
   for (int c = 0; c < MAXC; ++c) {
     if (c < nc) {
-      ld8(xr + (sub + c * LR) * 8, v[c]);
-      if (radd) {
-        float t[8];
-        ld8(radd + (ok ? row : 0) * D + (sub + c * LR) * 8, t);
+      if constexpr (RS) {
+        const bf16x8 xb = *reinterpret_cast<const bf16x8*>(xr + (sub + c * LR) * 8);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[c][k] = bf2f(f2bf(v[c][k] + t[k]));
-        if (ok) st8(hout + row * D + (sub + c * LR) * 8, v[c]);
+        for (int k = 0; k < 8; ++k) v[c][k] = bf2f(xb.v[k]);
+        if (rs != 0.f) {
+          float t[8];
+          ld8(radd + (ok ? row : 0) * D + (sub + c * LR) * 8, t);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) v[c][k] = bf2f(f2bf(scaled_add(v[c][k], t[k], rs)));
+          if (ok) st8(hout + row * D + (sub + c * LR) * 8, v[c]);
+        } else if (ok) {
+          *reinterpret_cast<bf16x8*>(hout + row * D + (sub + c * LR) * 8) = xb;
+        }
+      } else {
+        ld8(xr + (sub + c * LR) * 8, v[c]);
+        if (radd) {
+          float t[8];
+          ld8(radd + (ok ? row : 0) * D + (sub + c * LR) * 8, t);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) v[c][k] = bf2f(f2bf(v[c][k] + t[k]));
+          if (ok) st8(hout + row * D + (sub + c * LR) * 8, v[c]);
+        }
       }
 #pragma unroll
       for (int k = 0; k < 8; ++k) s += v[c][k];
@@ -123,11 +153,15 @@ __global__ void __launch_bounds__(256) layernorm_fwd_kernel(
 // single row serialises at the memory-side atomic unit once ~1000 blocks add.)
 constexpr int kLnSlots = 32;
 
-template <int LR, int MAXC>
+// RS (see the forward): the row-scaled branch's gradient dr = bf16(o * s) is a
+// second output, o being the fp32 total that is rounded into dx; +0 on the rows
+// of a dropped sample.
+template <int LR, int MAXC, bool RS>
 __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
     const u16* __restrict__ x, const u16* __restrict__ dy, const float* __restrict__ gamma,
     const float* __restrict__ mean_in, const float* __restrict__ rstd_in, u16* __restrict__ dx,
-    float* __restrict__ slots, long long rows, int D, const u16* __restrict__ dadd) {
+    float* __restrict__ slots, long long rows, int D, const u16* __restrict__ dadd,
+    const float* __restrict__ rscale, int tokens, u16* __restrict__ dr) {
   constexpr int RPW = 64 / LR;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, sub = lane % LR;
   const int nc = D / (8 * LR);
@@ -140,11 +174,12 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
   // software-pipelined over the wave's rows: the next row group's x / dy / dadd
   // (and mean / rstd) are in flight while this one is reduced and stored
   bf16x8 nx[MAXC], ny[MAXC], na[MAXC];
-  float nmean = 0.f, nrstd = 0.f;
+  float nmean = 0.f, nrstd = 0.f, nscale = 0.f;
   auto fetch = [&](long long row) {
     const long long r = row < rows ? row : 0;
     nmean = mean_in[r];
     nrstd = rstd_in[r];
+    if constexpr (RS) nscale = rscale[r / tokens];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) {
       if (c < nc) {
@@ -160,7 +195,7 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
   for (; row - lane / LR < rows; row += step) {
     const bool ok = row < rows;
     const long long r = ok ? row : 0;
-    const float mean = nmean, rstd = nrstd;
+    const float mean = nmean, rstd = nrstd, rs = nscale;
     bf16x8 cx[MAXC], cy[MAXC], ad[MAXC];
 #pragma unroll
     for (int c = 0; c < MAXC; ++c) { cx[c] = nx[c]; cy[c] = ny[c]; ad[c] = na[c]; }
@@ -203,6 +238,11 @@ __global__ void __launch_bounds__(256) layernorm_bwd_kernel(
             for (int k = 0; k < 8; ++k) o[k] += bf2f(ad[c].v[k]);
           }
           st8(dx + r * D + e0, o);
+          if constexpr (RS) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) o[k] = rs != 0.f ? o[k] * rs : 0.f;
+            st8(dr + r * D + e0, o);
+          }
         }
       }
     }
@@ -365,25 +405,25 @@ static int ln_lanes(int D) {
   return lr;
 }
 
-#define DMP_LN_LAUNCH(KERNEL, LR_, NC_, GRID, LDS, ...)                                         \
-  do {                                                                                         \
-    if ((NC_) <= 2) hipLaunchKernelGGL((KERNEL<LR_, 2>), GRID, dim3(256), LDS, s, __VA_ARGS__); \
-    else if ((NC_) == 3) hipLaunchKernelGGL((KERNEL<LR_, 3>), GRID, dim3(256), LDS, s, __VA_ARGS__); \
-    else if ((NC_) <= 4) hipLaunchKernelGGL((KERNEL<LR_, 4>), GRID, dim3(256), LDS, s, __VA_ARGS__); \
-    else hipLaunchKernelGGL((KERNEL<LR_, 8>), GRID, dim3(256), LDS, s, __VA_ARGS__);            \
+#define DMP_LN_LAUNCH(KERNEL, RS_, LR_, NC_, GRID, LDS, ...)                                          \
+  do {                                                                                               \
+    if ((NC_) <= 2) hipLaunchKernelGGL((KERNEL<LR_, 2, RS_>), GRID, dim3(256), LDS, s, __VA_ARGS__); \
+    else if ((NC_) == 3) hipLaunchKernelGGL((KERNEL<LR_, 3, RS_>), GRID, dim3(256), LDS, s, __VA_ARGS__); \
+    else if ((NC_) <= 4) hipLaunchKernelGGL((KERNEL<LR_, 4, RS_>), GRID, dim3(256), LDS, s, __VA_ARGS__); \
+    else hipLaunchKernelGGL((KERNEL<LR_, 8, RS_>), GRID, dim3(256), LDS, s, __VA_ARGS__);            \
   } while (0)
 
-#define DMP_LN_BY_LR(KERNEL, LR, NC, GRID, LDS, ...)                         \
-  do {                                                                     \
-    switch (LR) {                                                          \
-      case 64: DMP_LN_LAUNCH(KERNEL, 64, NC, GRID, LDS, __VA_ARGS__); break; \
-      case 32: DMP_LN_LAUNCH(KERNEL, 32, NC, GRID, LDS, __VA_ARGS__); break; \
-      case 16: DMP_LN_LAUNCH(KERNEL, 16, NC, GRID, LDS, __VA_ARGS__); break; \
-      case 8: DMP_LN_LAUNCH(KERNEL, 8, NC, GRID, LDS, __VA_ARGS__); break;   \
-      case 4: DMP_LN_LAUNCH(KERNEL, 4, NC, GRID, LDS, __VA_ARGS__); break;   \
-      case 2: DMP_LN_LAUNCH(KERNEL, 2, NC, GRID, LDS, __VA_ARGS__); break;   \
-      default: DMP_LN_LAUNCH(KERNEL, 1, NC, GRID, LDS, __VA_ARGS__); break;  \
-    }                                                                      \
+#define DMP_LN_BY_LR(KERNEL, RS_, LR, NC, GRID, LDS, ...)                         \
+  do {                                                                          \
+    switch (LR) {                                                               \
+      case 64: DMP_LN_LAUNCH(KERNEL, RS_, 64, NC, GRID, LDS, __VA_ARGS__); break; \
+      case 32: DMP_LN_LAUNCH(KERNEL, RS_, 32, NC, GRID, LDS, __VA_ARGS__); break; \
+      case 16: DMP_LN_LAUNCH(KERNEL, RS_, 16, NC, GRID, LDS, __VA_ARGS__); break; \
+      case 8: DMP_LN_LAUNCH(KERNEL, RS_, 8, NC, GRID, LDS, __VA_ARGS__); break;   \
+      case 4: DMP_LN_LAUNCH(KERNEL, RS_, 4, NC, GRID, LDS, __VA_ARGS__); break;   \
+      case 2: DMP_LN_LAUNCH(KERNEL, RS_, 2, NC, GRID, LDS, __VA_ARGS__); break;   \
+      default: DMP_LN_LAUNCH(KERNEL, RS_, 1, NC, GRID, LDS, __VA_ARGS__); break;  \
+    }                                                                           \
   } while (0)
 
 // D % 8 == 0 and at most 8 chunks of 8 per lane
@@ -391,18 +431,24 @@ bool layernorm_supported(int D) { return D > 0 && D % 8 == 0 && D / 8 / ln_lanes
 
 void launch_layernorm_fwd(const u16* x, const float* gamma, const float* beta, u16* y,
                           float* mean, float* rstd, long long rows, int D, float eps,
-                          hipStream_t s, const u16* radd, u16* hout) {
+                          hipStream_t s, const u16* radd, u16* hout, const float* rscale,
+                          int tokens) {
   const int lr = ln_lanes(D), nc = D / 8 / lr;
   const long long rows_per_block = 4LL * (64 / lr);
   const dim3 grid((unsigned)((rows + rows_per_block - 1) / rows_per_block));
-  DMP_LN_BY_LR(layernorm_fwd_kernel, lr, nc, grid, 0, x, gamma, beta, y, mean, rstd, rows, D, eps,
-               radd, hout);
+  if (rscale != nullptr)
+    DMP_LN_BY_LR(layernorm_fwd_kernel, true, lr, nc, grid, 0, x, gamma, beta, y, mean, rstd, rows,
+                 D, eps, radd, hout, rscale, tokens);
+  else
+    DMP_LN_BY_LR(layernorm_fwd_kernel, false, lr, nc, grid, 0, x, gamma, beta, y, mean, rstd, rows,
+                 D, eps, radd, hout, nullptr, 0);
 }
 
 // slots: [kLnSlots][2][D] fp32, zero on entry and on return (nullptr: no param grads)
 void launch_layernorm_bwd(const u16* x, const u16* dy, const float* gamma, const float* mean,
                           const float* rstd, u16* dx, float* dgamma, float* dbeta, float* slots,
-                          long long rows, int D, hipStream_t s, const u16* dadd) {
+                          long long rows, int D, hipStream_t s, const u16* dadd,
+                          const float* rscale, int tokens, u16* dr) {
   const int lr = ln_lanes(D), nc = D / 8 / lr;
   const long long rows_per_block = 4LL * (64 / lr);
   long long blocks = (rows + rows_per_block - 1) / rows_per_block;
@@ -420,8 +466,13 @@ void launch_layernorm_bwd(const u16* x, const u16* dy, const float* gamma, const
   if (blocks > cap) blocks = cap;
   const bool grads = slots != nullptr && (dgamma != nullptr || dbeta != nullptr);
   const size_t lds = grads ? (size_t)8 * D * sizeof(float) : 0;
-  DMP_LN_BY_LR(layernorm_bwd_kernel, lr, nc, dim3((unsigned)blocks), lds, x, dy, gamma, mean, rstd,
-               dx, grads ? slots : nullptr, rows, D, dadd);
+  float* sl = grads ? slots : nullptr;
+  if (rscale != nullptr)
+    DMP_LN_BY_LR(layernorm_bwd_kernel, true, lr, nc, dim3((unsigned)blocks), lds, x, dy, gamma,
+                 mean, rstd, dx, sl, rows, D, dadd, rscale, tokens, dr);
+  else
+    DMP_LN_BY_LR(layernorm_bwd_kernel, false, lr, nc, dim3((unsigned)blocks), lds, x, dy, gamma,
+                 mean, rstd, dx, sl, rows, D, dadd, nullptr, 0, nullptr);
   if (grads)
     hipLaunchKernelGGL(layernorm_param_grad_kernel, dim3((2 * D + 255) / 256), dim3(256), 0, s,
                        slots, dgamma, dbeta, D);

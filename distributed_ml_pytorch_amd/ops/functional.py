@@ -679,18 +679,24 @@ def dropout(x, p: float, training: bool, channelwise: bool = False, state=None, 
 
 
 # ----------------------------------------------------------------- layernorm
-def _ln_backward(ctx, dy, dh, gi):
-    """``(dx, dgamma, dbeta)`` of the three LayerNorm Functions: ``dh`` is the
+def _ln_backward(ctx, dy, dh, gi, rscale=None):
+    """``(dx, dgamma, dbeta)`` of the LayerNorm Functions: ``dh`` is the
     residual stream's own gradient (added inside the kernel), ``gi`` gamma's
-    position among the forward inputs (beta follows it)."""
-    x, mean, rstd = ctx.saved_tensors
+    position among the forward inputs (beta follows it).  With ``rscale`` (the
+    row-scaled add) ``dx`` is the pair ``(dx, dr)``."""
+    x, mean, rstd = ctx.saved_tensors[:3]
     gamma = ctx.gamma
     sg = GradSink(gamma, ctx.needs_input_grad[gi])
     sb = GradSink(ctx.beta, ctx.needs_input_grad[gi + 1])
     g32 = gamma.detach() if gamma is not None else None
     if dh is not None and dh.dtype != x.dtype:
         dh = dh.to(x.dtype)
-    dx = native().layernorm_bwd(x, dy.to(x.dtype), g32, mean, rstd, sg.buf, sb.buf, ctx.slots, dh)
+    if rscale is None:
+        dx = native().layernorm_bwd(x, dy.to(x.dtype), g32, mean, rstd, sg.buf, sb.buf, ctx.slots,
+                                    dh)
+    else:
+        dx = native().layernorm_bwd(x, dy.to(x.dtype), g32, mean, rstd, sg.buf, sb.buf, ctx.slots,
+                                    dh, rscale, x.numel() // x.shape[-1] // rscale.numel())
     return dx, sg.done(), sb.done()
 
 
@@ -732,6 +738,36 @@ class _AddLayerNorm(Function):
             return dh, dh, None, None, None, None
         dx, dg, db = _ln_backward(ctx, dy, dh, 2)
         return dx, dx, dg, db, None, None
+
+
+class _AddLayerNormScaled(Function):
+    """:class:`_AddLayerNorm` with the add scaled per sample (stochastic depth):
+    ``h = x + r * rscale[sample]`` inside the forward kernel, and the backward
+    kernel writes ``r``'s gradient ``dh_total * rscale[sample]`` next to ``dx``.
+    ``rscale`` is the forward's own table row, saved with it."""
+
+    @staticmethod
+    def forward(ctx, x, r, gamma, beta, eps, slots, rscale):
+        ctx.set_materialize_grads(False)
+        x = x.contiguous()
+        g32 = gamma.detach() if gamma is not None else None
+        b32 = beta.detach() if beta is not None else None
+        tokens = x.numel() // x.shape[-1] // rscale.numel()
+        y, mean, rstd, h = native().layernorm_fwd(x, g32, b32, float(eps), r.contiguous(), rscale,
+                                                  tokens)
+        ctx.save_for_backward(h, mean, rstd, rscale)
+        ctx.gamma, ctx.beta, ctx.slots = gamma, beta, slots
+        return h, y
+
+    @staticmethod
+    def backward(ctx, dh, dy):
+        rscale = ctx.saved_tensors[3]
+        if dy is None:
+            if dh is None:
+                return (None,) * 7
+            return dh, native().drop_path_rows(dh, rscale), None, None, None, None, None
+        (dx, dr), dg, db = _ln_backward(ctx, dy, dh, 2, rscale)
+        return dx, dr, dg, db, None, None, None
 
 
 class _LayerNormStream(Function):
@@ -785,16 +821,129 @@ def layernorm_supported(D: int) -> bool:
     return nch // lr <= 8
 
 
-def add_layer_norm(x, r, weight, bias, eps: float, slots=None):
+def add_layer_norm(x, r, weight, bias, eps: float, slots=None, rscale=None):
     """``h = x + r`` and ``LayerNorm(h)`` -> ``(h, y)``: one native pass for bf16 GPU
-    rows (``csrc/transformer.hip``), add + :func:`layer_norm` otherwise."""
+    rows (``csrc/transformer.hip``), add + :func:`layer_norm` otherwise.
+
+    ``rscale`` (float32 ``[B]``, a row of :func:`drop_path_table`): stochastic
+    depth, ``h = x + r * rscale[sample]`` with the product and the sum rounded
+    separately in fp32; a sample whose scale is 0 keeps ``x`` bit for bit and
+    ``r`` is not read for it."""
     if (x.is_cuda and x.dtype == torch.bfloat16 and r.dtype == torch.bfloat16
             and x.shape == r.shape and layernorm_supported(x.shape[-1])
             and (weight is None or weight.dtype == torch.float32)
             and (bias is None or bias.dtype == torch.float32)):
+        if rscale is not None:
+            return _AddLayerNormScaled.apply(x, r, weight, bias, eps, slots, rscale)
         return _AddLayerNorm.apply(x, r, weight, bias, eps, slots)
-    h = x + r
+    if rscale is None:
+        h = x + r
+    elif x.is_cuda and x.dtype == torch.bfloat16:
+        h = x + drop_path(r, rscale)      # a D the fused kernel refuses: native scaling
+    else:
+        h = scaled_add(x, r, rscale)
     return h, layer_norm(h, weight, bias, eps, slots)
+
+
+# ----------------------------------------------------------- stochastic depth
+# Per-sample drop path (Huang et al. 2016; timm's ``drop_path``) on the residual
+# branches of the ViT.  One table per training forward, ``S[j][b]`` = the scale
+# sample ``b`` applies to branch ``j``: ``1 / (1 - p_j)`` when kept, 0 when
+# dropped.  The draw of (b, j) at step ``t`` is word ``b & 3`` of
+# ``philox4x32_10(ctr=(b >> 2, j, t, "drop"), key=(seed_lo, seed_hi))``, kept
+# when it is ``>= min(int(p_j * 2^32), 0xFFFFFFFF)``: a pure function of
+# (seed, step, branch, sample), the same bits from the kernel
+# (``csrc/drop_path.hip``) and from the torch form below.
+DROP_DOMAIN = 0x64726F70        # "drop": counter word 3 (0x64617461 "data" is the data stream's)
+
+
+def drop_path_rates(drop_path: float, depth: int) -> list:
+    """Rate of each of ``depth`` blocks: the linear ramp ``drop_path * i /
+    (depth - 1)`` (timm's ``linspace(0, drop_path, depth)``); one block gets
+    ``drop_path`` itself."""
+    p = float(drop_path)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"drop path rate must be in [0, 1), got {drop_path}")
+    if depth < 1:
+        raise ValueError(f"depth must be >= 1, got {depth}")
+    if depth == 1:
+        return [p]
+    return [p * i / (depth - 1) for i in range(depth)]
+
+
+def drop_path_consts(rates, device=None):
+    """``(thresholds int64, scales float32)`` of the branches with drop rates
+    ``rates``: keep iff the draw ``>= thresholds[j]``; ``scales[j] = float32(1) /
+    float32(1 - p_j)`` (exactly 1 at ``p_j == 0``, where every draw is kept)."""
+    for p in rates:
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f"drop path rate must be in [0, 1), got {p}")
+    thr = torch.tensor([min(int(float(p) * 4294967296.0), 0xFFFFFFFF) for p in rates],
+                       dtype=torch.int64)
+    keep = torch.tensor([1.0 - float(p) for p in rates], dtype=torch.float32)
+    scales = torch.ones_like(keep) / keep
+    return thr.to(device), scales.to(device)
+
+
+def drop_path_table(state, thresholds, scales, batch: int, seed: int):
+    """The ``[branches, batch]`` float32 scale table of step ``state[0]`` (a
+    device-side int64 counter, advanced by 1): one native launch on the GPU, the
+    same draws in torch on the CPU."""
+    if state.is_cuda:
+        return native().drop_path_draw(state, thresholds, scales, int(batch), int(seed))
+    from ..utils.device_data import philox4x32_10
+
+    t = int(state[0]) & 0xFFFFFFFF
+    nb = scales.numel()
+    b = torch.arange(batch, dtype=torch.int64)
+    j = torch.arange(nb, dtype=torch.int64)[:, None]
+    z = torch.zeros(nb, batch, dtype=torch.int64)
+    words = philox4x32_10((z + (b >> 2), z + j, z + t, z + DROP_DOMAIN),
+                          (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF))
+    word = torch.stack(words, 0).gather(0, (z + (b & 3))[None])[0]
+    keep = word >= thresholds.to(torch.int64)[:, None]
+    state[0] += 1
+    return torch.where(keep, scales[:, None].expand(nb, batch),
+                       torch.zeros((), dtype=torch.float32))
+
+
+def _sample_scale(rscale, like):
+    return rscale.view(-1, *([1] * (like.dim() - 1)))
+
+
+def scaled_add(x, r, rscale):
+    """The specification of the row-scaled add in torch: ``x + r * s`` per sample,
+    fp32 product and sum rounded separately, one rounding to ``x``'s dtype; a
+    dropped sample (``s == 0``) is ``x`` itself and takes nothing from ``r``."""
+    stock_gpu("drop_path (scaled add)", x)
+    s = _sample_scale(rscale, x)
+    h = (x.float() + r.float() * s).to(x.dtype)
+    return torch.where(s != 0, h, x)
+
+
+class _DropPath(Function):
+    @staticmethod
+    def forward(ctx, x, rscale):
+        ctx.save_for_backward(rscale)
+        return native().drop_path_rows(x, rscale)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (rscale,) = ctx.saved_tensors
+        return native().drop_path_rows(dy, rscale), None
+
+
+def drop_path(x, rscale):
+    """``x * rscale[sample]`` (float32 ``[B]`` scales of :func:`drop_path_table`) for
+    a residual branch that is added outside the fused add+LayerNorm: the native
+    row kernel for bf16 GPU input, torch otherwise."""
+    if rscale is None:
+        return x
+    if (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] == rscale.numel()
+            and (x.numel() // x.shape[0]) % 8 == 0):
+        return _DropPath.apply(x, rscale)
+    stock_gpu("drop_path", x)
+    return (x.float() * _sample_scale(rscale, x)).to(x.dtype)
 
 
 def layer_norm(x, weight, bias, eps: float, slots=None):

@@ -29,7 +29,7 @@ from dataclasses import asdict, dataclass, field
 import torch
 import torch.distributed as dist
 
-from ..models import build_model
+from ..models import build_model, is_vit
 from ..ops.eval_fold import fold_session
 from ..ops.functional import softmax_cross_entropy, softmax_cross_entropy_mix, unit_grad
 from ..parallel.arena import attach_arena
@@ -119,6 +119,7 @@ class TrainConfig:
     cutmix: float = 0.0               # CutMix alpha, 0 = off (device_data only)
     mix_prob: float = 1.0             # probability that a batch is mixed at all
     mix_switch_prob: float = 0.5      # with both on: probability of CutMix over Mixup
+    drop_path: float = 0.0            # stochastic depth rate of the last ViT block; 0 = off
     verbose: bool = True
     extra: dict = field(default_factory=dict)
 
@@ -140,6 +141,7 @@ class Worker:
         check_push_wire_config(cfg, client)
         check_delay_comp_config(cfg, info, client)
         check_device_data_config(cfg, info)
+        check_drop_path_config(cfg)
         if cfg.deterministic:
             cfg = self.cfg = enable_determinism(cfg)
         torch.manual_seed(cfg.seed + info.rank)
@@ -157,7 +159,8 @@ class Worker:
                     "in bf16 (fp32 master weights and accumulation), so this would train "
                     "entirely on stock MIOpen / hipBLASLt / ATen kernels.  Use --dtype bf16, "
                     "or --deterministic for the explicit fp32 stock-kernel oracle mode.")
-        model, shape, nc = build_model(cfg.model, cfg.num_classes)
+        # (the model draws its drop-path seed from torch's generator, seeded per rank above)
+        model, shape, nc = build_model(cfg.model, cfg.num_classes, drop_path=cfg.drop_path)
         self.input_shape, self.num_classes = shape, nc
         self.model = model.to(self.device)
         shadow = self.compute_dtype if self.compute_dtype != torch.float32 else None
@@ -549,6 +552,17 @@ def check_device_data_config(cfg: TrainConfig, info: DistInfo):
                          "(fp32 compute); use --dtype bf16 or the host loader")
 
 
+def check_drop_path_config(cfg: TrainConfig):
+    """Stochastic depth lives in the ViT's fused residual adds: a rate outside
+    [0, 1), or a model without them, is an error at start-up."""
+    if not 0.0 <= cfg.drop_path < 1.0:
+        raise ValueError(f"--drop-path must be in [0, 1), got {cfg.drop_path}")
+    if cfg.drop_path > 0 and not is_vit(cfg.model):
+        raise ValueError(f"--drop-path {cfg.drop_path} with --model {cfg.model}: stochastic depth "
+                         "exists for the ViT models only (the ResNets' residual add lives in "
+                         "the BatchNorm kernels)")
+
+
 def make_device_loaders(cfg: TrainConfig, info: DistInfo, w: "Worker"):
     """Train and test :class:`DeviceLoader` of a run with ``device_data``: the
     train loader augments and mixes as configured and shards as the host path does
@@ -667,6 +681,7 @@ def run_training(cfg: TrainConfig, info: DistInfo):
     check_push_wire_config(cfg)
     check_delay_comp_config(cfg, info)
     check_device_data_config(cfg, info)
+    check_drop_path_config(cfg)
     ps_groups = None
     central = cfg.mode == "asgd" and cfg.ps == "central" and info.is_distributed
     if central:
