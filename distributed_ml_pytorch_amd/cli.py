@@ -133,6 +133,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--drop-path", type=float, default=0.0, metavar="RATE",
                    help="ViT models: stochastic depth (drop path), per sample; RATE in [0, 1) is "
                         "the last block's, the blocks ramp up to it linearly (0 = off)")
+    p.add_argument("--model-ema", type=float, default=0.0, metavar="DECAY",
+                   help="keep an exponential moving average of the weights and BatchNorm "
+                        "statistics with this decay in [0, 1) and evaluate it next to the live "
+                        "model (0 = off); updated inside the fused optimizer pass")
+    p.add_argument("--model-ema-every", type=int, default=None, metavar="K",
+                   help="with --model-ema: update the average every K optimizer steps (default 1)")
+    p.add_argument("--model-ema-warmup", action="store_true", default=False,
+                   help="with --model-ema: decay min(DECAY, (1 + u) / (10 + u)) at EMA update u")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--log-dir", default="log")
     p.add_argument("--no-eval", action="store_true", default=False)
@@ -143,6 +151,12 @@ def build_parser() -> argparse.ArgumentParser:
 
 def config_from_args(a) -> TrainConfig:
     mode = "single" if a.no_distributed else a.mode
+    if a.model_ema == 0 and (a.model_ema_every is not None or a.model_ema_warmup):
+        raise ValueError("--model-ema-every / --model-ema-warmup need --model-ema DECAY")
+    if a.model_ema_every is not None and a.model_ema_every < 1:
+        raise ValueError(f"--model-ema-every must be >= 1, got {a.model_ema_every}")
+    if not 0.0 <= a.model_ema < 1.0:
+        raise ValueError(f"--model-ema must be in [0, 1), got {a.model_ema}")
     return TrainConfig(
         model=a.model, num_classes=a.num_classes, dataset=a.dataset, data_dir=a.data_dir,
         n_train=a.n_train, n_test=a.n_test, batch_size=a.batch_size,
@@ -161,7 +175,9 @@ def config_from_args(a) -> TrainConfig:
         adam_eps=a.adam_eps, clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,
         lr_min=a.lr_min, schedule_steps=a.schedule_steps, device_data=a.device_data,
         augment=a.augment, crop_pad=a.crop_pad, mixup=a.mixup, cutmix=a.cutmix,
-        mix_prob=a.mix_prob, mix_switch_prob=a.mix_switch_prob, drop_path=a.drop_path)
+        mix_prob=a.mix_prob, mix_switch_prob=a.mix_switch_prob, drop_path=a.drop_path,
+        model_ema=a.model_ema, model_ema_every=a.model_ema_every or 1,
+        model_ema_warmup=a.model_ema_warmup)
 
 
 def main(argv=None):

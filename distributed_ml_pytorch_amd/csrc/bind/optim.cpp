@@ -15,6 +15,17 @@ void check_flat_opt(const optional<Tensor>& t, at::ScalarType dt, int64_t n, con
   if (has(t)) check_flat(*t, dt, n, name);
 }
 
+bool overlaps(const Tensor& a, const Tensor& b);
+
+// the model EMA of a step (None: off): fp32 [n], contiguous, on p's device, not p
+float* ema_ptr(const optional<Tensor>& ema, const Tensor& p, int64_t n) {
+  if (!has(ema)) return nullptr;
+  check_flat(*ema, at::kFloat, n, "ema");
+  TORCH_CHECK(ema->is_contiguous() && ema->device() == p.device() && !overlaps(*ema, p),
+              "ema must be contiguous, on the parameters' device and must not alias p");
+  return ema->data_ptr<float>();
+}
+
 void asgd_fused_step(Tensor g, Tensor p, optional<Tensor> acc, optional<Tensor> mom,
                      optional<Tensor> w16, double lr, double wd, double momentum,
                      double dampening, bool nesterov) {
@@ -59,7 +70,7 @@ void optim_hyper(Tensor hyper, optional<Tensor> g, optional<Tensor> partials) {
 
 void asgd_fused_step_dev(Tensor g, Tensor p, optional<Tensor> acc, optional<Tensor> mom,
                          optional<Tensor> w16, Tensor hyper, double wd, double momentum,
-                         double dampening, bool nesterov) {
+                         double dampening, bool nesterov, optional<Tensor> ema) {
   const int64_t n = flat_len(p, "flat arena length");
   check_flat(p, at::kFloat, n, "p");
   check_flat(g, at::kFloat, n, "g");
@@ -71,13 +82,14 @@ void asgd_fused_step_dev(Tensor g, Tensor p, optional<Tensor> acc, optional<Tens
   dmp::launch_asgd_fused_step_dev(g.data_ptr<float>(), p.data_ptr<float>(),
                                   ptr_or_null<float>(acc), ptr_or_null<float>(mom),
                                   bf16_or_null(w16), n, hyper.data_ptr<float>(), (float)wd,
-                                  (float)momentum, (float)dampening, nesterov, cur_stream());
+                                  (float)momentum, (float)dampening, nesterov, cur_stream(),
+                                  ema_ptr(ema, p, n));
 }
 
 // `decay`: uint8 mask, one entry per 64-element arena block (None: decay all)
 void adamw_fused_step(Tensor g, Tensor p, optional<Tensor> acc, Tensor m, Tensor v,
                       optional<Tensor> w16, optional<Tensor> decay, Tensor hyper, double wd,
-                      double eps) {
+                      double eps, optional<Tensor> ema) {
   const int64_t n = flat_len(p, "flat arena length");
   check_flat(p, at::kFloat, n, "p");
   check_flat(g, at::kFloat, n, "g");
@@ -98,7 +110,38 @@ void adamw_fused_step(Tensor g, Tensor p, optional<Tensor> acc, Tensor m, Tensor
   dmp::launch_adamw_fused_step(g.data_ptr<float>(), p.data_ptr<float>(), ptr_or_null<float>(acc),
                                m.data_ptr<float>(), v.data_ptr<float>(), bf16_or_null(w16),
                                ptr_or_null<const uint8_t>(decay), n, hyper.data_ptr<float>(),
-                               (float)wd, (float)eps, cur_stream());
+                               (float)wd, (float)eps, cur_stream(), ema_ptr(ema, p, n));
+}
+
+// p <-> e in place, w16 = bf16(new p): evaluation on the averaged weights
+void arena_swap(Tensor p, Tensor ema, optional<Tensor> w16) {
+  const int64_t n = flat_len(p, "flat arena length");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat_opt(w16, at::kBFloat16, n, "w16");
+  TORCH_CHECK(ema.defined(), "arena_swap: ema must be a tensor");
+  float* e = ema_ptr(ema, p, n);
+  TORCH_CHECK(p.is_contiguous() && (!has(w16) || w16->device() == p.device()),
+              "arena_swap: p must be contiguous and w16 on its device");
+  dmp::launch_arena_swap(p.data_ptr<float>(), e, bf16_or_null(w16), n, cur_stream());
+}
+
+// EMA of the model's fp32 buffers.  `table`: int64 [rows, 3] on the device, a row
+// is (data pointer of the live buffer, offset into `flat`, numel); mode 0
+// averages flat from the live buffers with D / O of `hyper`, mode 1 exchanges.
+// The caller vouches for the pointers; offsets are checked again on the device.
+void ema_buffers(Tensor table, Tensor flat, Tensor hyper, int64_t mode) {
+  TORCH_CHECK(table.is_cuda() && table.scalar_type() == at::kLong && table.is_contiguous() &&
+                  table.dim() == 2 && table.size(1) == 3,
+              "table must be a contiguous int64 GPU tensor of shape [rows, 3], got ",
+              table.scalar_type(), " ", table.sizes());
+  TORCH_CHECK(flat.is_cuda() && flat.scalar_type() == at::kFloat && flat.is_contiguous() &&
+                  flat.dim() == 1,
+              "flat must be a contiguous 1-D fp32 GPU tensor");
+  check_hyper(hyper, flat);
+  TORCH_CHECK(table.device() == flat.device(), "table must be on the device of flat");
+  TORCH_CHECK(mode == 0 || mode == 1, "ema_buffers: mode is 0 (average) or 1 (exchange)");
+  dmp::launch_ema_buffers(i64(table), (int)table.size(0), flat.data_ptr<float>(), flat.numel(),
+                          hyper.data_ptr<float>(), (int)mode, cur_stream());
 }
 
 // fp32 or bf16 wire payload of n elements (`name`s it in the message)
@@ -382,8 +425,18 @@ void bind_optim(pybind11::module_& m) {
         "fp32 words of an optimizer's device-resident hyper block");
   m.def("optim_hyper", &optim_hyper, "advance a hyper block one step (norm, clip, schedule)");
   m.def("asgd_fused_step_dev", &asgd_fused_step_dev,
-        "fused flat ASGD/SGD update, lr and gradient scale from the hyper block");
-  m.def("adamw_fused_step", &adamw_fused_step, "fused flat AdamW update");
+        "fused flat ASGD/SGD update, lr and gradient scale from the hyper block", py::arg("g"),
+        py::arg("p"), py::arg("acc"), py::arg("mom"), py::arg("w16"), py::arg("hyper"),
+        py::arg("wd"), py::arg("momentum"), py::arg("dampening"), py::arg("nesterov"),
+        py::arg("ema") = py::none());
+  m.def("adamw_fused_step", &adamw_fused_step, "fused flat AdamW update", py::arg("g"),
+        py::arg("p"), py::arg("acc"), py::arg("m"), py::arg("v"), py::arg("w16"),
+        py::arg("decay"), py::arg("hyper"), py::arg("wd"), py::arg("eps"),
+        py::arg("ema") = py::none());
+  m.def("arena_swap", &arena_swap, "exchange p and its EMA in place, refresh the bf16 shadow",
+        py::arg("p"), py::arg("ema"), py::arg("w16") = py::none());
+  m.def("ema_buffers", &ema_buffers, "EMA update / exchange of the model's fp32 buffers",
+        py::arg("table"), py::arg("flat"), py::arg("hyper"), py::arg("mode"));
   m.def("ps_apply", &ps_apply, "parameter-server delta apply", py::arg("shard"), py::arg("delta"),
         py::arg("mirror") = py::none(), py::arg("scale") = 1.0, py::arg("atomic") = false,
         py::arg("factor") = py::none());

@@ -17,12 +17,23 @@ void launch_asgd_fused_step(const float* g, float* p, float* acc, float* mom, ui
 // read lr / gradient scale / bias corrections from it.
 int optim_hyper_words();
 void launch_optim_hyper(float* hyper, const float* g, float* partial, long long n, hipStream_t s);
+// `ema` non-null: the fp32 moving average of p [n], updated in the same pass on
+// the steps the hyper block marks (O != 0); null = the kernels without it.
 void launch_asgd_fused_step_dev(const float* g, float* p, float* acc, float* mom, uint16_t* w16,
                                 long long n, const float* hyper, float wd, float momentum,
-                                float dampening, bool nesterov, hipStream_t s);
+                                float dampening, bool nesterov, hipStream_t s,
+                                float* ema = nullptr);
 void launch_adamw_fused_step(const float* g, float* p, float* acc, float* m, float* v,
                              uint16_t* w16, const uint8_t* decay, long long n, const float* hyper,
-                             float wd, float eps, hipStream_t s);
+                             float wd, float eps, hipStream_t s, float* ema = nullptr);
+// Model EMA (parallel/ema.py).  launch_arena_swap: p <-> e in place, w16 =
+// bf16(new p) (null = no shadow); n % 4 == 0.  launch_ema_buffers: one block per
+// row (live pointer, offset into `flat`, numel) of the int64 device `table`;
+// mode 0 averages flat <- D flat + O live with D / O from the hyper block, mode
+// 1 exchanges live <-> flat.  A row that does not fit in flat_numel is skipped.
+void launch_arena_swap(float* p, float* e, uint16_t* w16, long long n, hipStream_t s);
+void launch_ema_buffers(const long long* table, int rows, float* flat, long long flat_numel,
+                        const float* hyper, int mode, hipStream_t s);
 // A payload on the wire: n fp32 or bf16 elements, or the MX8 payload of n
 // elements (mx8_layout(n) bytes, 16-B aligned, n % 4 == 0; parallel/wire8.py)
 struct Wire {

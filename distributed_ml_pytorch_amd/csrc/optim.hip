@@ -27,17 +27,46 @@ __device__ __forceinline__ void store_bf16x4(bf16x4* __restrict__ dst, long long
   dst[i] = o;
 }
 
+// Model EMA of one element: e = D e + O p with the two products and the sum each
+// rounded on its own, the bits of torch's e.mul(D).add(p.mul(O)) on the CPU
+// (parallel/fused_optim.py).  Plain operators with contraction off for these
+// statements, as in mx8_axpy: the __fmul_rn / __fadd_rn intrinsics inline as
+// operations that still carry the header's contract flag, and the backend
+// fuses them into one multiply-add (seen in the assembly).
+// timm's form: about an ulp of rounding noise per update, and no stalling once
+// O |p - e| drops below an ulp of e.
+__device__ __forceinline__ float ema_lane(float e, float p, float D, float O) {
+#pragma clang fp contract(off)
+  const float a = D * e;
+  const float b = O * p;
+  return a + b;
+}
+
+__device__ __forceinline__ void ema_update4(float4* __restrict__ e, long long i, const float4& p,
+                                            float D, float O) {
+  float4 ev = e[i];
+  ev.x = ema_lane(ev.x, p.x, D, O); ev.y = ema_lane(ev.y, p.y, D, O);
+  ev.z = ema_lane(ev.z, p.z, D, O); ev.w = ema_lane(ev.w, p.w, D, O);
+  e[i] = ev;
+}
+
 // One grid-stride pass of the SGD update, shared by the two kernels below.
 // `gscale` (device-hyper variant only, SCALE = true) multiplies the gradient
-// before weight decay and momentum see it; __fmul_rn keeps that product out of
-// FMA contraction, so gscale == 1 leaves every later rounding where the
-// by-value kernel has it (bitwise-equal results).
-template <bool SCALE>
+// before weight decay and momentum see it.  That product is rounded on its own:
+// below it is only ever an addend or a factor of the next operation, never a
+// product that feeds a sum, so there is no multiply-add to contract it into (the
+// __fmul_rn spelling alone would not prevent one, see ema_lane).  gscale == 1
+// therefore leaves every later rounding where the by-value kernel has it
+// (bitwise-equal results, pinned by a test).
+// EMA (device-hyper variant only): `ema` is updated from the new p under the
+// grid-uniform branch O != 0, so a step between two EMA updates moves none of
+// its bytes.  Without EMA the three trailing arguments do not exist in the code.
+template <bool SCALE, bool EMA = false>
 __device__ __forceinline__ void asgd_fused_step_body(
     const float4* __restrict__ g, float4* __restrict__ p, float4* __restrict__ acc,
     float4* __restrict__ mom, bf16x4* __restrict__ w16, long long n4, float lr, float gscale,
     float weight_decay, float momentum, float dampening, int nesterov, long long first,
-    long long stride) {
+    long long stride, float4* __restrict__ ema = nullptr, float D = 1.f, float O = 0.f) {
   for (long long i = first; i < n4; i += stride) {
     float4 gv = g[i];
     float4 pv = p[i];
@@ -71,6 +100,9 @@ __device__ __forceinline__ void asgd_fused_step_body(
     pv.x += d.x; pv.y += d.y; pv.z += d.z; pv.w += d.w;
     p[i] = pv;
     if (w16) store_bf16x4(w16, i, pv);
+    if constexpr (EMA) {
+      if (O != 0.f) ema_update4(ema, i, pv, D, O);
+    }
   }
 }
 
@@ -111,7 +143,14 @@ enum HyperWord {
   kHGradScale = 14,
   kHOmb1 = 15,      // 1 - beta1, rounded from the host's double (as torch passes it)
   kHOmb2 = 16,      // 1 - beta2
-  kHyperWords = 20,
+  // model EMA (parallel/ema.py): e = D e + O p on the steps with t % K == 0
+  kHEmaD = 17,      // fp32(d_u) of this step; 1 on a step without an EMA update
+  kHEmaO = 18,      // fp32(1 - d_u), the difference taken in fp64; 0 = EMA untouched
+  kHEmaU = 19,      // int32  u = t / K: EMA updates applied so far
+  kHEmaDecay = 20,  // base decay
+  kHEmaEvery = 21,  // int32  K; 0: EMA off, none of 17..19 is written
+  kHEmaWarm = 22,   // int32  1: d_u = min(decay, (1 + u) / (10 + u))
+  kHyperWords = 24,
 };
 
 __device__ __forceinline__ float hyper_load(const float* hyper, int w) {
@@ -156,6 +195,9 @@ __global__ void __launch_bounds__(256) optim_hyper_kernel(float* __restrict__ hy
   const int t = hi[kHStep] + 1;
   const double base = (double)hyper[kHBaseLr], lmin = (double)hyper[kHLrMin];
   const int warm = hi[kHWarmup], total = hi[kHTotal];
+  // read with the other inputs, before any store: one round trip for all of them
+  const int every = hi[kHEmaEvery], ema_warm = hi[kHEmaWarm];
+  const float ema_decay = hyper[kHEmaDecay];
   double lr = base;
   if (hi[kHKind] == 1) {
     if (t <= warm) lr = base * (double)t / (double)warm;
@@ -170,21 +212,51 @@ __global__ void __launch_bounds__(256) optim_hyper_kernel(float* __restrict__ hy
   hyper[kHBc1] = (float)(1.0 - pow(b1, (double)t));
   hyper[kHBc2] = (float)(1.0 - pow(b2, (double)t));
   hyper[kHNorm] = norm;
+  // model EMA: every K-th step is EMA update u = t / K with decay d_u; the steps
+  // between publish D = 1, O = 0, which the step kernels read as "leave e alone"
+  if (every > 0) {
+    const int u = t / every;
+    float D = 1.f, O = 0.f;
+    if (t % every == 0) {
+      double d = (double)ema_decay;
+      if (ema_warm) {
+        const double w = (1.0 + (double)u) / (10.0 + (double)u);
+        d = d < w ? d : w;
+      }
+      D = (float)d;
+      O = (float)(1.0 - d);
+    }
+    hyper[kHEmaD] = D;
+    hyper[kHEmaO] = O;
+    hi[kHEmaU] = u;
+  }
 }
 
 // SGD with lr and the gradient scale read from the hyper block (schedules and
 // clipping for the SGD paths); otherwise asgd_fused_step_kernel.
+// EMA: one trailing argument, the fp32 moving average of p [n]; the <false>
+// instantiation has neither the argument nor a trace of it in its code.
+template <bool EMA, typename... E>
 __global__ void __launch_bounds__(256) asgd_fused_step_dev_kernel(
     const float4* __restrict__ g, float4* __restrict__ p, float4* __restrict__ acc,
     float4* __restrict__ mom, bf16x4* __restrict__ w16, long long n4,
     const float* __restrict__ hyper, float weight_decay, float momentum, float dampening,
-    int nesterov) {
+    int nesterov, E... ema) {
+  static_assert(sizeof...(E) == (EMA ? 1 : 0), "EMA: exactly one float4* ema");
   const float lr = hyper_load(hyper, kHLr);
   const float gscale = hyper_load(hyper, kHGscale);
   const long long stride = (long long)gridDim.x * blockDim.x;
-  asgd_fused_step_body<true>(g, p, acc, mom, w16, n4, lr, gscale, weight_decay, momentum,
-                             dampening, nesterov,
-                             (long long)blockIdx.x * blockDim.x + threadIdx.x, stride);
+  if constexpr (EMA) {
+    const float D = hyper_load(hyper, kHEmaD), O = hyper_load(hyper, kHEmaO);
+    asgd_fused_step_body<true, true>(g, p, acc, mom, w16, n4, lr, gscale, weight_decay, momentum,
+                                     dampening, nesterov,
+                                     (long long)blockIdx.x * blockDim.x + threadIdx.x, stride,
+                                     ema..., D, O);
+  } else {
+    asgd_fused_step_body<true>(g, p, acc, mom, w16, n4, lr, gscale, weight_decay, momentum,
+                               dampening, nesterov,
+                               (long long)blockIdx.x * blockDim.x + threadIdx.x, stride);
+  }
 }
 
 // AdamW (torch.optim.AdamW's form) in one pass over the flat arena:
@@ -197,11 +269,19 @@ __global__ void __launch_bounds__(256) asgd_fused_step_dev_kernel(
 //         null = decay everything.
 // Division and square root are the correctly rounded ones: the pass moves
 // ~38 B per element and has the VALU time to spare.
+// EMA: as asgd_fused_step_dev_kernel, 8 B per element more on an EMA step.
+template <bool EMA, typename... E>
 __global__ void __launch_bounds__(256) adamw_fused_step_kernel(
     const float4* __restrict__ g, float4* __restrict__ p, float4* __restrict__ acc,
     float4* __restrict__ m, float4* __restrict__ v, bf16x4* __restrict__ w16,
     const u8* __restrict__ decay, long long n4, const float* __restrict__ hyper,
-    float weight_decay, float eps) {
+    float weight_decay, float eps, E... ema) {
+  static_assert(sizeof...(E) == (EMA ? 1 : 0), "EMA: exactly one float4* ema");
+  float emaD = 1.f, emaO = 0.f;
+  if constexpr (EMA) {
+    emaD = hyper_load(hyper, kHEmaD);
+    emaO = hyper_load(hyper, kHEmaO);
+  }
   const float lr = hyper_load(hyper, kHLr);
   const float gscale = hyper_load(hyper, kHGscale);
   const float b1 = hyper_load(hyper, kHBeta1), b2 = hyper_load(hyper, kHBeta2);
@@ -236,6 +316,55 @@ __global__ void __launch_bounds__(256) adamw_fused_step_kernel(
       acc[i] = a;
     }
     if (w16) store_bf16x4(w16, i, pn);
+    if constexpr (EMA) {
+      if (emaO != 0.f) ema_update4(ema..., i, pn, emaD, emaO);
+    }
+  }
+}
+
+// ---- model EMA outside the step kernels (parallel/ema.py) -------------------
+// In-place exchange p <-> e with w16 = bf16(new p) in the same pass: evaluation
+// on the averaged weights swaps them in and, by a second application, out again
+// (bit for bit: the exchange moves values, the cast is a function of p).
+__global__ void __launch_bounds__(256) arena_swap_kernel(float4* __restrict__ p,
+                                                         float4* __restrict__ e,
+                                                         bf16x4* __restrict__ w16, long long n4) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const float4 pv = p[i], ev = e[i];
+    p[i] = ev;
+    e[i] = pv;
+    if (w16) store_bf16x4(w16, i, ev);
+  }
+}
+
+// The model's floating-point buffers (BatchNorm running statistics), which are
+// no part of the arena: one block per row of `table`, int64 (live pointer,
+// element offset into `flat`, numel).  Scalar accesses: a running-stat tensor
+// promises no 16-byte multiple.  mode 0: flat = D flat + O live with D / O of
+// the hyper block and the step kernels' skip; mode 1: exchange live <-> flat.
+// A row that does not lie inside flat[0, flat_numel) is skipped.
+__global__ void __launch_bounds__(256) ema_buffers_kernel(const long long* __restrict__ table,
+                                                          float* __restrict__ flat,
+                                                          long long flat_numel,
+                                                          const float* __restrict__ hyper,
+                                                          int mode) {
+  const long long* row = table + 3 * (long long)blockIdx.x;
+  float* live = reinterpret_cast<float*>(row[0]);
+  const long long off = row[1], n = row[2];
+  if (live == nullptr || off < 0 || n < 0 || off > flat_numel || n > flat_numel - off) return;
+  float* e = flat + off;
+  if (mode == 0) {
+    const float D = hyper_load(hyper, kHEmaD), O = hyper_load(hyper, kHEmaO);
+    if (O == 0.f) return;
+    for (long long i = threadIdx.x; i < n; i += blockDim.x)
+      e[i] = ema_lane(e[i], live[i], D, O);
+  } else {
+    for (long long i = threadIdx.x; i < n; i += blockDim.x) {
+      const float a = live[i], b = e[i];
+      live[i] = b;
+      e[i] = a;
+    }
   }
 }
 
@@ -808,20 +937,46 @@ void launch_optim_hyper(float* hyper, const float* g, float* partial, long long 
 
 void launch_asgd_fused_step_dev(const float* g, float* p, float* acc, float* mom, u16* w16,
                                 long long n, const float* hyper, float wd, float momentum,
-                                float dampening, bool nesterov, hipStream_t s) {
+                                float dampening, bool nesterov, hipStream_t s, float* ema) {
   const long long n4 = n / 4;
-  hipLaunchKernelGGL(asgd_fused_step_dev_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                     (const float4*)g, (float4*)p, (float4*)acc, (float4*)mom, (bf16x4*)w16, n4,
-                     hyper, wd, momentum, dampening, nesterov ? 1 : 0);
+  const dim3 grid(stream_grid(n4, 256));
+  if (ema)
+    hipLaunchKernelGGL((asgd_fused_step_dev_kernel<true, float4*>), grid, dim3(256), 0, s,
+                       (const float4*)g, (float4*)p, (float4*)acc, (float4*)mom, (bf16x4*)w16, n4,
+                       hyper, wd, momentum, dampening, nesterov ? 1 : 0, (float4*)ema);
+  else
+    hipLaunchKernelGGL(asgd_fused_step_dev_kernel<false>, grid, dim3(256), 0, s,
+                       (const float4*)g, (float4*)p, (float4*)acc, (float4*)mom, (bf16x4*)w16, n4,
+                       hyper, wd, momentum, dampening, nesterov ? 1 : 0);
 }
 
 void launch_adamw_fused_step(const float* g, float* p, float* acc, float* m, float* v, u16* w16,
                              const u8* decay, long long n, const float* hyper, float wd,
-                             float eps, hipStream_t s) {
+                             float eps, hipStream_t s, float* ema) {
   const long long n4 = n / 4;
-  hipLaunchKernelGGL(adamw_fused_step_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s,
-                     (const float4*)g, (float4*)p, (float4*)acc, (float4*)m, (float4*)v,
-                     (bf16x4*)w16, decay, n4, hyper, wd, eps);
+  const dim3 grid(stream_grid(n4, 256));
+  if (ema)
+    hipLaunchKernelGGL((adamw_fused_step_kernel<true, float4*>), grid, dim3(256), 0, s,
+                       (const float4*)g, (float4*)p, (float4*)acc, (float4*)m, (float4*)v,
+                       (bf16x4*)w16, decay, n4, hyper, wd, eps, (float4*)ema);
+  else
+    hipLaunchKernelGGL(adamw_fused_step_kernel<false>, grid, dim3(256), 0, s,
+                       (const float4*)g, (float4*)p, (float4*)acc, (float4*)m, (float4*)v,
+                       (bf16x4*)w16, decay, n4, hyper, wd, eps);
+}
+
+void launch_arena_swap(float* p, float* e, u16* w16, long long n, hipStream_t s) {
+  if (n <= 0) return;
+  const long long n4 = n / 4;
+  hipLaunchKernelGGL(arena_swap_kernel, dim3(stream_grid(n4, 256)), dim3(256), 0, s, (float4*)p,
+                     (float4*)e, (bf16x4*)w16, n4);
+}
+
+void launch_ema_buffers(const long long* table, int rows, float* flat, long long flat_numel,
+                        const float* hyper, int mode, hipStream_t s) {
+  if (rows <= 0) return;
+  hipLaunchKernelGGL(ema_buffers_kernel, dim3(rows), dim3(256), 0, s, table, flat, flat_numel,
+                     hyper, mode);
 }
 
 // One launch shape per form: the plain apply takes 16 B per lane (stream_grid),

@@ -27,7 +27,8 @@ from torch.optim.optimizer import Optimizer, required
 
 from .arena import attach_arena, get_arena
 from .clients import GlooPSClient, LocalPSClient, PSClient, check_push_wire
-from .fused_optim import FusedOptimCore, sync_base_lr
+from .ema import ModelEma
+from .fused_optim import FusedOptimCore, check_ema_options, sync_base_lr
 
 
 def default_client(**kw) -> PSClient:
@@ -44,8 +45,14 @@ class Asynchronous(Optimizer):
                  pull_mode: str = "overwrite", wire_dtype: torch.dtype = torch.float32,
                  shadow_dtype: torch.dtype | None | str = "auto", optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0,
-                 schedule=None, push_wire: str = "same", push_topk: int = 8):
-        """``push_wire="mx8"``: pushes travel as block-scaled 8-bit payloads
+                 schedule=None, push_wire: str = "same", push_topk: int = 8,
+                 ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False):
+        """``ema_decay > 0``: an exponential moving average of the parameters and the
+        floating-point buffers is kept by the update pass (:mod:`.fused_optim`,
+        :mod:`.ema`; ``self.ema.applied()`` evaluates with it).  A pull landing is no
+        EMA event: the average sees the landed values at its next update.
+
+        ``push_wire="mx8"``: pushes travel as block-scaled 8-bit payloads
         (:mod:`.wire8`) and the accumulator keeps the quantisation residual, so
         nothing is lost, only delayed to the next push.  ``push_wire="topk"``:
         a push carries the ``push_topk`` (1..32) largest entries of every
@@ -60,6 +67,7 @@ class Asynchronous(Optimizer):
             raise ValueError("n_push and n_pull must be >= 1")
         if optimizer not in ("sgd", "adamw"):
             raise ValueError(f"unknown optimizer {optimizer!r}; 'sgd' or 'adamw'")
+        check_ema_options(ema_decay, ema_every, ema_warmup)
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
                         weight_decay=weight_decay)
         super().__init__(params, defaults)
@@ -81,15 +89,16 @@ class Asynchronous(Optimizer):
         self.acc = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
         self._mom_steps = 0
         self.mom = torch.zeros_like(self.acc) if momentum and optimizer == "sgd" else None
-        # AdamW, clipping or a per-step schedule: the update reads lr and the
-        # gradient scale from a device-resident hyper block (fused_optim.py);
-        # plain constant-lr SGD keeps the by-value kernel
+        # AdamW, clipping, a per-step schedule or a model EMA: the update reads lr
+        # and the gradient scale from a device-resident hyper block
+        # (fused_optim.py); plain constant-lr SGD keeps the by-value kernel
         self.core = None
-        if optimizer == "adamw" or max_grad_norm > 0 or schedule is not None:
+        if optimizer == "adamw" or max_grad_norm > 0 or schedule is not None or ema_decay > 0:
             self.core = FusedOptimCore(arena, optimizer, lr, betas=betas, eps=eps,
                                        weight_decay=weight_decay, momentum=momentum,
                                        nesterov=nesterov, max_grad_norm=max_grad_norm,
-                                       schedule=schedule, model=model)
+                                       schedule=schedule, model=model, ema_decay=ema_decay,
+                                       ema_every=ema_every, ema_warmup=ema_warmup)
         self.idx = 0
         self.timer = _NO_TIMER      # a utils.metrics.StepTimer when the trainer wires one
         if client is None:
@@ -102,6 +111,11 @@ class Asynchronous(Optimizer):
         self.client = client
         self.client.attach(self)
         self.client.init()
+        # the average starts from the parameters as the PS client left them
+        self.ema = None
+        if ema_decay > 0:
+            self.core.reset_ema()
+            self.ema = ModelEma(model, self.core, self.client)
         self._nat = None
         if dev.type == "cuda":
             from ..ops._ext import native
@@ -162,6 +176,8 @@ class Asynchronous(Optimizer):
     def local_step(self):
         """Device-only half of a step (graph-capturable): fused accumulate + SGD."""
         self._local_update(self.param_groups[0]["lr"])
+        if self.ema is not None:
+            self.ema.update_buffers()
         self.arena.bump()
         self.client.in_compute = False
 

@@ -30,7 +30,8 @@ import torch.distributed as dist
 from torch.optim.optimizer import Optimizer
 
 from .arena import FlatArena
-from .fused_optim import FusedOptimCore, sync_base_lr
+from .ema import ModelEma
+from .fused_optim import FusedOptimCore, check_ema_options, sync_base_lr
 
 
 _CAL_MB = (2.0, 4.0, 8.0, 16.0, 32.0, 64.0)
@@ -163,21 +164,28 @@ class FusedSGD(Optimizer):
 
     def __init__(self, params, arena: FlatArena, lr: float, momentum: float = 0.0,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
-                 grad_scale: float = 1.0, max_grad_norm: float = 0.0, schedule=None):
+                 grad_scale: float = 1.0, max_grad_norm: float = 0.0, schedule=None,
+                 model=None, ema_decay: float = 0.0, ema_every: int = 1,
+                 ema_warmup: bool = False):
+        """``ema_decay > 0``: model EMA (:mod:`.ema`); ``model`` names the buffers
+        that are averaged with the parameters (None: parameters only)."""
+        check_ema_options(ema_decay, ema_every, ema_warmup)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening,
                                       nesterov=nesterov, weight_decay=weight_decay))
         self.arena = arena
         self.grad_scale = grad_scale
         self.mom = torch.zeros_like(arena.p32) if momentum else None
         self._mom_steps = 0
-        # clipping or a per-step schedule: lr and the gradient scale (1/W
-        # included) come from the device-resident hyper block (fused_optim.py)
+        # clipping, a per-step schedule or a model EMA: lr and the gradient scale
+        # (1/W included) come from the device-resident hyper block (fused_optim.py)
         self.core = None
-        if max_grad_norm > 0 or schedule is not None:
+        if max_grad_norm > 0 or schedule is not None or ema_decay > 0:
             self.core = FusedOptimCore(arena, "sgd", lr, weight_decay=weight_decay,
                                        momentum=momentum, nesterov=nesterov,
                                        grad_scale=grad_scale, max_grad_norm=max_grad_norm,
-                                       schedule=schedule)
+                                       schedule=schedule, ema_decay=ema_decay,
+                                       ema_every=ema_every, ema_warmup=ema_warmup)
+        self.ema = ModelEma(model, self.core) if ema_decay > 0 else None
         self._nat = None
         if arena.device.type == "cuda":
             from ..ops._ext import native
@@ -211,6 +219,8 @@ class FusedSGD(Optimizer):
             self._mom_steps += 1
             sync_base_lr(self.core, lr)
             self.core.step(a, None, self.mom, damp)
+            if self.ema is not None:
+                self.ema.update_buffers()
             return
         if self.grad_scale != 1.0:
             # fold the 1/W average into lr (and rescale weight decay so wd*p is not scaled)
@@ -252,12 +262,16 @@ class FusedAdamW(Optimizer):
 
     def __init__(self, params, arena: FlatArena, lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.01, grad_scale: float = 1.0,
-                 max_grad_norm: float = 0.0, schedule=None, model=None):
+                 max_grad_norm: float = 0.0, schedule=None, model=None,
+                 ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.arena = arena
         self.core = FusedOptimCore(arena, "adamw", lr, betas=betas, eps=eps,
                                    weight_decay=weight_decay, grad_scale=grad_scale,
-                                   max_grad_norm=max_grad_norm, schedule=schedule, model=model)
+                                   max_grad_norm=max_grad_norm, schedule=schedule, model=model,
+                                   ema_decay=ema_decay, ema_every=ema_every,
+                                   ema_warmup=ema_warmup)
+        self.ema = ModelEma(model, self.core) if ema_decay > 0 else None
 
     def zero_grad(self, set_to_none: bool = False):
         self.arena.ensure_grads_attached()
@@ -280,3 +294,5 @@ class FusedAdamW(Optimizer):
         self.arena.bump()
         sync_base_lr(self.core, self.param_groups[0]["lr"])
         self.core.step(self.arena, None)
+        if self.ema is not None:
+            self.ema.update_buffers()

@@ -28,9 +28,25 @@ One step (the CPU path below is the readable specification; the GPU path is
 shifts) and for the names a model lists in ``no_weight_decay()``; AdamW's
 decoupled weight decay skips them.  It is held as one ``uint8`` per 64-element
 arena block (every parameter starts on such a boundary, ``arena.ALIGN``).
+
+Model EMA (``ema_decay > 0``; evaluation through :mod:`.ema`): a flat fp32
+buffer ``e`` of the arena's length, a copy of ``p32`` when the optimizer is
+built, averaged in the same pass after the parameter update of step ``t``::
+
+    t % K != 0:  e untouched                       (K = ema_every)
+    u   = t / K                                    (EMA update index, 1-based)
+    d_u = min(decay, (1 + u) / (10 + u))  with ema_warmup, else decay    (fp64)
+    D, O = fp32(d_u), fp32(1 - d_u)                (the difference in fp64)
+    e   = fl32(fl32(D * e) + fl32(O * p_new))      (three roundings, no FMA)
+
+timm's form: it carries about one ulp of rounding noise per update and never
+stalls.  ``decay`` enters as its fp32 rounding, as ``base_lr`` does.  A pull
+landing (``Asynchronous``) changes ``p32`` between two steps and is no EMA
+event: the average sees the landed values at its next update.
 """
 from __future__ import annotations
 
+import logging
 import math
 from dataclasses import asdict, dataclass
 
@@ -38,12 +54,49 @@ import torch
 
 from .arena import ALIGN, FlatArena
 
+_LOG = logging.getLogger(__name__)
+
 # hyper-block words (csrc/optim.hip enum HyperWord)
 H_STEP, H_LR, H_GSCALE, H_BC1, H_BC2, H_NORM, H_KIND, H_BASE_LR, H_LR_MIN, H_WARMUP, H_TOTAL, \
-    H_BETA1, H_BETA2, H_MAX_NORM, H_GRAD_SCALE, H_OMB1, H_OMB2 = range(17)
-HYPER_WORDS = 20
+    H_BETA1, H_BETA2, H_MAX_NORM, H_GRAD_SCALE, H_OMB1, H_OMB2, H_EMA_D, H_EMA_O, H_EMA_U, \
+    H_EMA_DECAY, H_EMA_EVERY, H_EMA_WARM = range(23)
+HYPER_WORDS = 24
 _KINDS = {"constant": 0, "warmup_cosine": 1}
 _PARTIALS = 1024            # launch_sumsq_partial's block cap
+
+
+def _f32(x: float) -> float:
+    """``x`` rounded to fp32, as a Python float."""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def check_ema_options(decay: float, every: int = 1, warmup: bool = False) -> float:
+    """Validate the model-EMA options -> the decay as its fp32 rounding.
+    ``decay`` in [0, 1) (0 = off), ``every >= 1``; ``every`` / ``warmup`` without a
+    decay are an error, never silently ignored."""
+    if not (isinstance(decay, (int, float)) and 0.0 <= decay < 1.0):
+        raise ValueError(f"model EMA decay must be in [0, 1), got {decay!r}")
+    if int(every) != every or every < 1:
+        raise ValueError(f"model EMA interval (every) must be an integer >= 1, got {every!r}")
+    d32 = _f32(decay)
+    if d32 >= 1.0:
+        raise ValueError(f"model EMA decay {decay!r} rounds to 1 in fp32: the average would "
+                         "never move")
+    if decay == 0 and (every != 1 or warmup):
+        raise ValueError("model EMA interval / warmup given without a decay (model EMA is off)")
+    return d32
+
+
+def ema_coeffs(decay: float, every: int, warmup: bool, t: int):
+    """``(u, D, O)`` of optimizer step ``t`` (1-based): the EMA update index and
+    the two published fp32 scalars; ``D = 1, O = 0`` on a step without an update."""
+    u = t // every
+    if t % every:
+        return u, 1.0, 0.0
+    d = _f32(decay)
+    if warmup:
+        d = min(d, (1 + u) / (10 + u))
+    return u, _f32(d), _f32(1.0 - d)
 
 
 @dataclass(frozen=True)
@@ -126,7 +179,8 @@ class FusedOptimCore:
                  betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  momentum: float = 0.0, nesterov: bool = False, grad_scale: float = 1.0,
                  max_grad_norm: float = 0.0, schedule=None,
-                 model: torch.nn.Module | None = None):
+                 model: torch.nn.Module | None = None, ema_decay: float = 0.0,
+                 ema_every: int = 1, ema_warmup: bool = False):
         if kind not in ("sgd", "adamw"):
             raise ValueError(f"unknown optimizer {kind!r}; 'sgd' or 'adamw'")
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
@@ -146,6 +200,9 @@ class FusedOptimCore:
         self.grad_scale = float(grad_scale)
         self.max_grad_norm = float(max_grad_norm)
         self.schedule = make_schedule(schedule)
+        self.ema_decay = check_ema_options(ema_decay, ema_every, ema_warmup)
+        self.ema_every = int(ema_every)
+        self.ema_warmup = bool(ema_warmup)
         dev = arena.device
         self.native = None
         if dev.type == "cuda":
@@ -169,6 +226,33 @@ class FusedOptimCore:
         self.hyper = None
         if self.native is not None:
             self._write_hyper()
+        # model EMA: a copy of the parameters as they are now (an optimizer whose
+        # PS client re-seeds them afterwards calls reset_ema() again)
+        self.ema = None
+        self._ema_last = (1.0, 0.0)         # (D, O) of the last step, CPU path
+        if self.ema_decay > 0:
+            self.ema = torch.empty(arena.numel, dtype=torch.float32, device=dev)
+            self.reset_ema()
+
+    # -------------------------------------------------------------- model EMA
+    @torch.no_grad()
+    def reset_ema(self):
+        """``e <- p32`` (construction, and a resume whose checkpoint holds no EMA)."""
+        if self.ema is not None:
+            self.ema.copy_(self.arena.p32)
+
+    @property
+    def ema_updates(self) -> int:
+        """EMA updates applied so far (a device read-back on the GPU)."""
+        if self.ema is None:
+            return 0
+        if self.hyper is None:
+            return self._t // self.ema_every
+        return int(self._read_hyper().view(torch.int32)[H_EMA_U])
+
+    def ema_last(self):
+        """``(D, O)`` of the last step (CPU path; the kernels read the hyper block)."""
+        return self._ema_last
 
     # ------------------------------------------------------------ hyper block
     def _write_hyper(self):
@@ -193,6 +277,13 @@ class FusedOptimCore:
         h[H_MAX_NORM] = self.max_grad_norm
         h[H_GRAD_SCALE] = self.grad_scale
         h[H_OMB1], h[H_OMB2] = 1.0 - b1, 1.0 - b2
+        if self.ema_decay > 0:
+            # between steps: "no update" until the next step publishes its own
+            h[H_EMA_D], h[H_EMA_O] = 1.0, 0.0
+            hi[H_EMA_U] = t // self.ema_every
+            h[H_EMA_DECAY] = self.ema_decay
+            hi[H_EMA_EVERY] = self.ema_every
+            hi[H_EMA_WARM] = int(self.ema_warmup)
         if self.hyper is None:
             self.hyper = h.to(self.arena.device)
         else:
@@ -250,11 +341,11 @@ class FusedOptimCore:
             self.native.optim_hyper(self.hyper, a.g32 if clip else None, self.partials)
             if self.kind == "adamw":
                 self.native.adamw_fused_step(a.g32, a.p32, acc, self.m, self.v, a.w16, self.mask,
-                                             self.hyper, self.weight_decay, self.eps)
+                                             self.hyper, self.weight_decay, self.eps, self.ema)
             else:
                 self.native.asgd_fused_step_dev(a.g32, a.p32, acc, mom, a.w16, self.hyper,
                                                 self.weight_decay, self.momentum, dampening,
-                                                self.nesterov)
+                                                self.nesterov, self.ema)
             return
         g = a.g32
         clipc = 1.0
@@ -288,6 +379,11 @@ class FusedOptimCore:
         p.copy_(new)
         if a.w16 is not None:
             a.w16.copy_(p)
+        if self.ema is not None:
+            _, D, O = ema_coeffs(self.ema_decay, self.ema_every, self.ema_warmup, t)
+            self._ema_last = (D, O)
+            if O != 0.0:
+                self.ema.copy_(self.ema.mul(D).add(p.mul(O)))
 
     def _decay_elems(self) -> torch.Tensor:
         if getattr(self, "_decay_f", None) is None:
@@ -296,10 +392,13 @@ class FusedOptimCore:
 
     # ------------------------------------------------------------- checkpoint
     def state_dict(self) -> dict:
-        return {"kind": self.kind, "t": self.t, "base_lr": self.base_lr,
-                "schedule": asdict(self.schedule),
-                "m": self.m.detach().cpu() if self.m is not None else None,
-                "v": self.v.detach().cpu() if self.v is not None else None}
+        sd = {"kind": self.kind, "t": self.t, "base_lr": self.base_lr,
+              "schedule": asdict(self.schedule),
+              "m": self.m.detach().cpu() if self.m is not None else None,
+              "v": self.v.detach().cpu() if self.v is not None else None}
+        if self.ema is not None:      # a run without EMA writes the keys it always wrote
+            sd.update(ema=self.ema.detach().cpu(), ema_updates=self.ema_updates)
+        return sd
 
     def load_state_dict(self, sd: dict):
         if sd.get("kind", self.kind) != self.kind:
@@ -313,3 +412,20 @@ class FusedOptimCore:
             self.schedule = make_schedule(sd["schedule"])
         self.base_lr = float(sd.get("base_lr", self.base_lr))
         self._resync(int(sd.get("t", 0)))
+        self._ema_last = (1.0, 0.0)
+        # EMA state of a checkpoint is ignored with EMA off; a checkpoint without
+        # it starts the average from the parameters that were just loaded
+        if self.ema is not None:
+            e = sd.get("ema")
+            if e is not None and e.numel() == self.ema.numel():
+                with torch.no_grad():
+                    self.ema.copy_(e)
+                if int(sd.get("ema_updates", 0)) != self._t // self.ema_every:
+                    _LOG.warning("model EMA: the checkpoint counts %s EMA updates, step %d at "
+                                 "interval %d gives %d; continuing with the latter",
+                                 sd.get("ema_updates"), self._t, self.ema_every,
+                                 self._t // self.ema_every)
+            else:
+                _LOG.warning("model EMA: the checkpoint holds no EMA of this arena; starting "
+                             "the average from the loaded parameters")
+                self.reset_ema()

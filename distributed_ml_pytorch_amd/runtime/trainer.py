@@ -38,7 +38,7 @@ from ..parallel.async_sharded import AsyncShardedPSClient
 from ..parallel.clients import (MX8_FLAVOURS, GlooPSClient, LocalPSClient, RcclPSClient,
                                 ShardedPSClient, SharedPSClient, check_push_wire)
 from ..parallel.ddp import BucketedAllReduce, FusedAdamW, FusedSGD
-from ..parallel.fused_optim import Schedule
+from ..parallel.fused_optim import Schedule, check_ema_options
 from ..parallel.server import ParameterServer, make_ps_groups
 from ..parallel.staleness import check_policy
 from ..utils import checkpoint as ckpt
@@ -120,6 +120,9 @@ class TrainConfig:
     mix_prob: float = 1.0             # probability that a batch is mixed at all
     mix_switch_prob: float = 0.5      # with both on: probability of CutMix over Mixup
     drop_path: float = 0.0            # stochastic depth rate of the last ViT block; 0 = off
+    model_ema: float = 0.0            # decay of the model EMA (parallel/ema.py); 0 = off
+    model_ema_every: int = 1          # EMA update every K optimizer steps
+    model_ema_warmup: bool = False    # decay min(d, (1 + u) / (10 + u)) at EMA update u
     verbose: bool = True
     extra: dict = field(default_factory=dict)
 
@@ -142,6 +145,7 @@ class Worker:
         check_delay_comp_config(cfg, info, client)
         check_device_data_config(cfg, info)
         check_drop_path_config(cfg)
+        check_model_ema_config(cfg)
         if cfg.deterministic:
             cfg = self.cfg = enable_determinism(cfg)
         torch.manual_seed(cfg.seed + info.rank)
@@ -194,6 +198,11 @@ class Worker:
             total = cfg.schedule_steps or cfg.max_steps or \
                 cfg.epochs * max(1, cfg.n_train // cfg.batch_size)
             okw["schedule"] = Schedule("warmup_cosine", cfg.warmup_steps, total, cfg.lr_min)
+        sgd_kw = {}
+        if cfg.model_ema > 0:
+            okw.update(ema_decay=cfg.model_ema, ema_every=cfg.model_ema_every,
+                       ema_warmup=cfg.model_ema_warmup)
+            sgd_kw["model"] = self.model       # FusedSGD: the buffers that are averaged
         adam = dict(betas=(cfg.beta1, cfg.beta2), eps=cfg.adam_eps)
         if cfg.mode == "asgd":
             client = client if client is not None else self._make_client(ps_groups)
@@ -216,14 +225,15 @@ class Worker:
                                       grad_scale=1.0 / world, model=self.model, **adam, **okw)
             else:
                 self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
-                                    weight_decay=cfg.weight_decay, grad_scale=1.0 / world, **okw)
+                                    weight_decay=cfg.weight_decay, grad_scale=1.0 / world, **okw,
+                                    **sgd_kw)
         elif cfg.mode == "single":
             if cfg.optimizer == "adamw":
                 self.opt = FusedAdamW(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
                                       model=self.model, **adam, **okw)
             else:
                 self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
-                                    weight_decay=cfg.weight_decay, **okw)
+                                    weight_decay=cfg.weight_decay, **okw, **sgd_kw)
         else:
             raise ValueError(f"unknown mode {cfg.mode!r}")
         if isinstance(self.opt, Asynchronous):
@@ -457,14 +467,24 @@ class Worker:
         return loss.detach(), hits
 
     @torch.no_grad()
-    def evaluate(self, loader, max_batches: int | None = None, per_class: bool = False):
+    def evaluate(self, loader, max_batches: int | None = None, per_class: bool = False,
+                 ema: bool = False):
         """Mean loss and accuracy over ALL test batches (reference used the last batch
         only, main.py:127); restores train mode afterwards (D6).
+
+        ``ema``: evaluate the averaged model (``--model-ema``): parameters and
+        buffers are exchanged with their averages for the pass and back afterwards.
 
         ``per_class``: also return the [C, C] confusion matrix (rows = true class),
         from which :func:`~..utils.metrics.classification_report` prints the
         reference's verbose per-class precision/recall/F1 table (main.py:127-131).
         """
+        if ema:
+            avg = getattr(self.opt, "ema", None)
+            if avg is None:
+                raise ValueError("evaluate(ema=True) needs a run with model_ema > 0")
+            with avg.applied():
+                return self.evaluate(loader, max_batches, per_class)
         was = self.model.training
         self.model.eval()
         tot_loss = torch.zeros((), device=self.device)
@@ -561,6 +581,15 @@ def check_drop_path_config(cfg: TrainConfig):
         raise ValueError(f"--drop-path {cfg.drop_path} with --model {cfg.model}: stochastic depth "
                          "exists for the ViT models only (the ResNets' residual add lives in "
                          "the BatchNorm kernels)")
+
+
+def check_model_ema_config(cfg: TrainConfig):
+    """Model EMA options: decay in [0, 1), interval >= 1, and neither the interval
+    nor the decay warm-up without a decay -- an error at start-up."""
+    try:
+        check_ema_options(cfg.model_ema, cfg.model_ema_every, cfg.model_ema_warmup)
+    except ValueError as e:
+        raise ValueError(f"--model-ema / --model-ema-every / --model-ema-warmup: {e}") from None
 
 
 def make_device_loaders(cfg: TrainConfig, info: DistInfo, w: "Worker"):
@@ -682,6 +711,7 @@ def run_training(cfg: TrainConfig, info: DistInfo):
     check_delay_comp_config(cfg, info)
     check_device_data_config(cfg, info)
     check_drop_path_config(cfg)
+    check_model_ema_config(cfg)
     ps_groups = None
     central = cfg.mode == "asgd" and cfg.ps == "central" and info.is_distributed
     if central:
@@ -743,6 +773,9 @@ def run_training(cfg: TrainConfig, info: DistInfo):
                         f"(loss {float(loss):.4g}); lower --lr or pass --no-divergence-check")
                 if cfg.evaluate:
                     row["test_loss"], row["test_accuracy"] = w.evaluate(test_loader)
+                    if cfg.model_ema > 0:
+                        row["ema_test_loss"], row["ema_test_accuracy"] = \
+                            w.evaluate(test_loader, ema=True)
                 log.flush_pending()
                 if cfg.verbose:
                     print("Timestamp: {timestamp} | Iteration: {iteration:6} | "
@@ -765,11 +798,16 @@ def run_training(cfg: TrainConfig, info: DistInfo):
                 # the reference's verbose eval prints sklearn's per-class report
                 # (/root/reference/example/main.py:127-131)
                 print(classification_report(conf), flush=True)
+            if cfg.model_ema > 0 and cfg.verbose:      # only ever printed: no pass without it
+                el, ea = w.evaluate(test_loader, ema=True)
+                print(f"epoch {epoch}: model EMA test loss {el:.4f} test accuracy {ea:.4f}",
+                      flush=True)
         if done:
             break
     w.finish()
     elapsed = time.perf_counter() - t_start
     final = w.evaluate(test_loader) if cfg.evaluate else (float("nan"), float("nan"))
+    final_ema = w.evaluate(test_loader, ema=True) if cfg.evaluate and cfg.model_ema > 0 else None
     if cfg.checkpoint:
         ckpt.save_worker_checkpoint(_worker_ckpt(cfg, info), w.model, w.opt, w.step_idx)
     from ..utils.metrics import log_path
@@ -780,6 +818,8 @@ def run_training(cfg: TrainConfig, info: DistInfo):
     res = {"role": "worker", "rank": info.rank, "steps": w.step_idx, "elapsed_s": elapsed,
            "samples_per_sec": meter.rate(), "test_loss": final[0], "test_accuracy": final[1],
            "data": source, "log": path, "preflight": pf}
+    if final_ema is not None:
+        res["ema_test_loss"], res["ema_test_accuracy"] = final_ema
     if isinstance(w.opt, Asynchronous):
         res.update(w.opt.stats())
     res["phases"] = w.timer.summary()

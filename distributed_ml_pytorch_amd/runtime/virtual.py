@@ -29,6 +29,9 @@ class VirtualWorkers:
             raise ValueError("need at least one virtual worker")
         if cfg.mode != "asgd":
             raise ValueError("virtual workers run the asynchronous (asgd) mode")
+        if cfg.model_ema > 0:
+            raise ValueError("--model-ema is not supported with virtual workers (K averages "
+                             "on one device)")
         device = device or (torch.device("cuda", 0) if torch.cuda.is_available() and cfg.cuda
                             else torch.device("cpu"))
         self.device = device

@@ -11,9 +11,12 @@ Files are written atomically (tmp + rename) and loaded with
 """
 from __future__ import annotations
 
+import logging
 import os
 
 import torch
+
+_LOG = logging.getLogger(__name__)
 
 
 def _atomic_save(obj, path: str):
@@ -54,6 +57,11 @@ def save_worker_checkpoint(path: str, model: torch.nn.Module, optimizer=None, st
         if core is not None:
             # AdamW moments, step count and schedule (parallel/fused_optim.py)
             sd["opt"].update(core.state_dict())
+        ema = getattr(optimizer, "ema", None)
+        if ema is not None:
+            # averaged model buffers (parallel/ema.py); the averaged parameters are
+            # part of the core's state above
+            sd["ema"] = ema.state_dict()
         client = getattr(optimizer, "client", None)
         if client is not None:
             # PS state held on this worker (in-process master / its sharded-PS shard)
@@ -109,6 +117,13 @@ def load_worker_optimizer(path: str, optimizer) -> None:
         core = getattr(optimizer, "core", None)
         if core is not None and "t" in o:     # absent in checkpoints of plain SGD runs
             core.load_state_dict(o)
+        elif core is not None and core.ema is not None:
+            _LOG.warning("model EMA: the checkpoint holds no EMA; starting the average from "
+                         "the loaded parameters")
+            core.reset_ema()
+    ema = getattr(optimizer, "ema", None)
+    if ema is not None:       # EMA state in a checkpoint is ignored when EMA is off
+        ema.load_state_dict(sd.get("ema"))
     client = getattr(optimizer, "client", None)
     if client is not None and sd.get("client"):
         client.load_state_dict(sd["client"])
