@@ -503,13 +503,33 @@ __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) gemm_kernel(GemmArgs g) 
       if (stats) {
         // the RPI row lanes of each 8-column segment, then one atomic per
         // column per wave into slot (block % kBnSlots)
+        if constexpr ((CPR & (CPR - 1)) == 0) {
 #pragma unroll
-        for (int off = CPR; off < 64; off <<= 1)
+          for (int off = CPR; off < 64; off <<= 1)
 #pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            s_sum[e] += __shfl_xor(s_sum[e], off, 64);
-            s_sq[e] += __shfl_xor(s_sq[e], off, 64);
+            for (int e = 0; e < 8; ++e) {
+              s_sum[e] += __shfl_xor(s_sum[e], off, 64);
+              s_sq[e] += __shfl_xor(s_sq[e], off, 64);
+            }
+        } else {
+          // 48-column wave tiles (BN 192): CPR = 6 segments per row, lane = lrow *
+          // CPR + ch, so an XOR butterfly over the lane id would add other columns'
+          // sums; a shift-down tree over the RPI row lanes of a segment instead
+          // (before step s a lane holds rows lrow .. lrow + s - 1)
+#pragma unroll
+          for (int s = 1; s < RPI; s <<= 1) {
+            const bool take = lane_on && lrow + s < RPI;
+            const int src = take ? lane + s * CPR : lane;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const float a = __shfl(s_sum[e], src, 64), b = __shfl(s_sq[e], src, 64);
+              if (take) {
+                s_sum[e] += a;
+                s_sq[e] += b;
+              }
+            }
           }
+        }
         if (lrow == 0) {
           const int slot = (int)(blockIdx.x % kBnSlots);
 #pragma unroll
