@@ -115,11 +115,24 @@ def build_parser() -> argparse.ArgumentParser:
                    help="keep the dataset on the device as uint8 and assemble every batch with "
                         "one native kernel (gather, crop / flip, normalise) straight into the "
                         "step's input buffers: no host loader, no upload, no cast")
-    p.add_argument("--augment", default="none", choices=["none", "crop", "flip", "crop_flip"],
+    p.add_argument("--augment", default="none",
+                   choices=["none", "crop", "flip", "crop_flip", "rrc", "rrc_flip"],
                    help="--device-data: per-sample random crop (zero padding --crop-pad) and / "
-                        "or horizontal flip of the training batches")
-    p.add_argument("--crop-pad", type=int, default=4, metavar="P",
-                   help="--augment crop: zero padding of the random crop, 0..16")
+                        "or horizontal flip of the training batches; rrc / rrc_flip: a random "
+                        "resized crop (--rrc-scale, --rrc-ratio) of the stored image, resampled "
+                        "to the model's input size")
+    p.add_argument("--crop-pad", type=int, default=None, metavar="P",
+                   help="--augment crop: zero padding of the random crop, 0..16 (default 4)")
+    p.add_argument("--rrc-scale", type=float, nargs=2, default=(0.08, 1.0), metavar=("LO", "HI"),
+                   help="--augment rrc: range of the box area as a fraction of the stored "
+                        "image (default 0.08 1)")
+    p.add_argument("--rrc-ratio", type=float, nargs=2, default=(3.0 / 4.0, 4.0 / 3.0),
+                   metavar=("LO", "HI"),
+                   help="--augment rrc: range of the box's aspect ratio, log-uniform "
+                        "(default 0.75 1.3333)")
+    p.add_argument("--stored-size", type=int, default=0, metavar="S",
+                   help="--dataset synthetic with --augment rrc: generate and keep S x S images "
+                        "while the model's input stays its own size (default: the input size)")
     p.add_argument("--mixup", type=float, default=0.0, metavar="ALPHA",
                    help="--device-data: Mixup of the training batches, lam ~ Beta(ALPHA, ALPHA) "
                         "per batch, blended in the batch assembler (0 = off)")
@@ -157,6 +170,9 @@ def config_from_args(a) -> TrainConfig:
         raise ValueError(f"--model-ema-every must be >= 1, got {a.model_ema_every}")
     if not 0.0 <= a.model_ema < 1.0:
         raise ValueError(f"--model-ema must be in [0, 1), got {a.model_ema}")
+    if a.crop_pad is not None and a.augment in ("rrc", "rrc_flip"):
+        raise ValueError(f"--crop-pad belongs to --augment crop; --augment {a.augment} pads "
+                         "nothing")
     return TrainConfig(
         model=a.model, num_classes=a.num_classes, dataset=a.dataset, data_dir=a.data_dir,
         n_train=a.n_train, n_test=a.n_test, batch_size=a.batch_size,
@@ -174,7 +190,9 @@ def config_from_args(a) -> TrainConfig:
         deterministic=a.deterministic, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
         adam_eps=a.adam_eps, clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,
         lr_min=a.lr_min, schedule_steps=a.schedule_steps, device_data=a.device_data,
-        augment=a.augment, crop_pad=a.crop_pad, mixup=a.mixup, cutmix=a.cutmix,
+        augment=a.augment, crop_pad=4 if a.crop_pad is None else a.crop_pad,
+        rrc_scale=tuple(a.rrc_scale), rrc_ratio=tuple(a.rrc_ratio), stored_size=a.stored_size,
+        mixup=a.mixup, cutmix=a.cutmix,
         mix_prob=a.mix_prob, mix_switch_prob=a.mix_switch_prob, drop_path=a.drop_path,
         model_ema=a.model_ema, model_ema_every=a.model_ema_every or 1,
         model_ema_warmup=a.model_ema_warmup)

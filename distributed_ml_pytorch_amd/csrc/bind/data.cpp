@@ -112,6 +112,154 @@ bool batch_assemble_is_staged(Tensor data) {
                                     (int)data.size(3));
 }
 
+// ------------------------------------------------ random-resized-crop form
+// (data_rrc.hip).  Exactly one of `table` (int16 [T, 2] box sizes on the GPU) and
+// `box` ((y0, x0, bh, bw), applied to every sample) says where a view comes from.
+struct RrcCall {
+  int64_t N, Hs, Ws, C, Ho, Wo, T;
+  int box[4];
+  bool fixed;
+};
+
+RrcCall check_assemble_rrc(const Tensor& data, const Tensor& labels, const Tensor& lut,
+                           const Tensor& index, int64_t count, const optional<Tensor>& table,
+                           const optional<std::vector<int64_t>>& box, const Tensor& out_x,
+                           const Tensor& out_y, const optional<Tensor>& draws, int64_t epoch,
+                           int64_t path, bool check_table) {
+  TORCH_CHECK(data.is_cuda() && data.scalar_type() == at::kByte && data.dim() == 4 &&
+                  data.is_contiguous(),
+              "batch_assemble_rrc: data must be a contiguous uint8 [N, H, W, C] GPU tensor");
+  RrcCall r{};
+  r.N = data.size(0), r.Hs = data.size(1), r.Ws = data.size(2), r.C = data.size(3);
+  TORCH_CHECK(dmp::guard::dataset_ok(r.N, r.Hs, r.Ws, r.C),
+              "batch_assemble_rrc: a dataset needs 1..", dmp::guard::kDatasetMaxChannels,
+              " channels and N*H*W*C < 2 GiB, got ", data.sizes());
+  TORCH_CHECK(out_x.dim() == 4, "batch_assemble_rrc: out_x must be [>= ", count, ", ", r.C,
+              ", Ho, Wo], got ", out_x.sizes());
+  r.Ho = out_x.size(2), r.Wo = out_x.size(3);
+  TORCH_CHECK(count >= 0 && dmp::guard::rrc_ok(count, r.Hs, r.Ws, r.C, r.Ho, r.Wo),
+              "batch_assemble_rrc: stored and output extents must lie in 1..",
+              dmp::guard::kRrcMaxExtent, " and the batch under 2 GiB of bf16; got ", data.sizes(),
+              " -> ", out_x.sizes(), ", count ", count);
+  check_out_x(out_x, count, r.C, r.Ho, r.Wo);
+  TORCH_CHECK(epoch >= 0 && epoch <= 0xffffffffLL, "batch_assemble_rrc: epoch out of range");
+  TORCH_CHECK(path == -1 || path == 0,
+              "batch_assemble_rrc: path is -1 (automatic) or 0 (direct)");
+  TORCH_CHECK(labels.is_cuda() && labels.scalar_type() == at::kLong && labels.is_contiguous() &&
+                  labels.numel() == r.N,
+              "batch_assemble_rrc: labels must be a contiguous int64 GPU tensor of ", r.N,
+              " elements");
+  TORCH_CHECK(lut.is_cuda() && lut.scalar_type() == at::kBFloat16 && lut.is_contiguous() &&
+                  lut.dim() == 2 && lut.size(0) == r.C && lut.size(1) == 256,
+              "batch_assemble_rrc: lut must be a contiguous bf16 [", r.C, ", 256] GPU tensor");
+  TORCH_CHECK(index.is_cuda() && index.scalar_type() == at::kInt && index.is_contiguous() &&
+                  index.numel() >= count,
+              "batch_assemble_rrc: index must be a contiguous int32 GPU tensor of >= ", count,
+              " elements");
+  TORCH_CHECK(out_y.is_cuda() && out_y.scalar_type() == at::kLong && out_y.is_contiguous() &&
+                  out_y.numel() >= count,
+              "batch_assemble_rrc: out_y must be a contiguous int64 GPU tensor of >= ", count,
+              " elements");
+  if (has(draws))
+    TORCH_CHECK(draws->is_cuda() && draws->scalar_type() == at::kShort &&
+                    draws->is_contiguous() && draws->numel() >= 5 * count &&
+                    draws->device() == data.device(),
+                "batch_assemble_rrc: draws must be a contiguous int16 [>= ", count,
+                ", 5] tensor on ", data.device());
+  for (const Tensor* t : {&labels, &lut, &index, &out_x, &out_y})
+    TORCH_CHECK(t->device() == data.device(), "batch_assemble_rrc: every tensor must be on ",
+                data.device(), ", got one on ", t->device());
+  r.fixed = box.has_value();
+  TORCH_CHECK(r.fixed != has(table),
+              "batch_assemble_rrc: give either a box table or a fixed box, not both or neither");
+  if (r.fixed) {
+    TORCH_CHECK(box->size() == 4 && dmp::guard::rrc_box_ok(r.Hs, r.Ws, (*box)[0], (*box)[1],
+                                                           (*box)[2], (*box)[3]),
+                "batch_assemble_rrc: the box (y0, x0, bh, bw) must hold a pixel and lie inside the ",
+                r.Hs, " x ", r.Ws, " image, got ", *box);
+    for (int k = 0; k < 4; ++k) r.box[k] = (int)(*box)[k];
+    return r;
+  }
+  TORCH_CHECK(table->is_cuda() && table->scalar_type() == at::kShort && table->is_contiguous() &&
+                  table->dim() == 2 && table->size(1) == 2 && table->size(0) >= 1 &&
+                  table->size(0) <= dmp::guard::kRrcMaxTable && table->device() == data.device(),
+              "batch_assemble_rrc: table must be a contiguous int16 [1..",
+              dmp::guard::kRrcMaxTable, ", 2] tensor on ", data.device());
+  r.T = table->size(0);
+  if (check_table) {
+    // a device-to-host read: a loader asks for it on its first launch only (the
+    // kernel clamps what it reads, so an unchecked table cannot address outside)
+    const Tensor host = table->cpu();
+    const int16_t* t = host.data_ptr<int16_t>();
+    for (int64_t k = 0; k < r.T; ++k)
+      TORCH_CHECK(dmp::guard::rrc_box_ok(r.Hs, r.Ws, 0, 0, t[2 * k], t[2 * k + 1]),
+                  "batch_assemble_rrc: table entry ", k, " (", t[2 * k], " x ", t[2 * k + 1],
+                  ") does not lie within the ", r.Hs, " x ", r.Ws, " image");
+  }
+  return r;
+}
+
+void launch_rrc(const RrcCall& r, const Tensor& data, const Tensor& labels, const Tensor& lut,
+                const Tensor& index, int64_t count, const optional<Tensor>& table,
+                const Tensor& out_x, const Tensor& out_y, const optional<Tensor>& draws, bool flip,
+                uint64_t seed, int64_t epoch, const dmp::RrcMixParams* mix, int64_t path) {
+  dmp::launch_batch_assemble_rrc(data.data_ptr<uint8_t>(), i64(labels), bf16(lut),
+                                 index.data_ptr<int>(), (int)count, (int)r.N, (int)r.Hs, (int)r.Ws,
+                                 (int)r.C, r.fixed ? nullptr : ptr_or_null<short>(table), (int)r.T,
+                                 r.fixed ? r.box : nullptr, (int)r.Ho, (int)r.Wo, bf16(out_x),
+                                 i64(out_y), ptr_or_null<short>(draws), flip,
+                                 (unsigned long long)seed, (uint32_t)epoch, mix, (int)path,
+                                 cur_stream());
+}
+
+void batch_assemble_rrc(Tensor data, Tensor labels, Tensor lut, Tensor index, int64_t count,
+                        optional<Tensor> table, optional<std::vector<int64_t>> box, Tensor out_x,
+                        Tensor out_y, optional<Tensor> draws, bool flip, uint64_t seed,
+                        int64_t epoch, int64_t path, bool check_table) {
+  const RrcCall r = check_assemble_rrc(data, labels, lut, index, count, table, box, out_x, out_y,
+                                       draws, epoch, path, check_table);
+  launch_rrc(r, data, labels, lut, index, count, table, out_x, out_y, draws, flip, seed, epoch,
+             nullptr, path);
+}
+
+void batch_assemble_rrc_mix(Tensor data, Tensor labels, Tensor lut, Tensor index, int64_t count,
+                            optional<Tensor> table, optional<std::vector<int64_t>> box,
+                            Tensor out_x, Tensor out_y, Tensor out_y2, Tensor out_lam,
+                            optional<Tensor> draws, bool flip, uint64_t seed, int64_t epoch,
+                            double pix_lam, double label_lam, int64_t y0, int64_t y1, int64_t x0,
+                            int64_t x1, int64_t path, bool check_table) {
+  const RrcCall r = check_assemble_rrc(data, labels, lut, index, count, table, box, out_x, out_y,
+                                       draws, epoch, path, check_table);
+  TORCH_CHECK(out_y2.is_cuda() && out_y2.scalar_type() == at::kLong && out_y2.is_contiguous() &&
+                  out_y2.numel() >= count && out_y2.device() == data.device(),
+              "batch_assemble_rrc_mix: out_y2 must be a contiguous int64 tensor of >= ", count,
+              " elements on ", data.device());
+  TORCH_CHECK(out_lam.is_cuda() && out_lam.scalar_type() == at::kFloat &&
+                  out_lam.is_contiguous() && out_lam.numel() >= count &&
+                  out_lam.device() == data.device(),
+              "batch_assemble_rrc_mix: out_lam must be a contiguous float32 tensor of >= ", count,
+              " elements on ", data.device());
+  TORCH_CHECK(dmp::guard::mix_ok(r.Ho, r.Wo, y0, y1, x0, x1, pix_lam, label_lam),
+              "batch_assemble_rrc_mix: the box must satisfy 0 <= y0 <= y1 <= ", r.Ho,
+              " and 0 <= x0 <= x1 <= ", r.Wo, " and pix_lam, label_lam must lie in [0, 1]; got box (",
+              y0, ", ", y1, ", ", x0, ", ", x1, "), pix_lam ", pix_lam, ", label_lam ", label_lam);
+  const dmp::RrcMixParams mix{i64(out_y2), out_lam.data_ptr<float>(), (float)pix_lam,
+                              (float)label_lam, (int)y0, (int)y1, (int)x0, (int)x1};
+  launch_rrc(r, data, labels, lut, index, count, table, out_x, out_y, draws, flip, seed, epoch,
+             &mix, path);
+}
+
+// (staged, strip rows R, staged rows per view, LDS bytes) of guard::rrc_plan
+std::tuple<bool, int64_t, int64_t, int64_t> batch_assemble_rrc_plan(int64_t Hs, int64_t Ws,
+                                                                    int64_t C, int64_t Ho,
+                                                                    int64_t Wo, bool mix) {
+  TORCH_CHECK(dmp::guard::rrc_ok(1, Hs, Ws, C, Ho, Wo), "batch_assemble_rrc_plan: extents must "
+              "lie in 1..", dmp::guard::kRrcMaxExtent, " and channels in 1..",
+              dmp::guard::kDatasetMaxChannels);
+  const dmp::guard::RrcPlan p = dmp::guard::rrc_plan(Hs, Ws, C, Ho, Wo, mix);
+  return {p.staged, p.strip, p.stage_rows, p.lds_bytes};
+}
+
 }  // namespace
 
 void bind_data(pybind11::module_& m) {
@@ -130,6 +278,23 @@ void bind_data(pybind11::module_& m) {
         py::arg("x0"), py::arg("x1"), py::arg("path") = -1);
   m.def("batch_assemble_is_staged", &batch_assemble_is_staged,
         "whether batch_assemble stages this dataset's images through LDS");
+  m.def("batch_assemble_rrc", &batch_assemble_rrc,
+        "random-resized-crop form of batch_assemble: a box of every stored image, drawn from "
+        "`table` or given as `box`, resampled (integer bilinear) to out_x's height and width",
+        py::arg("data_u8"), py::arg("labels"), py::arg("lut"), py::arg("index_i32"),
+        py::arg("count"), py::arg("table"), py::arg("box"), py::arg("out_x"), py::arg("out_y"),
+        py::arg("draws"), py::arg("flip"), py::arg("seed"), py::arg("epoch"),
+        py::arg("path") = -1, py::arg("check_table") = true);
+  m.def("batch_assemble_rrc_mix", &batch_assemble_rrc_mix,
+        "batch_assemble_rrc with Mixup / CutMix of row b and row count - 1 - b",
+        py::arg("data_u8"), py::arg("labels"), py::arg("lut"), py::arg("index_i32"),
+        py::arg("count"), py::arg("table"), py::arg("box"), py::arg("out_x"), py::arg("out_y"),
+        py::arg("out_y2"), py::arg("out_lam"), py::arg("draws"), py::arg("flip"), py::arg("seed"),
+        py::arg("epoch"), py::arg("pix_lam"), py::arg("label_lam"), py::arg("y0"), py::arg("y1"),
+        py::arg("x0"), py::arg("x1"), py::arg("path") = -1, py::arg("check_table") = true);
+  m.def("batch_assemble_rrc_plan", &batch_assemble_rrc_plan,
+        "(staged, strip rows, staged rows per view, LDS bytes) batch_assemble_rrc launches with",
+        py::arg("Hs"), py::arg("Ws"), py::arg("C"), py::arg("Ho"), py::arg("Wo"), py::arg("mix"));
 }
 
 }  // namespace dmp::bind

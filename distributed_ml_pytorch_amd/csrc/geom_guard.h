@@ -97,5 +97,78 @@ inline bool mix_ok(int64_t h, int64_t w, int64_t y0, int64_t y1, int64_t x0, int
   return pix_lam >= 0.0 && pix_lam <= 1.0 && label_lam >= 0.0 && label_lam <= 1.0;
 }
 
+// random-resized-crop form of the assembler (data_rrc.hip): a box of the stored
+// hs x ws image resampled to ho x wo.  Extents up to 4096 keep every product of
+// the integer bilinear weights in 32 bits ((2 o + 1) b <= 2^25, i0 * c <= 2^14).
+constexpr int64_t kRrcMaxExtent = 4096;
+constexpr int64_t kRrcMaxTable = 4096;         // the 64 x 64 grid of box cells
+inline bool rrc_ok(int64_t count, int64_t hs, int64_t ws, int64_t c, int64_t ho, int64_t wo) {
+  for (int64_t v : {hs, ws, ho, wo})
+    if (v < 1 || v > kRrcMaxExtent) return false;
+  return c >= 1 && c <= kDatasetMaxChannels && fits_int(count) && bf16_bytes_ok(count, ho, wo, c);
+}
+
+// a box (y0, x0, bh, bw) of at least one pixel inside the hs x ws image
+inline bool rrc_box_ok(int64_t hs, int64_t ws, int64_t y0, int64_t x0, int64_t bh, int64_t bw) {
+  return bh >= 1 && bw >= 1 && y0 >= 0 && x0 >= 0 && bh <= hs && bw <= ws && y0 <= hs - bh &&
+         x0 <= ws - bw;
+}
+
+// Source rows staged for `r` consecutive output rows of a bh -> ho resample.
+// Output row o reads rows i0(o) = floor(s(o)) and i0(o) + 1 with s(o + 1) - s(o)
+// = bh / ho, so the rows from the strip's first tap to its last number
+// floor(s + d) - floor(s) + 2 <= ceil(d) + 2, d = (r - 1) bh / ho: what the
+// kernel copies.  The plan counts the strip's whole footprint, floor(r bh / ho) +
+// 2 rows, where that is more (it is from bh >= ho on): a reduction whose taps
+// skip rows would stage bytes nobody reads, and is better off in the direct
+// form.  Never more rows than the box holds.
+inline int64_t rrc_strip_rows(int64_t r, int64_t bh, int64_t ho) {
+  const int64_t taps = ((r - 1) * bh + ho - 1) / ho + 2, footprint = r * bh / ho + 2;
+  const int64_t rows = taps > footprint ? taps : footprint;
+  return rows < bh ? rows : bh;
+}
+
+// LDS of one workgroup of data_rrc.hip: the [4][256] bf16 look-up table, then per
+// view the column table (wo x u32), three row tables of kRrcMaxStrip u32 and the
+// staged source rows.  A staged row keeps its global 16-byte phase, so its pitch
+// is the widest box row plus 15 bytes, rounded up to 16.
+constexpr int kRrcMaxStrip = 8;
+constexpr int64_t kRrcStageBudget = 48 * 1024;  // staged source bytes, both views together
+constexpr int64_t kRrcLdsLimit = 64 * 1024;     // what a launch gets without an attribute
+struct RrcPlan {
+  bool staged;        // false: the four taps are gathered through L2
+  int strip;          // R: output rows per workgroup
+  int stage_rows;     // staged rows per view (0 in the direct form)
+  int pitch;          // bytes between staged rows
+  int table_bytes;    // look-up table + column and row tables, a multiple of 16
+  int lds_bytes;      // dynamic LDS of the launch
+};
+
+// The largest strip of 8 / 4 / 2 / 1 output rows whose worst case (a box of the
+// whole image) fits the staging budget, halved per view when two are staged
+// (mix); the direct form, at the full strip, where not even one row does or
+// where `direct` asks for it.
+inline RrcPlan rrc_plan(int64_t hs, int64_t ws, int64_t c, int64_t ho, int64_t wo, bool mix,
+                        bool direct = false) {
+  const int64_t views = mix ? 2 : 1;
+  RrcPlan p{};
+  p.pitch = (int)((ws * c + 15 + 15) / 16 * 16);
+  p.table_bytes = (int)((4 * 256 * 2 + views * (wo * 4 + 3 * kRrcMaxStrip * 4) + 15) / 16 * 16);
+  p.strip = kRrcMaxStrip;
+  int64_t budget = kRrcLdsLimit - p.table_bytes;
+  if (budget > kRrcStageBudget) budget = kRrcStageBudget;
+  for (int r = kRrcMaxStrip; r >= 1 && !direct; r /= 2) {
+    const int64_t rows = rrc_strip_rows(r, hs, ho);
+    if (rows * p.pitch * views <= budget) {
+      p.staged = true;
+      p.strip = r;
+      p.stage_rows = (int)rows;
+      break;
+    }
+  }
+  p.lds_bytes = p.table_bytes + (int)(views * p.stage_rows * p.pitch);
+  return p;
+}
+
 }  // namespace guard
 }  // namespace dmp

@@ -387,6 +387,65 @@ void check_dataset_guard() {
          "mix weights outside [0, 1], NaN or infinite");
 }
 
+// random-resized-crop plans (data_rrc.hip): the rows a strip's taps span never
+// exceed what the plan stages for the worst box, every plan fits its LDS, and
+// the shapes the planner is known by come out as stated
+void check_rrc_plans() {
+  using namespace dmp::guard;
+  auto axis = [](int64_t o, int64_t b, int64_t O, int64_t* i0, int64_t* i1) {
+    const int64_t n = (2 * o + 1) * b - O, num = n > 0 ? n : 0;
+    *i0 = num / (2 * O);
+    *i1 = *i0 + 1 < b - 1 ? *i0 + 1 : b - 1;
+  };
+  for (int64_t ho = 1; ho <= 40; ++ho)
+    for (int64_t bh = 1; bh <= 96; ++bh)
+      for (int64_t r = 1; r <= kRrcMaxStrip; r *= 2)
+        for (int64_t r0 = 0; r0 < ho; r0 += r) {
+          const int64_t r1 = r0 + r < ho ? r0 + r : ho;
+          int64_t lo, hi, unused;
+          axis(r0, bh, ho, &lo, &unused);
+          axis(r1 - 1, bh, ho, &unused, &hi);
+          EXPECT(hi >= lo && hi < bh && hi - lo + 1 <= rrc_strip_rows(r, bh, ho) &&
+                     rrc_strip_rows(r, bh, ho) <= rrc_strip_rows(r, bh + 1, ho),
+                 "rrc rows %lld..%lld of a %lld -> %lld strip at %lld (R %lld): plan %lld",
+                 (long long)lo, (long long)hi, (long long)bh, (long long)ho, (long long)r0,
+                 (long long)r, (long long)rrc_strip_rows(r, bh, ho));
+        }
+  for (int64_t hs : {1, 12, 32, 224, 256, 1024, 4096})
+    for (int64_t ho : {1, 8, 17, 224, 4096})
+      for (int64_t c : {1, 3, 4})
+        for (int mix = 0; mix < 2; ++mix) {
+          const RrcPlan p = rrc_plan(hs, hs, c, ho, ho, mix != 0);
+          const int64_t views = mix ? 2 : 1;
+          EXPECT(p.lds_bytes <= kRrcLdsLimit && p.table_bytes % 16 == 0 && p.pitch % 16 == 0 &&
+                     p.pitch >= hs * c + 15 && p.strip >= 1 && p.strip <= kRrcMaxStrip &&
+                     p.lds_bytes == p.table_bytes + views * p.stage_rows * p.pitch,
+                 "rrc plan %lld -> %lld c %lld mix %d: lds %d", (long long)hs, (long long)ho,
+                 (long long)c, mix, p.lds_bytes);
+          EXPECT(p.staged ? p.stage_rows == rrc_strip_rows(p.strip, hs, ho) &&
+                                views * p.stage_rows * p.pitch <= kRrcStageBudget
+                          : p.stage_rows == 0 && p.strip == kRrcMaxStrip,
+                 "rrc plan %lld -> %lld c %lld mix %d: staged %d rows %d", (long long)hs,
+                 (long long)ho, (long long)c, mix, (int)p.staged, p.stage_rows);
+          EXPECT(!rrc_plan(hs, hs, c, ho, ho, mix != 0, true).staged, "rrc direct on request");
+        }
+  EXPECT(rrc_plan(256, 256, 3, 224, 224, false).staged &&
+             rrc_plan(256, 256, 3, 224, 224, false).strip == 8 &&
+             rrc_plan(224, 224, 3, 224, 224, true).strip == 8 &&
+             !rrc_plan(1024, 1024, 3, 8, 8, false).staged,
+         "rrc: ImageNet-shaped crops stage 8-row strips, a 1024 -> 8 reduction gathers directly");
+  EXPECT(rrc_ok(128, 256, 256, 3, 224, 224) && rrc_ok(0, 1, 1, 1, 4096, 4096) &&
+             !rrc_ok(1, 4097, 8, 3, 8, 8) && !rrc_ok(1, 8, 8, 3, 8, 4097) &&
+             !rrc_ok(1, 8, 0, 3, 8, 8) && !rrc_ok(1, 8, 8, 5, 8, 8) && !rrc_ok(-1, 8, 8, 3, 8, 8) &&
+             !rrc_ok(int64_t(1) << 20, 8, 8, 3, 224, 224),
+         "rrc extents and batch bytes");
+  EXPECT(rrc_box_ok(8, 9, 0, 0, 8, 9) && rrc_box_ok(8, 9, 7, 8, 1, 1) && !rrc_box_ok(8, 9, 1, 0, 8, 9) &&
+             !rrc_box_ok(8, 9, 0, 0, 0, 1) && !rrc_box_ok(8, 9, -1, 0, 2, 2) &&
+             !rrc_box_ok(8, 9, 0, 0, 9, 9) && !rrc_box_ok(8, 9, INT64_MAX, 0, 2, 2) &&
+             !rrc_box_ok(8, 9, 0, 0, INT64_MAX, 1),
+         "rrc boxes inside and outside the image");
+}
+
 // attention plans (attn_plan.h) over every token count either route takes, the
 // edges that must be refused, and batch * heads products up to the grid limit
 void check_attention_plans() {
@@ -536,6 +595,7 @@ int main(int argc, char** argv) {
   check_guards();
   check_mx8_layout();
   check_dataset_guard();
+  check_rrc_plans();
   check_attention_plans();
   std::printf("host_check: %lld checks over %zu conv shapes, %d failed\n", g_checks, convs.size(),
               g_fail);

@@ -130,6 +130,28 @@ void launch_batch_assemble_mix(const uint8_t* data, const long long* labels, con
                                float label_lam, int y0, int y1, int x0, int x1, int path,
                                hipStream_t s);
 
+// data_rrc.hip: the random-resized-crop form of the assembler.  Every sample is
+// a box of its stored Hs x Ws image resampled (integer bilinear) to Ho x Wo.
+// table [T][2] int16 holds the box sizes (bh, bw) the per-sample Philox draw
+// picks from; box (null, or host memory (y0, x0, bh, bw)) replaces the draw for
+// every sample.  draws (null or [count][5] int16) receives (y0, x0, bh, bw, f).
+// mix (null: plain): the mixing rule of launch_batch_assemble_mix on the two
+// resampled views, the box in output coordinates.  path: -1 the staged form
+// where guard::rrc_plan says it fits, 0 always the direct gather.
+// guard::rrc_ok, rrc_box_ok and mix_ok are the caller's checks.
+struct RrcMixParams {
+  long long* out_y2;
+  float* out_lam;
+  float pix_lam, label_lam;
+  int y0, y1, x0, x1;
+};
+void launch_batch_assemble_rrc(const uint8_t* data, const long long* labels, const uint16_t* lut,
+                               const int* index, int count, int N, int Hs, int Ws, int C,
+                               const short* table, int T, const int* box, int Ho, int Wo,
+                               uint16_t* out_x, long long* out_y, short* draws, bool flip,
+                               unsigned long long seed, uint32_t epoch, const RrcMixParams* mix,
+                               int path, hipStream_t s);
+
 // bn.hip
 int bn_num_partials(long long M, int C);
 // inference-time BN folding into the producing conv (bn.hip): w16 = bf16(w * s),

@@ -43,7 +43,8 @@ from ..parallel.server import ParameterServer, make_ps_groups
 from ..parallel.staleness import check_policy
 from ..utils import checkpoint as ckpt
 from ..utils.data import get_datasets, make_loaders
-from ..utils.device_data import (AUGMENTS, MAX_PAD, DeviceLoader, MixConfig, check_mix_config,
+from ..utils.device_data import (AUGMENTS, MAX_PAD, RRC_AUGMENTS, DeviceLoader, MixConfig,
+                                 RrcConfig, check_mix_config, check_rrc_config, eval_box,
                                  get_device_datasets)
 from ..utils.metrics import IterationLog, StepTimer, Throughput, classification_report
 from .determinism import enable_determinism
@@ -113,8 +114,12 @@ class TrainConfig:
     deterministic: bool = False       # bitwise-reproducible debug mode (runtime/determinism.py)
     device_data: bool = False         # dataset resident on the device as uint8, batches assembled
                                       # by one native kernel per step (utils/device_data.py)
-    augment: str = "none"             # none | crop | flip | crop_flip (device_data only)
+    augment: str = "none"             # none | crop | flip | crop_flip | rrc | rrc_flip
+                                      # (device_data only)
     crop_pad: int = 4                 # zero padding of the random crop
+    rrc_scale: tuple = (0.08, 1.0)    # rrc: area range of the box, as a fraction of the image
+    rrc_ratio: tuple = (3.0 / 4.0, 4.0 / 3.0)   # rrc: aspect-ratio range of the box
+    stored_size: int = 0              # synthetic dataset: images kept S x S (0: the input size)
     mixup: float = 0.0                # Mixup alpha, 0 = off (device_data only)
     cutmix: float = 0.0               # CutMix alpha, 0 = off (device_data only)
     mix_prob: float = 1.0             # probability that a batch is mixed at all
@@ -552,8 +557,9 @@ def check_stale_config(cfg: TrainConfig, info: DistInfo):
 def check_device_data_config(cfg: TrainConfig, info: DistInfo):
     """Augmentation exists in the device-resident data path only, and that path
     writes bf16 batches on a GPU: anything else is an error at start-up."""
-    if cfg.augment not in AUGMENTS:
-        raise ValueError(f"unknown --augment {cfg.augment!r}; one of {sorted(AUGMENTS)}")
+    if cfg.augment not in AUGMENTS and cfg.augment not in RRC_AUGMENTS:
+        raise ValueError(f"unknown --augment {cfg.augment!r}; one of "
+                         f"{sorted([*AUGMENTS, *RRC_AUGMENTS])}")
     if cfg.augment != "none" and not cfg.device_data:
         raise ValueError(f"--augment {cfg.augment} needs --device-data: the host loader applies "
                          "no augmentation (random crop and flip run in the batch assembler)")
@@ -561,10 +567,27 @@ def check_device_data_config(cfg: TrainConfig, info: DistInfo):
     if (cfg.mixup > 0 or cfg.cutmix > 0) and not cfg.device_data:
         raise ValueError("--mixup / --cutmix need --device-data: the host loader mixes nothing "
                          "(both samples are blended in the batch assembler)")
+    if cfg.stored_size and cfg.dataset.lower() != "synthetic":
+        raise ValueError(f"--stored-size is for --dataset synthetic: {cfg.dataset} images have "
+                         "the size of their files")
+    if cfg.stored_size and not cfg.device_data:
+        raise ValueError("--stored-size needs --device-data: only the batch assembler resamples "
+                         "a stored image to the model's input size")
     if not cfg.device_data:
         return
     if not 0 <= cfg.crop_pad <= MAX_PAD:
         raise ValueError(f"--crop-pad must be in 0..{MAX_PAD}, got {cfg.crop_pad}")
+    if cfg.augment in RRC_AUGMENTS:
+        if cfg.crop_pad != TrainConfig.crop_pad:
+            raise ValueError(f"--crop-pad belongs to --augment crop; --augment {cfg.augment} "
+                             "pads nothing")
+        try:
+            check_rrc_config(cfg.rrc_scale, cfg.rrc_ratio)
+        except ValueError as e:
+            raise ValueError(f"--rrc-scale / --rrc-ratio: {e}") from None
+    elif cfg.stored_size:
+        raise ValueError(f"--stored-size {cfg.stored_size} needs --augment rrc or rrc_flip: "
+                         f"--augment {cfg.augment} cannot change the resolution")
     on_gpu = cfg.cuda and info.device.type == "cuda"
     if on_gpu and (cfg.deterministic or _dtype(cfg.dtype) != torch.bfloat16):
         raise ValueError("--device-data on the GPU assembles bf16 batches: it cannot feed "
@@ -598,17 +621,29 @@ def make_device_loaders(cfg: TrainConfig, info: DistInfo, w: "Worker"):
     (sync DP by rank, every other mode the whole set in the rank's own order); the
     test loader serves the test set in order, unaugmented and unmixed."""
     tr, te, source = get_device_datasets(cfg.dataset, cfg.data_dir, w.input_shape, w.num_classes,
-                                         cfg.n_train, cfg.n_test, cfg.seed, w.device)
-    crop, flip = AUGMENTS[cfg.augment]
+                                         cfg.n_train, cfg.n_test, cfg.seed, w.device,
+                                         stored_size=cfg.stored_size)
     shard = cfg.mode == "sync" and info.is_distributed
     mix = MixConfig(cfg.mixup, cfg.cutmix, cfg.mix_prob, cfg.mix_switch_prob) \
         if cfg.mixup > 0 or cfg.cutmix > 0 else None
+    out_hw = tuple(int(v) for v in w.input_shape[1:])
+    if cfg.augment in RRC_AUGMENTS:
+        # random resized crops of the stored images, brought to the model's input size
+        geometry = dict(flip=RRC_AUGMENTS[cfg.augment], out_hw=out_hw,
+                        rrc=RrcConfig(tuple(cfg.rrc_scale), tuple(cfg.rrc_ratio)))
+    else:
+        crop, flip = AUGMENTS[cfg.augment]
+        geometry = dict(pad=cfg.crop_pad if crop else 0, flip=flip)
     train = DeviceLoader(tr, cfg.batch_size, shuffle=True, drop_last=True,
-                         pad=cfg.crop_pad if crop else 0, flip=flip, seed=cfg.seed + info.rank,
-                         rank=info.rank if shard else 0, world=info.world_size if shard else 1,
-                         out_dtype=w.compute_dtype, mix=mix)
+                         seed=cfg.seed + info.rank, rank=info.rank if shard else 0,
+                         world=info.world_size if shard else 1, out_dtype=w.compute_dtype,
+                         mix=mix, **geometry)
+    # evaluation: the stored image itself, or where its size is not the input's the
+    # central window / the whole image resampled (utils/device_data.py, eval_box)
+    view = {} if (te.height, te.width) == out_hw else \
+        dict(out_hw=out_hw, box=eval_box((te.height, te.width), out_hw))
     test = DeviceLoader(te, cfg.test_batch_size, shuffle=False, drop_last=False,
-                        out_dtype=w.compute_dtype)
+                        out_dtype=w.compute_dtype, **view)
     return train, test, source + "+device"
 
 

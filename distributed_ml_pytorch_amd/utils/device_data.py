@@ -58,6 +58,38 @@ kernel and ``(a.float() * lam + p.float() * (1 - lam)).to(bfloat16)`` agree bit
 for bit.  The step receives ``y`` (row b's label), ``y2`` (the partner's) and
 ``lam = label_lam`` per row for the two-target loss
 (``ops.functional.softmax_cross_entropy_mix``).
+
+**Random resized crop** (``csrc/data_rrc.hip``) is a second view function: a box
+of the stored ``Hs x Ws`` image resampled to an ``Ho x Wo`` output, torchvision's
+``RandomResizedCrop(scale, ratio)`` in integers.  The box sizes come from a table
+built once on the host in fp64 (:func:`rrc_box_table`) -- torchvision's rejection
+sampling, stratified: for ``u, v`` in a 64 x 64 grid::
+
+    area = Hs Ws (s0 + (s1 - s0)(u + .5) / 64)
+    r    = exp(log r0 + (log r1 - log r0)(v + .5) / 64)
+    bw   = round(sqrt(area r)),  bh = round(sqrt(area / r))
+
+kept when ``1 <= bh <= Hs`` and ``1 <= bw <= Ws`` -- and each sample draws from it::
+
+    r = philox4x32_10(ctr=(i, epoch, 1, 0x64617461), key=seed)      # word 2 is 1
+    t = (r.x * T) >> 32,  (bh, bw) = table[t]
+    y0 = (r.y * (Hs - bh + 1)) >> 32,  x0 = (r.z * (Ws - bw + 1)) >> 32
+    f = r.w >> 31 if flip else 0
+
+A fixed box ``(y0, x0, bh, bw)`` may stand in for the draw (evaluation).  The
+resample is bilinear with ``align_corners=False`` and no antialiasing, in
+integers.  For output column ``o`` of ``O = Wo`` over a box of width ``b`` (``o``
+mirrored to ``O - 1 - o`` first when ``f`` is set; rows alike, never mirrored)::
+
+    num = max((2 o + 1) b - O, 0)
+    i0 = num // (2 O),  fx = ((num % (2 O)) * 256 + O) // (2 O),  i1 = min(i0 + 1, b - 1)
+    v = (256 - fy)((256 - fx) p00 + fx p01) + fy((256 - fx) p10 + fx p11)       # < 2^24
+    byte = (v + 32768) >> 16
+
+and the stored value is ``lut[c][byte]``.  A box of the output's own size is the
+plain crop byte for byte; the result is within 1.5 levels of the fp64
+interpolation (0.5 from the last rounding, 2 * 255 * 0.5 / 256 from the two 8-bit
+weights).  Mixing takes these views in place of the crop's, unchanged otherwise.
 """
 from __future__ import annotations
 
@@ -79,6 +111,10 @@ MNIST_MEAN, MNIST_STD = (0.1307,), (0.3081,)
 SYNTH_MEAN, SYNTH_STD = 128.0 / 255.0, 32.0 / 255.0
 AUGMENTS = {"none": (False, False), "crop": (True, False), "flip": (False, True),
             "crop_flip": (True, True)}
+RRC_AUGMENTS = {"rrc": False, "rrc_flip": True}     # random resized crop: its flip
+RRC_GRID = 64               # the box table's cells per axis
+RRC_STREAM = 1              # counter word 2 of the draw (the crop form's is 0)
+RRC_MAX_EXTENT = 4096       # stored and output extents (csrc/geom_guard.h, rrc_ok)
 
 MIX_DOMAIN = 0x6D697875     # "mixu": the mix generator's seed, apart from epoch_order's
 
@@ -187,10 +223,17 @@ def quantize_synthetic(x: torch.Tensor) -> torch.Tensor:
 
 
 def get_device_datasets(name: str, data_dir: str, input_shape, num_classes: int, n_train: int,
-                        n_test: int, seed: int, device):
+                        n_test: int, seed: int, device, stored_size: int = 0):
     """The device-resident form of :func:`..utils.data.get_datasets`: returns
-    ``(train, test, source)`` with the same sources and the same normalisation."""
+    ``(train, test, source)`` with the same sources and the same normalisation.
+    ``stored_size``: the synthetic images are generated and kept ``S x S`` (0: the
+    input's own size); a random resized crop brings them to the input size."""
     name = name.lower()
+    if stored_size and name != "synthetic":
+        raise ValueError(f"a stored size is a property of the synthetic dataset; {name} images "
+                         "have the size of their files")
+    if stored_size and not 1 <= stored_size <= RRC_MAX_EXTENT:
+        raise ValueError(f"the stored size must be in 1..{RRC_MAX_EXTENT}, got {stored_size}")
     readers = {"cifar10": (read_cifar10_binary, CIFAR_MEAN, CIFAR_STD),
                "mnist": (read_mnist_idx, MNIST_MEAN, MNIST_STD)}
     if name in readers:
@@ -209,11 +252,12 @@ def get_device_datasets(name: str, data_dir: str, input_shape, num_classes: int,
         raise ValueError(f"--device-data needs image inputs [C<={MAX_CHANNELS}, H, W], "
                          f"got {tuple(input_shape)}")
     out = []
+    shape = (c, stored_size, stored_size) if stored_size else tuple(input_shape)
     for n, s in ((n_train, seed), (n_test, seed + 1)):
-        if n * int(input_shape[0]) * int(input_shape[1]) * int(input_shape[2]) >= (1 << 31):
-            raise ValueError(f"{n} synthetic images of {tuple(input_shape)} exceed the 2 GiB of a "
+        if n * int(shape[0]) * int(shape[1]) * int(shape[2]) >= (1 << 31):
+            raise ValueError(f"{n} synthetic images of {tuple(shape)} exceed the 2 GiB of a "
                              "device-resident dataset; lower --n-train / --n-test")
-        src = SyntheticImages(n, input_shape, num_classes, seed=s)
+        src = SyntheticImages(n, shape, num_classes, seed=s)
         out.append(DeviceDataset(quantize_synthetic(src.x), src.y, (SYNTH_MEAN,) * c,
                                  (SYNTH_STD,) * c, device))
     return out[0], out[1], "synthetic"
@@ -359,6 +403,12 @@ def assemble_mix_reference(ds: DeviceDataset, index: torch.Tensor, params: MixPa
     partner's label), ``lam`` float32 [B] (``label_lam``) and row b's ``draws``."""
     _check_mix_params(params, ds.height, ds.width)
     a, y, draws = assemble_reference(ds, index, pad, flip, seed, epoch)
+    return (*_mix_views(a, y, params), draws)
+
+
+def _mix_views(a: torch.Tensor, y: torch.Tensor, params: MixParams):
+    """The mixing rule on the views ``a`` [B, C, H, W] and labels ``y`` of a batch:
+    ``(x, y, y2, lam)``."""
     p, y2 = a.flip(0), y.flip(0)                 # row count - 1 - b
     y0, y1, x0, x1 = params.box
     if params.pix_lam == 1:
@@ -366,11 +416,11 @@ def assemble_mix_reference(ds: DeviceDataset, index: torch.Tensor, params: MixPa
     else:
         lam = torch.tensor(params.pix_lam, dtype=torch.float32)
         x = (a.float() * lam + p.float() * (1 - lam)).to(torch.bfloat16)
-    box = torch.zeros((ds.height, ds.width), dtype=torch.bool)
+    box = torch.zeros(a.shape[2:], dtype=torch.bool)
     box[y0:y1, x0:x1] = True
     x = torch.where(box, p, x)
     lam_rows = torch.full((len(y),), params.label_lam, dtype=torch.float32)
-    return x, y, y2, lam_rows, draws
+    return x, y, y2, lam_rows
 
 
 def assemble_mix(ds: DeviceDataset, index: torch.Tensor, count: int, out_x: torch.Tensor,
@@ -398,6 +448,200 @@ def assemble_mix(ds: DeviceDataset, index: torch.Tensor, count: int, out_x: torc
         draws[:count].copy_(d)
 
 
+# ---------------------------------------------------------- random resized crop
+def check_rrc_config(scale, ratio):
+    for name, r in (("scale", scale), ("ratio", ratio)):
+        if len(r) != 2 or not all(math.isfinite(v) for v in r) or not 0 < r[0] <= r[1]:
+            raise ValueError(f"the random-resized-crop {name} range must be 0 < lo <= hi, "
+                             f"got {tuple(r)}")
+
+
+@dataclass(frozen=True)
+class RrcConfig:
+    """Random resized crop of the training batches (module docstring)."""
+    scale: tuple = (0.08, 1.0)
+    ratio: tuple = (3.0 / 4.0, 4.0 / 3.0)
+
+    def __post_init__(self):
+        check_rrc_config(self.scale, self.ratio)
+
+
+def rrc_box_table(Hs: int, Ws: int, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0)) -> torch.Tensor:
+    """int16 ``[T, 2]``: the box sizes ``(bh, bw)`` of the cells of the 64 x 64
+    (area, log-ratio) grid that fit the image (module docstring), in fp64; the
+    cell of area index ``u`` and ratio index ``v`` comes before that of a larger
+    ``(u, v)``.  ``ValueError`` when no cell fits."""
+    check_rrc_config(scale, ratio)
+    if not (1 <= Hs <= RRC_MAX_EXTENT and 1 <= Ws <= RRC_MAX_EXTENT):
+        raise ValueError(f"random resized crop takes images up to {RRC_MAX_EXTENT} pixels a side, "
+                         f"got {Hs} x {Ws}")
+    k = (torch.arange(RRC_GRID, dtype=torch.float64) + 0.5) / RRC_GRID
+    area = (Hs * Ws * (scale[0] + (scale[1] - scale[0]) * k)).view(-1, 1)
+    r = torch.exp(math.log(ratio[0]) + (math.log(ratio[1]) - math.log(ratio[0])) * k).view(1, -1)
+    bw, bh = torch.round(torch.sqrt(area * r)), torch.round(torch.sqrt(area / r))
+    keep = (bh >= 1) & (bh <= Hs) & (bw >= 1) & (bw <= Ws)
+    if not bool(keep.any()):
+        raise ValueError(f"no random-resized-crop box of scale {tuple(scale)} and ratio "
+                         f"{tuple(ratio)} fits a {Hs} x {Ws} image")
+    return torch.stack([bh[keep], bw[keep]], 1).to(torch.int16)
+
+
+def _check_rrc_box(box, Hs: int, Ws: int):
+    y0, x0, bh, bw = box            # the guard of csrc/geom_guard.h (rrc_box_ok)
+    if not (bh >= 1 and bw >= 1 and 0 <= y0 <= Hs - bh and 0 <= x0 <= Ws - bw):
+        raise ValueError(f"the box (y0, x0, bh, bw) = {tuple(box)} must hold a pixel and lie "
+                         f"inside the {Hs} x {Ws} image")
+
+
+def _rrc_source(table, box, Hs: int, Ws: int):
+    if (table is None) == (box is None):
+        raise ValueError("give either a box table or a fixed box, not both or neither")
+    if box is not None:
+        _check_rrc_box(box, Hs, Ws)
+        return None
+    t = table.to("cpu", torch.int64)
+    if t.dim() != 2 or t.shape[1] != 2 or not 1 <= t.shape[0] <= RRC_GRID * RRC_GRID or \
+            int(t.min()) < 1 or int(t[:, 0].max()) > Hs or int(t[:, 1].max()) > Ws:
+        raise ValueError(f"a box table is [1..{RRC_GRID * RRC_GRID}, 2] sizes within the "
+                         f"{Hs} x {Ws} image")
+    return t
+
+
+def rrc_draws(index: torch.Tensor, Hs: int, Ws: int, table=None, box=None, flip: bool = False,
+              seed: int = 0, epoch: int = 0) -> torch.Tensor:
+    """int64 ``[B, 5]``: ``(y0, x0, bh, bw, f)`` of the dataset indices ``index``."""
+    t = _rrc_source(table, box, Hs, Ws)
+    i = index.to("cpu", torch.int64).reshape(-1) & _M32
+    z = torch.zeros_like(i)
+    r = philox4x32_10((i, z + (epoch & _M32), z + RRC_STREAM, z + DOMAIN),
+                      (seed & _M32, (seed >> 32) & _M32))
+    if t is None:
+        y0, x0, bh, bw = (z + int(v) for v in box)
+    else:
+        bh, bw = t[(r[0] * len(t)) >> 32].unbind(1)
+        y0, x0 = (r[1] * (Hs - bh + 1)) >> 32, (r[2] * (Ws - bw + 1)) >> 32
+    f = (r[3] >> 31) if flip else z
+    return torch.stack([y0, x0, bh, bw, f], 1)
+
+
+def _rrc_axis(O: int, b: torch.Tensor, f=None):
+    """``(i0, i1, weight)`` int64 ``[B, O]`` of the outputs of one axis over boxes of
+    extent ``b`` [B]; ``f`` [B]: mirror the outputs of these samples first."""
+    o = torch.arange(O).view(1, O).expand(len(b), O)
+    if f is not None:
+        o = torch.where(f.view(-1, 1) != 0, O - 1 - o, o)
+    num = ((2 * o + 1) * b.view(-1, 1) - O).clamp(min=0)
+    i0 = num // (2 * O)
+    w = ((num % (2 * O)) * 256 + O) // (2 * O)
+    return i0, torch.minimum(i0 + 1, b.view(-1, 1) - 1), w
+
+
+def assemble_rrc_reference(ds: DeviceDataset, index: torch.Tensor, out_hw, table=None, box=None,
+                           flip: bool = False, seed: int = 0, epoch: int = 0):
+    """The definition of a random-resized-crop batch (module docstring), in torch
+    on the CPU.  ``table``: the box sizes to draw from; ``box``: one box for every
+    sample instead.
+
+    Returns ``x`` bf16 [B, C, Ho, Wo] with channels-last strides, ``y`` int64 [B]
+    and ``draws`` int16 [B, 5] holding ``(y0, x0, bh, bw, f)`` per sample."""
+    _check_args(0, seed, epoch)
+    ho, wo = (int(v) for v in out_hw)
+    if not (1 <= ho <= RRC_MAX_EXTENT and 1 <= wo <= RRC_MAX_EXTENT):
+        raise ValueError(f"the output must be 1..{RRC_MAX_EXTENT} pixels a side, got {ho} x {wo}")
+    index = index.to("cpu", torch.int64).reshape(-1)
+    if index.numel() and (int(index.min()) < -(1 << 31) or int(index.max()) >= (1 << 31)):
+        raise ValueError("dataset indices must fit int32")
+    n, c, hs, ws = ds.n, ds.channels, ds.height, ds.width
+    data, labels, lut = ds.data.cpu(), ds.labels.cpu(), ds.lut.cpu()
+    d = rrc_draws(index, hs, ws, table, box, flip, seed, epoch)
+    y0, x0, bh, bw, f = d.unbind(1)
+    valid = (index >= 0) & (index < n)
+    safe = torch.where(valid, index, torch.zeros_like(index)).view(-1, 1, 1)
+    ya, yb, fy = (t.unsqueeze(2) for t in _rrc_axis(ho, bh))               # [B, Ho, 1]
+    xa, xb, fx = (t.unsqueeze(1) for t in _rrc_axis(wo, bw, f))            # [B, 1, Wo]
+    ya, yb = ya + y0.view(-1, 1, 1), yb + y0.view(-1, 1, 1)
+    xa, xb = xa + x0.view(-1, 1, 1), xb + x0.view(-1, 1, 1)
+    fy, fx = fy.unsqueeze(3), fx.unsqueeze(3)
+    p00, p01 = data[safe, ya, xa].to(torch.int64), data[safe, ya, xb].to(torch.int64)
+    p10, p11 = data[safe, yb, xa].to(torch.int64), data[safe, yb, xb].to(torch.int64)
+    v = (256 - fy) * ((256 - fx) * p00 + fx * p01) + fy * ((256 - fx) * p10 + fx * p11)
+    byte = torch.where(valid.view(-1, 1, 1, 1), (v + 32768) >> 16, torch.zeros_like(v))
+    x = lut[torch.arange(c).view(1, 1, 1, c), byte].permute(0, 3, 1, 2)    # [B, Ho, Wo, C] storage
+    y = torch.where(valid, labels[safe.view(-1)], torch.full_like(index, IGNORE_LABEL))
+    return x, y, d.to(torch.int16)
+
+
+def assemble_rrc_mix_reference(ds: DeviceDataset, index: torch.Tensor, params: MixParams, out_hw,
+                               table=None, box=None, flip: bool = False, seed: int = 0,
+                               epoch: int = 0):
+    """:func:`assemble_mix_reference` on the views of :func:`assemble_rrc_reference`;
+    the CutMix box is in output coordinates.  Returns ``(x, y, y2, lam, draws)``."""
+    _check_mix_params(params, int(out_hw[0]), int(out_hw[1]))
+    a, y, draws = assemble_rrc_reference(ds, index, out_hw, table, box, flip, seed, epoch)
+    return (*_mix_views(a, y, params), draws)
+
+
+def assemble_rrc(ds: DeviceDataset, index: torch.Tensor, count: int, out_x: torch.Tensor,
+                 out_y: torch.Tensor, draws=None, table=None, box=None, flip: bool = False,
+                 seed: int = 0, epoch: int = 0, path: int = -1, check_table: bool = True):
+    """Write the random-resized-crop batch of ``index[:count]`` into rows ``[0,
+    count)`` of ``out_x`` (whose height and width are the output size) / ``out_y``
+    (and ``draws``): the native kernel on a GPU dataset -- a missing extension is an
+    error -- and :func:`assemble_rrc_reference` on a CPU one.  ``table`` lives on
+    the dataset's device; ``check_table=False`` spares the native path the read-back
+    of a table an earlier launch has checked."""
+    _check_args(0, seed, epoch)
+    if ds.device.type == "cuda":
+        from ..ops._ext import native
+
+        native().batch_assemble_rrc(ds.data, ds.labels, ds.lut, index, count, table,
+                                    None if box is None else list(box), out_x, out_y, draws,
+                                    flip, seed, epoch, path, check_table)
+        return
+    x, y, d = assemble_rrc_reference(ds, index[:count], out_x.shape[2:], table, box, flip, seed,
+                                     epoch)
+    out_x[:count].copy_(x)
+    out_y[:count].copy_(y)
+    if draws is not None:
+        draws[:count].copy_(d)
+
+
+def assemble_rrc_mix(ds: DeviceDataset, index: torch.Tensor, count: int, out_x: torch.Tensor,
+                     out_y: torch.Tensor, out_y2: torch.Tensor, out_lam: torch.Tensor, draws=None,
+                     params: MixParams = NO_MIX, table=None, box=None, flip: bool = False,
+                     seed: int = 0, epoch: int = 0, path: int = -1, check_table: bool = True):
+    """:func:`assemble_rrc` with the mix ``params``: also writes rows ``[0, count)``
+    of ``out_y2`` and ``out_lam``."""
+    _check_args(0, seed, epoch)
+    _check_mix_params(params, out_x.shape[2], out_x.shape[3])
+    if ds.device.type == "cuda":
+        from ..ops._ext import native
+
+        native().batch_assemble_rrc_mix(ds.data, ds.labels, ds.lut, index, count, table,
+                                        None if box is None else list(box), out_x, out_y, out_y2,
+                                        out_lam, draws, flip, seed, epoch, params.pix_lam,
+                                        params.label_lam, *params.box, path, check_table)
+        return
+    x, y, y2, lam, d = assemble_rrc_mix_reference(ds, index[:count], params, out_x.shape[2:],
+                                                  table, box, flip, seed, epoch)
+    out_x[:count].copy_(x)
+    out_y[:count].copy_(y)
+    out_y2[:count].copy_(y2)
+    out_lam[:count].copy_(lam)
+    if draws is not None:
+        draws[:count].copy_(d)
+
+
+def eval_box(stored_hw, out_hw):
+    """The evaluation view of a stored image larger or smaller than the model's
+    input: the central ``Ho x Wo`` window where the image holds one (an exact
+    copy: resize-256 / centre-crop-224), else the whole image, resampled."""
+    (hs, ws), (ho, wo) = stored_hw, out_hw
+    if hs >= ho and ws >= wo:
+        return ((hs - ho) // 2, (ws - wo) // 2, ho, wo)
+    return (0, 0, hs, ws)
+
+
 class DeviceLoader:
     """Batches of a :class:`DeviceDataset`, iterable once per epoch.
 
@@ -413,12 +657,18 @@ class DeviceLoader:
     with the draw of ``(seed, epoch, batch number)`` -- the unmixed batches too,
     with ``lam = 1``.  ``next`` still returns ``(x, y)``; the partner labels and
     the weights of that batch are ``last_mix = (y2, lam)``, written into the
-    third and fourth buffer of ``out`` when it has them."""
+    third and fourth buffer of ``out`` when it has them.
+
+    ``rrc``: a :class:`RrcConfig` makes every view a random resized crop of the
+    stored image, ``box`` one fixed box ``(y0, x0, bh, bw)`` (evaluation); either
+    way the batches are ``out_hw`` (default: the stored size) and ``pad`` is not
+    used."""
 
     def __init__(self, ds: DeviceDataset, batch: int, shuffle: bool = True,
                  drop_last: bool = True, pad: int = 0, flip: bool = False, seed: int = 0,
                  rank: int = 0, world: int = 1, out_dtype: torch.dtype = torch.bfloat16,
-                 mix: MixConfig | None = None):
+                 mix: MixConfig | None = None, rrc: RrcConfig | None = None, out_hw=None,
+                 box=None):
         if batch < 1:
             raise ValueError(f"batch must be >= 1, got {batch}")
         if not 0 <= rank < world:
@@ -429,6 +679,23 @@ class DeviceLoader:
         self.ds, self.batch, self.shuffle, self.drop_last = ds, batch, shuffle, drop_last
         self.pad, self.flip, self.seed, self.out_dtype = pad, flip, seed, out_dtype
         self.mix = mix
+        if rrc is not None and box is not None:
+            raise ValueError("a loader draws random resized crops or takes one fixed box, not both")
+        if (rrc is not None or box is not None) and pad:
+            raise ValueError("crop padding does not combine with a random resized crop")
+        if rrc is None and box is None and out_hw is not None and \
+                tuple(out_hw) != (ds.height, ds.width):
+            raise ValueError(f"without a resized crop the batches have the stored size "
+                             f"{ds.height} x {ds.width}, not {tuple(out_hw)}")
+        self.out_h, self.out_w = (int(v) for v in out_hw) if out_hw is not None else \
+            (ds.height, ds.width)
+        self.box = None if box is None else tuple(int(v) for v in box)
+        if self.box is not None:
+            _check_rrc_box(self.box, ds.height, ds.width)
+        # the box sizes, built once and kept on the dataset's device
+        self.table = None if rrc is None else \
+            rrc_box_table(ds.height, ds.width, rrc.scale, rrc.ratio).to(ds.device)
+        self._table_checked = False     # the native path reads the table back once
         self.last_mix = None        # (y2, lam) of the batch next() returned last
         self.last_params = None     # its MixParams
         self.shard = torch.arange(rank, ds.n, world, dtype=torch.int64)
@@ -481,10 +748,15 @@ class DeviceLoader:
         if out is not None:
             x, y = out
         else:
-            x = torch.empty((count, ds.channels, ds.height, ds.width), dtype=torch.bfloat16,
+            x = torch.empty((count, ds.channels, self.out_h, self.out_w), dtype=torch.bfloat16,
                             device=ds.device, memory_format=torch.channels_last)
             y = torch.empty(count, dtype=torch.int64, device=ds.device)
-        assemble(ds, index, count, x, y, None, self.pad, self.flip, self.seed, self._cur_epoch)
+        if self.table is not None or self.box is not None:
+            assemble_rrc(ds, index, count, x, y, None, self.table, self.box, self.flip, self.seed,
+                         self._cur_epoch, check_table=not self._table_checked)
+            self._table_checked = True
+        else:
+            assemble(ds, index, count, x, y, None, self.pad, self.flip, self.seed, self._cur_epoch)
         if x.shape[0] != count:
             x, y = x[:count], y[:count]
         if x.dtype != self.out_dtype:
@@ -497,7 +769,7 @@ class DeviceLoader:
         if len(out) >= 2:
             x, y = out[:2]
         else:
-            x = torch.empty((count, ds.channels, ds.height, ds.width), dtype=torch.bfloat16,
+            x = torch.empty((count, ds.channels, self.out_h, self.out_w), dtype=torch.bfloat16,
                             device=ds.device, memory_format=torch.channels_last)
             y = torch.empty(count, dtype=torch.int64, device=ds.device)
         if len(out) >= 4:
@@ -505,10 +777,16 @@ class DeviceLoader:
         else:
             y2 = torch.empty(x.shape[0], dtype=torch.int64, device=ds.device)
             lam = torch.empty(x.shape[0], dtype=torch.float32, device=ds.device)
-        params = mix_draw(self.seed, self._cur_epoch, batch_no, ds.height, ds.width,
+        params = mix_draw(self.seed, self._cur_epoch, batch_no, self.out_h, self.out_w,
                           m.mixup_alpha, m.cutmix_alpha, m.prob, m.switch_prob)
-        assemble_mix(ds, index, count, x, y, y2, lam, None, params, self.pad, self.flip, self.seed,
-                     self._cur_epoch)
+        if self.table is not None or self.box is not None:
+            assemble_rrc_mix(ds, index, count, x, y, y2, lam, None, params, self.table, self.box,
+                             self.flip, self.seed, self._cur_epoch,
+                             check_table=not self._table_checked)
+            self._table_checked = True
+        else:
+            assemble_mix(ds, index, count, x, y, y2, lam, None, params, self.pad, self.flip,
+                         self.seed, self._cur_epoch)
         if x.shape[0] != count:
             x, y, y2, lam = x[:count], y[:count], y2[:count], lam[:count]
         if x.dtype != self.out_dtype:
