@@ -25,6 +25,15 @@ CSRC = PKG_DIR / "csrc"
 BUILD = PKG_DIR.parent / "build" / "native"
 ARCH = os.environ.get("DMP_OFFLOAD_ARCH", "gfx950")
 EXT_NAME = "_native"
+# Kernel files built without the packed fp32 VALU forms (v_pk_fma_f32 and kin).
+# dwconv: with them the compiler pairs the accumulators and dwconv_kernel<5> / <7>
+# need 117 / 118 VGPRs, dwconv_wgrad_kernel<7> 136, against 84-95 without: the
+# flag buys a wave per SIMD (5 instead of 4) in kernels bound by LDS latency and
+# instruction issue.  layer_scale: memory-bound with every rounding pinned by
+# fp contract(off); the packed forms cannot shorten it, and it is built like
+# dwconv so that the two files of this family share one flag set.
+NO_PACKED_FP32 = {"dwconv", "layer_scale"}
+_NO_PACKED_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 
 def _ext_suffix() -> str:
@@ -99,7 +108,9 @@ def build(verbose: bool = False, jobs: int | None = None, force: bool = False) -
         obj = BUILD / (src.stem + ".o")
         objs.append(obj)
         if force or _needs(obj, [src, *headers]):
-            jobs_list.append([hipcc, *common, "-x", "hip", "-c", str(src), "-o", str(obj)])
+            extra = _NO_PACKED_FLAGS if src.stem in NO_PACKED_FP32 else []
+            jobs_list.append([hipcc, *common, *extra, "-x", "hip", "-c", str(src), "-o",
+                              str(obj)])
     inc, libdirs, defs = _torch_flags()
     py_inc = sysconfig.get_paths()["include"]
     # bindings: objects in their own directory (bind/optim.cpp vs optim.hip)

@@ -9,6 +9,7 @@ void bind_conv(pybind11::module_& m);
 void bind_gemm(pybind11::module_& m);
 void bind_transformer(pybind11::module_& m);
 void bind_data(pybind11::module_& m);
+void bind_dwconv(pybind11::module_& m);
 }  // namespace dmp::bind
 
 PYBIND11_MODULE(_native, m) {
@@ -19,5 +20,6 @@ PYBIND11_MODULE(_native, m) {
   dmp::bind::bind_gemm(m);
   dmp::bind::bind_transformer(m);
   dmp::bind::bind_data(m);
+  dmp::bind::bind_dwconv(m);
   m.attr("arch") = "gfx950";
 }

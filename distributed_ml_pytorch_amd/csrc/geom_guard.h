@@ -53,6 +53,17 @@ inline bool conv_offsets_ok(int64_t B, int64_t H, int64_t W, int64_t CI, int64_t
          bf16_bytes_ok(CO, CI, R, S);
 }
 
+// depthwise K x K / stride 1 / "same" conv (dwconv.hip): 32-bit element offsets
+// into the one [N, H, W, C] bf16 geometry that input, output and both gradients
+// share; the image index and the 32-channel chunk index are grid dimensions
+// (<= 65535 each)
+inline bool dwconv_ok(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K) {
+  for (int64_t v : {N, H, W, C})
+    if (v < 1 || !fits_int(v)) return false;
+  return (K == 3 || K == 5 || K == 7) && C % 8 == 0 && N <= 65535 && (C + 31) / 32 <= 65535 &&
+         bf16_bytes_ok(N, H, W, C);
+}
+
 // few-input-channel stem convs (conv_small.hip): 32-bit ELEMENT indexing of the
 // output, 2 GiB of input
 inline bool small_conv_ok(int64_t B, int64_t OH, int64_t OW, int64_t CO, int64_t x_numel) {

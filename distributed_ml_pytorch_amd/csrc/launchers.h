@@ -413,4 +413,27 @@ void launch_stem_fwd(const uint16_t* xs, const uint16_t* wp, uint16_t* y, float*
 void launch_stem_wgrad(const uint16_t* dy, const uint16_t* xs, float* dwp, int B, int H, int W,
                        hipStream_t s);
 
+// dwconv.hip: depthwise K x K (3 / 5 / 7), stride 1, pad K / 2 over [N, H, W, C]
+// bf16, w = bf16 [C][K*K] (tiles: dwconv_plan.h; geometry: guard::dwconv_ok).
+// y = conv(x) (+ fp32 bias) (+ bf16 addend); flip mirrors the taps (data gradient)
+void launch_dwconv(const uint16_t* x, const uint16_t* w, const float* bias, const uint16_t* addend,
+                   uint16_t* y, int N, int H, int W, int C, int K, bool flip, hipStream_t s);
+// dw [C][K*K] += weight gradient, db [C] += colsum(dy) (null: skipped), both by a
+// fixed-order reduce of the slab (dwconv_slab_floats(C, K) words, overwritten)
+void launch_dwconv_wgrad(const uint16_t* dy, const uint16_t* x, float* dw, float* db, float* slab,
+                         int N, int H, int W, int C, int K, hipStream_t s);
+
+// layer_scale.hip: h = x + gamma[c] * r (* rscale[row / tokens]) over [rows][C] bf16
+// rows, C % 8 == 0 and C <= layer_scale_max_channels(); rounding pinned (see the file)
+int layer_scale_max_channels();
+int layer_scale_num_slots();
+void launch_layer_scale_fwd(const uint16_t* x, const uint16_t* r, const float* gamma,
+                            const float* rscale, uint16_t* h, long long rows, int C, int tokens,
+                            hipStream_t s);
+// dr = dh * gamma (* rscale) (null: skipped); dgamma [C] += sum dh * r (* rscale)
+// through `slots` ([layer_scale_num_slots()][C] fp32, overwritten; null with dgamma)
+void launch_layer_scale_bwd(const uint16_t* dh, const uint16_t* r, const float* gamma,
+                            const float* rscale, uint16_t* dr, float* dgamma, float* slots,
+                            long long rows, int C, int tokens, hipStream_t s);
+
 }  // namespace dmp

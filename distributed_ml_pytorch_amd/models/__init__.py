@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 from .cnn import MLP, AlexNet, LeNet
+from .convnext import ConvNeXt, convnext_mini, convnext_tiny
 from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101
 from .vit import VisionTransformer, vit_b16, vit_mini_long, vit_tiny
 
@@ -19,11 +20,18 @@ REGISTRY = {
     "vit_b16_384": (lambda nc=1000, **kw: vit_b16(nc, image_size=384, **kw), (3, 384, 384), 1000),
     "vit_tiny": (lambda nc=10, **kw: vit_tiny(nc, **kw), (3, 32, 32), 10),
     "vit_mini_long": (lambda nc=10, **kw: vit_mini_long(nc, **kw), (3, 80, 80), 10),
+    "convnext_tiny": (lambda nc=1000, **kw: convnext_tiny(nc, **kw), (3, 224, 224), 1000),
+    "convnext_mini": (lambda nc=10, **kw: convnext_mini(nc, **kw), (3, 32, 32), 10),
 }
 
 
 def is_vit(name: str) -> bool:
     return _key(name).startswith("vit_")
+
+
+def has_drop_path(name: str) -> bool:
+    """Models whose residual adds carry stochastic depth: the ViTs and ConvNeXts."""
+    return _key(name).startswith(("vit_", "convnext_"))
 
 
 def _key(name: str) -> str:
@@ -33,7 +41,7 @@ def _key(name: str) -> str:
 
 def build_model(name: str, num_classes: int | None = None, drop_path: float = 0.0):
     """Return ``(model, input_shape, num_classes)`` for a registry name.
-    ``drop_path``: stochastic depth rate, for the ViTs only."""
+    ``drop_path``: stochastic depth rate, for the ViTs and ConvNeXts only."""
     key = _key(name)
     if key not in REGISTRY:
         raise KeyError(f"unknown model {name!r}; choose from {sorted(REGISTRY)}")
@@ -42,13 +50,13 @@ def build_model(name: str, num_classes: int | None = None, drop_path: float = 0.
     if not 0.0 <= drop_path < 1.0:
         raise ValueError(f"drop path rate must be in [0, 1), got {drop_path}")
     if drop_path > 0:
-        if not is_vit(key):
+        if not has_drop_path(key):
             raise ValueError(f"drop_path {drop_path} with model {name!r}: stochastic depth exists "
-                             "for the ViT models only (their residual adds carry it)")
+                             "for the ViT and ConvNeXt models only (their residual adds carry it)")
         return ctor(nc, drop_path=drop_path), shape, nc
     return ctor(nc), shape, nc
 
 
-__all__ = ["MLP", "AlexNet", "LeNet", "ResNet", "resnet18", "resnet34", "resnet50", "resnet101",
+__all__ = ["MLP", "AlexNet", "LeNet", "ConvNeXt", "convnext_mini", "convnext_tiny", "ResNet", "resnet18", "resnet34", "resnet50", "resnet101",
            "VisionTransformer", "vit_b16", "vit_mini_long", "vit_tiny", "REGISTRY", "build_model",
-           "is_vit"]
+           "has_drop_path", "is_vit"]

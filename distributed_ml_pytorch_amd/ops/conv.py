@@ -19,8 +19,12 @@ fp32 arena weight-gradient accumulation.
 Every other bf16 GPU conv (few input / output channels, large windows:
 AlexNet's 11x11/s4 stem, the LeNet convs, the ResNet-50 7x7 stem) runs as a
 native patch matrix (``csrc/im2col.hip``) on the native MFMA GEMM
-(``csrc/gemm.hip``) with bias / ReLU in its epilogue.  ``F.conv2d`` only for
-CPU / fp32 inputs.
+(``csrc/gemm.hip``) with bias / ReLU in its epilogue.
+
+Depthwise K x K convs (``groups == C``, K in 3 / 5 / 7, stride 1, "same" padding,
+``C % 8 == 0``: ConvNeXt's 7x7) run on the VALU + LDS kernels of
+``csrc/dwconv.hip``, all three passes, with a slab-reduced (atomic-free) weight
+and bias gradient.  ``F.conv2d`` only for CPU / fp32 inputs.
 """
 from __future__ import annotations
 
@@ -592,8 +596,93 @@ def im2col_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
     return _conv_route_ok(x, stride, padding, dilation, groups)
 
 
+# ------------------------------------------------------------ depthwise convs
+def depthwise_conv_supported(x, weight, stride, padding, dilation, groups) -> bool:
+    """Depthwise K x K (3 / 5 / 7), stride 1, "same" padding over a bf16 GPU input
+    with ``C % 8 == 0`` channels and a channel multiplier of 1: the VALU + LDS
+    kernels of ``csrc/dwconv.hip``."""
+    if not (_NATIVE_ENABLED and x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4):
+        return False
+    co, cig, r, s = weight.shape
+    k2 = r // 2
+    if not (groups == x.shape[1] == co and cig == 1 and groups % 8 == 0 and r == s
+            and r in (3, 5, 7)):
+        return False
+    return (_pair(stride) == (1, 1) and _pair(dilation) == (1, 1) and _pair(padding) == (k2, k2)
+            and x.shape[0] <= 65535 and groups <= 65535 * 32 and x.numel() < 2 ** 30)
+
+
+def dwconv_slab(owner, x, K: int):
+    """Persistent slab of the depthwise weight gradient on ``owner`` (its partials
+    are overwritten by every backward: never zeroed, so the step captures).  Its
+    size depends on the layer (C, K) alone: a captured step holds its address, so
+    no later call at another batch or map size may replace it."""
+    n = native().dwconv_slab_numel(x.shape[1], K)
+    buf = owner.__dict__.get("_dmp_dw_slab")
+    if buf is None or buf.device != x.device or buf.numel() != n:
+        buf = torch.empty(n, dtype=torch.float32, device=x.device)
+        owner.__dict__["_dmp_dw_slab"] = buf
+    return buf
+
+
+class _DepthwiseConv(Function):
+    """Depthwise conv on ``csrc/dwconv.hip``.  Saves ``x``; the data gradient (the
+    same kernel over ``dy`` with mirrored taps) runs only when ``x`` needs one.
+    ``alias``: ``x`` is handed back as a second output whose gradient is added in
+    the data-gradient epilogue (a residual block reads its input twice: autograd
+    would otherwise sum the two gradients with a stock add)."""
+
+    @staticmethod
+    def forward(ctx, x, w16, master, bias, slab, alias):
+        ctx.set_materialize_grads(False)
+        b32 = None
+        if bias is not None:
+            b32 = bias.detach()
+            if b32.dtype != torch.float32 or not b32.is_contiguous():
+                b32 = b32.float().contiguous()
+        y = native().dwconv_fwd(x, w16, b32)
+        ctx.save_for_backward(x, w16)
+        ctx.params = (master, bias, slab)
+        return y, (x.view_as(x) if alias else None)
+
+    @staticmethod
+    def backward(ctx, dy, dxa=None):
+        x, w16 = ctx.saved_tensors
+        master, bias, slab = ctx.params
+        if dxa is not None:
+            dxa = dxa.contiguous(memory_format=torch.channels_last)
+        if dy is None:
+            return (dxa if ctx.needs_input_grad[0] else None), None, None, None, None, None
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = native().dwconv_fwd(dy, w16, None, True, dxa)
+        sw = GradSink(master, master.requires_grad, "cl")
+        sb = GradSink(bias, bias is not None and bias.requires_grad)
+        if sw.buf is not None:
+            db = sb.buf if sb.buf is not None and sb.buf.dtype == torch.float32 else None
+            native().dwconv_wgrad(dy, x, sw.buf, db, slab)
+            if sb.buf is not None and db is None:
+                bias_grad_acc(dy, sb.buf)
+        elif sb.buf is not None:
+            bias_grad_acc(dy, sb.buf)
+        return dx, None, sw.done(), sb.done(), None, None
+
+
+def _depthwise(x, master, b, slab, alias):
+    w16 = _shadow16(master)
+    needs = torch.is_grad_enabled() and (x.requires_grad or master.requires_grad
+                                         or (b is not None and b.requires_grad))
+    if not needs:       # no autograd node under no_grad / for frozen layers
+        b32 = b.detach().float().contiguous() if b is not None else None
+        y = native().dwconv_fwd(x, w16, b32)
+        return (y, x) if alias else y
+    y, xa = _DepthwiseConv.apply(x, w16, master, b, slab, bool(alias))
+    return (y, xa) if alias else y
+
+
 def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=False,
-           slots=None, alias=False, relu=False, stem_scratch=None):
+           slots=None, alias=False, relu=False, stem_scratch=None, dw_slab=None):
     """Returns ``y`` (with BN slot sums attached as ``y._dmp_bn_part`` when ``want_stats``).
 
     ``stem_scratch``: the layer's ``stem_bwd_scratch`` (used on the MFMA stem route
@@ -605,6 +694,7 @@ def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=F
     into this conv's input gradient by the dgrad kernel itself.  ``alias="sub"``
     (native stride-2 convs): ``x_alias`` is ``x[:, :, ::2, ::2]`` (gathered), the
     input of a 1x1 / stride-2 shortcut run at stride 1; other routes hand back x.
+    ``dw_slab``: the layer's ``dwconv_slab`` (depthwise route); a fresh one when None.
     """
     if x.is_cuda and x.dim() == 4:
         x = x.contiguous(memory_format=torch.channels_last)
@@ -649,6 +739,9 @@ def conv2d(x, w, b, stride, padding, dilation, groups, master=None, want_stats=F
             if part is not None:
                 y._dmp_bn_part = part
             return (y, x) if alias else y
+        if master is not None and not relu and depthwise_conv_supported(
+                x, master, stride, padding, dilation, groups):
+            return _depthwise(x, master, b, dw_slab, alias)
         if master is not None and im2col_conv_supported(x, master, stride, padding, dilation,
                                                         groups):
             w16 = _shadow16(master)

@@ -946,6 +946,67 @@ def drop_path(x, rscale):
     return (x.float() * _sample_scale(rscale, x)).to(x.dtype)
 
 
+# ---------------------------------------------------- layer-scale residual add
+class _LayerScaleAdd(Function):
+    """``h = x + gamma * r (* rscale[sample])`` on ``csrc/layer_scale.hip``.  Backward:
+    ``dx`` is ``dh`` itself, ``dr`` and ``dgamma`` come from one pass over ``dh`` and
+    ``r``; ``dgamma`` goes through the layer's slot rows into the gradient sink."""
+
+    @staticmethod
+    def forward(ctx, x, r, gamma, rscale, slots):
+        x, r = x.contiguous(), r.contiguous()
+        h = native().layer_scale_fwd(x, r, gamma.detach(), rscale)
+        ctx.save_for_backward(r, rscale)
+        ctx.gamma, ctx.slots = gamma, slots
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        r, rscale = ctx.saved_tensors
+        gamma = ctx.gamma
+        sg = GradSink(gamma, ctx.needs_input_grad[2])
+        dr = native().layer_scale_bwd(dh.contiguous(), r, gamma.detach(), rscale, sg.buf,
+                                      ctx.slots, bool(ctx.needs_input_grad[1]))
+        return (dh if ctx.needs_input_grad[0] else None), dr, sg.done(), None, None
+
+
+def layer_scale_slots(owner, gamma):
+    """Persistent slot rows of a layer scale's ``dgamma`` on ``owner`` (overwritten
+    by every backward: never zeroed)."""
+    n = native().layer_scale_num_slots() * gamma.numel()
+    buf = owner.__dict__.get("_dmp_ls_slots")
+    if buf is None or buf.device != gamma.device or buf.numel() != n:
+        buf = torch.empty(n, dtype=torch.float32, device=gamma.device)
+        owner.__dict__["_dmp_ls_slots"] = buf
+    return buf
+
+
+def layer_scale_add(x, r, gamma, rscale=None, slots=None):
+    """``x + gamma * r`` over the last (channel) dim, ``r`` optionally times the
+    per-sample stochastic-depth scale ``rscale`` (float32 ``[B]``, a row of
+    :func:`drop_path_table`): the closing op of a ConvNeXt block.
+
+    The rounding is pinned: ``(x.float() + (gamma * r.float()) * s).to(x.dtype)`` with
+    every product and the sum rounded separately in fp32.  That torch expression
+    on the CPU, the native kernel (bit for bit the same) for bf16 GPU rows with
+    fp32 ``gamma`` and ``C % 8 == 0`` up to the kernel's widest row (2048); stock
+    kernels otherwise.
+    ``slots``: the layer's :func:`layer_scale_slots`."""
+    C = x.shape[-1]
+    if (x.is_cuda and x.dtype == torch.bfloat16 and r.dtype == torch.bfloat16
+            and x.shape == r.shape and gamma.dtype == torch.float32 and gamma.numel() == C
+            and C % 8 == 0 and C <= native().layer_scale_max_channels() and x.numel() > 0):
+        if torch.is_grad_enabled() and (x.requires_grad or r.requires_grad
+                                        or gamma.requires_grad):
+            return _LayerScaleAdd.apply(x, r, gamma, rscale, slots)
+        return native().layer_scale_fwd(x.contiguous(), r.contiguous(), gamma.detach(), rscale)
+    stock_gpu("layer_scale_add", x)
+    t = gamma.float() * r.float()
+    if rscale is not None:
+        t = t * _sample_scale(rscale, x)
+    return (x.float() + t).to(x.dtype)
+
+
 def layer_norm(x, weight, bias, eps: float, slots=None):
     """LayerNorm over the last dim: native row kernel for bf16 GPU input with fp32
     affine params (``csrc/transformer.hip``), PyTorch otherwise.  ``slots``: the

@@ -13,14 +13,16 @@ import torch.nn.functional as F
 
 from . import functional as DF
 from ._policy import stock_gpu
-from .conv import (bn_slot_buffer, conv2d as _conv2d, im2col_conv_supported,
-                   native_conv_supported, small_conv_supported, stem_bwd_scratch)
+from .conv import (bn_slot_buffer, conv2d as _conv2d, depthwise_conv_supported, dwconv_slab,
+                   im2col_conv_supported, native_conv_supported, small_conv_supported,
+                   stem_bwd_scratch)
 from .linear import arena_linear_ok, linear as _arena_linear
 
 
 class Conv2d(nn.Conv2d):
     """Conv2d on the native kernels for bf16 GPU input (implicit GEMM / halo
-    tiles, the VALU stem kernel, or patch matrix + MFMA GEMM: ``ops.conv``).
+    tiles, the VALU stem kernel, the depthwise kernels, or patch matrix + MFMA
+    GEMM: ``ops.conv``).
 
     ``emit_bn_stats`` (set by models where a BatchNorm follows) makes the
     native forward also produce the BN partial sums in its epilogue.
@@ -35,6 +37,14 @@ class Conv2d(nn.Conv2d):
         (``alias="sub"``: see ``ops.conv.conv2d``).  ``stride`` overrides the
         module's stride (a stride-2 shortcut applied to an already subsampled x)."""
         st = self.stride if stride is None else (stride, stride)
+        if not relu and depthwise_conv_supported(x, self.weight, st, self.padding, self.dilation,
+                                                 self.groups):
+            x = x.contiguous(memory_format=torch.channels_last)
+            # only where a backward can follow (not in a no_grad evaluation)
+            slab = dwconv_slab(self, x, self.kernel_size[0]) \
+                if torch.is_grad_enabled() and self.weight.requires_grad else None
+            return _conv2d(x, None, self.bias, st, self.padding, self.dilation, self.groups,
+                           master=self.weight, alias=alias, dw_slab=slab)
         if x.is_cuda and x.dtype == torch.bfloat16 and (
                 native_conv_supported(x, self.weight, st, self.padding, self.dilation,
                                       self.groups)

@@ -29,7 +29,7 @@ from dataclasses import asdict, dataclass, field
 import torch
 import torch.distributed as dist
 
-from ..models import build_model, is_vit
+from ..models import build_model, has_drop_path
 from ..ops.eval_fold import fold_session
 from ..ops.functional import softmax_cross_entropy, softmax_cross_entropy_mix, unit_grad
 from ..parallel.arena import attach_arena
@@ -596,14 +596,15 @@ def check_device_data_config(cfg: TrainConfig, info: DistInfo):
 
 
 def check_drop_path_config(cfg: TrainConfig):
-    """Stochastic depth lives in the ViT's fused residual adds: a rate outside
-    [0, 1), or a model without them, is an error at start-up."""
+    """Stochastic depth lives in the ViT's fused residual adds and ConvNeXt's
+    layer-scale add: a rate outside [0, 1), or a model without them, is an error
+    at start-up."""
     if not 0.0 <= cfg.drop_path < 1.0:
         raise ValueError(f"--drop-path must be in [0, 1), got {cfg.drop_path}")
-    if cfg.drop_path > 0 and not is_vit(cfg.model):
+    if cfg.drop_path > 0 and not has_drop_path(cfg.model):
         raise ValueError(f"--drop-path {cfg.drop_path} with --model {cfg.model}: stochastic depth "
-                         "exists for the ViT models only (the ResNets' residual add lives in "
-                         "the BatchNorm kernels)")
+                         "exists for the ViT and ConvNeXt models only (the ResNets' residual "
+                         "add lives in the BatchNorm kernels)")
 
 
 def check_model_ema_config(cfg: TrainConfig):
