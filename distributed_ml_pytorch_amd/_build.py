@@ -31,8 +31,11 @@ EXT_NAME = "_native"
 # flag buys a wave per SIMD (5 instead of 4) in kernels bound by LDS latency and
 # instruction issue.  layer_scale: memory-bound with every rounding pinned by
 # fp contract(off); the packed forms cannot shorten it, and it is built like
-# dwconv so that the two files of this family share one flag set.
-NO_PACKED_FP32 = {"dwconv", "layer_scale"}
+# dwconv so that the two files of this family share one flag set.  optim_trust:
+# memory-bound as well, and stage 1 and stage 2 of LAMB must form the same u bit
+# for bit, which is simplest to keep true with one scalar instruction per
+# operation.
+NO_PACKED_FP32 = {"dwconv", "layer_scale", "optim_trust"}
 _NO_PACKED_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 

@@ -69,10 +69,17 @@ def build_parser() -> argparse.ArgumentParser:
                    choices=["constant", "inv_epoch", "warmup_cosine"],
                    help="inv_epoch: lr / (epoch + 1) per epoch (host); warmup_cosine: linear "
                         "warm-up then cosine decay to --lr-min, per step on the device")
-    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw"])
+    p.add_argument("--optimizer", default="sgd", choices=["sgd", "adamw", "lamb", "lars"],
+                   help="lamb / lars: layer-wise adaptive (per-tensor trust ratios) for large "
+                        "batches; --beta1 / --beta2 / --adam-eps serve lamb, --momentum, "
+                        "--trust-coef and --lars-eps serve lars")
     p.add_argument("--beta1", type=float, default=0.9)
     p.add_argument("--beta2", type=float, default=0.999)
     p.add_argument("--adam-eps", type=float, default=1e-8)
+    p.add_argument("--trust-coef", type=float, default=0.001,
+                   help="--optimizer lars: coefficient of the local learning rate")
+    p.add_argument("--lars-eps", type=float, default=0.0,
+                   help="--optimizer lars: added to the local learning rate's denominator")
     p.add_argument("--clip-grad-norm", type=float, default=0.0, metavar="MAX",
                    help="clip the global gradient norm to MAX (0 = off)")
     p.add_argument("--warmup-steps", type=int, default=0)
@@ -188,7 +195,8 @@ def config_from_args(a) -> TrainConfig:
         stale_policy=a.stale_policy, delay_comp=a.delay_comp, bucket_mb=a.bucket_mb,
         label_smoothing=a.label_smoothing, divergence_check=not a.no_divergence_check,
         deterministic=a.deterministic, optimizer=a.optimizer, beta1=a.beta1, beta2=a.beta2,
-        adam_eps=a.adam_eps, clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,
+        adam_eps=a.adam_eps, trust_coef=a.trust_coef, lars_eps=a.lars_eps,
+        clip_grad_norm=a.clip_grad_norm, warmup_steps=a.warmup_steps,
         lr_min=a.lr_min, schedule_steps=a.schedule_steps, device_data=a.device_data,
         augment=a.augment, crop_pad=4 if a.crop_pad is None else a.crop_pad,
         rrc_scale=tuple(a.rrc_scale), rrc_ratio=tuple(a.rrc_ratio), stored_size=a.stored_size,

@@ -2,6 +2,8 @@
 // hand-offs, casts and fills.
 #include "util.h"
 
+#include "optim_trust.h"
+
 namespace dmp::bind {
 namespace {
 
@@ -111,6 +113,121 @@ void adamw_fused_step(Tensor g, Tensor p, optional<Tensor> acc, Tensor m, Tensor
                                m.data_ptr<float>(), v.data_ptr<float>(), bf16_or_null(w16),
                                ptr_or_null<const uint8_t>(decay), n, hyper.data_ptr<float>(),
                                (float)wd, (float)eps, cur_stream(), ema_ptr(ema, p, n));
+}
+
+// ---- LAMB / LARS (optim_trust.hip; tables: fused_optim.trust_tables)
+// int32 [rows, 3] table; `where`: at::kCPU for the host check, at::kCUDA for a step
+void check_trust_table(const Tensor& t, c10::DeviceType where, const char* name) {
+  TORCH_CHECK(t.device().type() == where && t.scalar_type() == at::kInt && t.is_contiguous() &&
+                  t.dim() == 2 && t.size(1) == dmp::kTrustRow,
+              name, " must be a contiguous int32 [rows, ", dmp::kTrustRow, "] tensor on the ",
+              where == at::kCPU ? "host" : "device", ", got ", t.scalar_type(), " ", t.sizes(),
+              " on ", t.device());
+}
+
+// The host-side check of a chunk table and its tensor table against an arena of
+// n elements, before they are copied to the device (the kernels skip a bad row,
+// they do not report it): chunks of at most kTrustChunk elements that start on
+// a 64-element boundary and end inside n; every tensor's chunks are the rows it
+// names, in order, without a gap.
+void trust_check_tables(Tensor chunks, Tensor tens, int64_t n) {
+  check_trust_table(chunks, at::kCPU, "chunks");
+  check_trust_table(tens, at::kCPU, "tens");
+  TORCH_CHECK(n > 0 && n % 64 == 0 && n < (int64_t(1) << 31),
+              "trust tables: the arena length must be a positive multiple of 64 below 2^31, got ",
+              n);
+  const int64_t nc = chunks.size(0), nt = tens.size(0);
+  const int* c = chunks.data_ptr<int>();
+  const int* t = tens.data_ptr<int>();
+  for (int64_t i = 0; i < nc; ++i) {
+    const int64_t id = c[3 * i], start = c[3 * i + 1], cnt = c[3 * i + 2];
+    TORCH_CHECK(id >= 0 && id < nt, "chunk ", i, " names tensor ", id, " of ", nt);
+    TORCH_CHECK(cnt >= 1 && cnt <= dmp::kTrustChunk, "chunk ", i, " has ", cnt,
+                " elements; a chunk holds 1..", dmp::kTrustChunk);
+    TORCH_CHECK(start >= 0 && start % 64 == 0, "chunk ", i, " starts at element ", start,
+                ", not on a 64-element boundary");
+    TORCH_CHECK(start + cnt <= n, "chunk ", i, " [", start, ", ", start + cnt,
+                ") crosses the arena length ", n);
+  }
+  for (int64_t i = 0; i < nt; ++i) {
+    const int64_t first = t[3 * i], cnt = t[3 * i + 1];
+    TORCH_CHECK(first >= 0 && cnt >= 0 && first + cnt <= nc, "tensor ", i, " names chunks [",
+                first, ", ", first + cnt, ") of ", nc);
+    for (int64_t j = first; j < first + cnt; ++j)
+      TORCH_CHECK(c[3 * j] == i, "chunk ", j, " belongs to tensor ", c[3 * j],
+                  ", the tensor table gives it to ", i);
+  }
+}
+
+// what a step takes: both tables on p's device and scratch long enough for them
+dmp::TrustTables trust_step_tables(const char* fn, const Tensor& chunks, const Tensor& tens,
+                                   const Tensor& partials, const Tensor& trust, const Tensor& p,
+                                   int64_t n) {
+  TORCH_CHECK(n % 64 == 0, fn, ": the arena length must be a multiple of 64, got ", n);
+  TORCH_CHECK(n < (int64_t(1) << 31), fn, ": the arena length must be below 2^31");
+  check_trust_table(chunks, at::kCUDA, "chunks");
+  check_trust_table(tens, at::kCUDA, "tens");
+  const int64_t nc = chunks.size(0), nt = tens.size(0);
+  for (const Tensor* b : {&partials, &trust})
+    TORCH_CHECK(b->is_cuda() && b->scalar_type() == at::kFloat && b->is_contiguous() &&
+                    aligned(*b),
+                fn, ": partials and trust must be contiguous, 16-byte aligned fp32 GPU tensors");
+  TORCH_CHECK(partials.numel() >= 2 * nc, fn, ": partials has ", partials.numel(),
+              " elements, ", nc, " chunks need ", 2 * nc);
+  TORCH_CHECK(trust.numel() >= dmp::kTrustOut * nt, fn, ": trust has ", trust.numel(),
+              " elements, ", nt, " tensors need ", dmp::kTrustOut * nt);
+  TORCH_CHECK(chunks.device() == p.device() && tens.device() == p.device() &&
+                  partials.device() == p.device() && trust.device() == p.device(),
+              fn, ": tables, partials and trust must be on the parameters' device");
+  return {chunks.data_ptr<int>(), (int)nc, tens.data_ptr<int>(), (int)nt,
+          partials.data_ptr<float>(), trust.data_ptr<float>()};
+}
+
+// One LAMB step after optim_hyper: stage 1, reduce, stage 2 on the current stream
+void lamb_fused_step(Tensor g, Tensor p, optional<Tensor> acc, Tensor m, Tensor v,
+                     optional<Tensor> w16, Tensor chunks, Tensor tens, Tensor partials,
+                     Tensor trust, Tensor hyper, double wd, double eps, optional<Tensor> ema,
+                     int64_t grid_cap) {
+  const int64_t n = flat_len(p, "flat arena length");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat(g, at::kFloat, n, "g");
+  check_flat(m, at::kFloat, n, "m");
+  check_flat(v, at::kFloat, n, "v");
+  check_flat_opt(acc, at::kFloat, n, "acc");
+  check_flat_opt(w16, at::kBFloat16, n, "w16");
+  check_hyper(hyper, p);
+  TORCH_CHECK(g.device() == p.device() && m.device() == p.device() && v.device() == p.device(),
+              "g, p, m and v must share a device");
+  const dmp::TrustTables t =
+      trust_step_tables("lamb_fused_step", chunks, tens, partials, trust, p, n);
+  dmp::launch_lamb_step(g.data_ptr<float>(), p.data_ptr<float>(), ptr_or_null<float>(acc),
+                        m.data_ptr<float>(), v.data_ptr<float>(), bf16_or_null(w16), t, n,
+                        hyper.data_ptr<float>(), (float)wd, (float)eps,
+                        (int)std::min<int64_t>(std::max<int64_t>(grid_cap, 0), 1 << 30),
+                        cur_stream(), ema_ptr(ema, p, n));
+}
+
+// One LARS step after optim_hyper; `mom` is the momentum buffer (always present)
+void lars_fused_step(Tensor g, Tensor p, optional<Tensor> acc, Tensor mom, optional<Tensor> w16,
+                     Tensor chunks, Tensor tens, Tensor partials, Tensor trust, Tensor hyper,
+                     double wd, double momentum, double trust_coef, double lars_eps,
+                     optional<Tensor> ema, int64_t grid_cap) {
+  const int64_t n = flat_len(p, "flat arena length");
+  check_flat(p, at::kFloat, n, "p");
+  check_flat(g, at::kFloat, n, "g");
+  check_flat(mom, at::kFloat, n, "mom");
+  check_flat_opt(acc, at::kFloat, n, "acc");
+  check_flat_opt(w16, at::kBFloat16, n, "w16");
+  check_hyper(hyper, p);
+  TORCH_CHECK(g.device() == p.device() && mom.device() == p.device(),
+              "g, p and mom must share a device");
+  const dmp::TrustTables t =
+      trust_step_tables("lars_fused_step", chunks, tens, partials, trust, p, n);
+  dmp::launch_lars_step(g.data_ptr<float>(), p.data_ptr<float>(), ptr_or_null<float>(acc),
+                        mom.data_ptr<float>(), bf16_or_null(w16), t, n, hyper.data_ptr<float>(),
+                        (float)wd, (float)momentum, (float)trust_coef, (float)lars_eps,
+                        (int)std::min<int64_t>(std::max<int64_t>(grid_cap, 0), 1 << 30),
+                        cur_stream(), ema_ptr(ema, p, n));
 }
 
 // p <-> e in place, w16 = bf16(new p): evaluation on the averaged weights
@@ -433,6 +550,21 @@ void bind_optim(pybind11::module_& m) {
         py::arg("p"), py::arg("acc"), py::arg("m"), py::arg("v"), py::arg("w16"),
         py::arg("decay"), py::arg("hyper"), py::arg("wd"), py::arg("eps"),
         py::arg("ema") = py::none());
+  m.def("trust_chunk", []() { return dmp::trust_chunk(); },
+        "elements of the longest chunk of a LAMB / LARS chunk table");
+  m.def("trust_check_tables", &trust_check_tables,
+        "host-side check of a LAMB / LARS chunk table and tensor table", py::arg("chunks"),
+        py::arg("tens"), py::arg("n"));
+  m.def("lamb_fused_step", &lamb_fused_step, "fused flat LAMB update (stage 1, reduce, stage 2)",
+        py::arg("g"), py::arg("p"), py::arg("acc"), py::arg("m"), py::arg("v"), py::arg("w16"),
+        py::arg("chunks"), py::arg("tens"), py::arg("partials"), py::arg("trust"),
+        py::arg("hyper"), py::arg("wd"), py::arg("eps"), py::arg("ema") = py::none(),
+        py::arg("grid_cap") = 0);
+  m.def("lars_fused_step", &lars_fused_step, "fused flat LARS update (norms, reduce, stage 2)",
+        py::arg("g"), py::arg("p"), py::arg("acc"), py::arg("mom"), py::arg("w16"),
+        py::arg("chunks"), py::arg("tens"), py::arg("partials"), py::arg("trust"),
+        py::arg("hyper"), py::arg("wd"), py::arg("momentum"), py::arg("trust_coef"),
+        py::arg("lars_eps"), py::arg("ema") = py::none(), py::arg("grid_cap") = 0);
   m.def("arena_swap", &arena_swap, "exchange p and its EMA in place, refresh the bf16 shadow",
         py::arg("p"), py::arg("ema"), py::arg("w16") = py::none());
   m.def("ema_buffers", &ema_buffers, "EMA update / exchange of the model's fp32 buffers",

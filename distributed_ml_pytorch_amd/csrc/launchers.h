@@ -83,6 +83,32 @@ void launch_cast_f32_bf16(const float* src, uint16_t* dst, long long n, hipStrea
 int launch_sumsq_partial(const float* x, float* partial, long long n, hipStream_t s);
 void launch_zero_fill(void* p, long long bytes, hipStream_t s);
 
+// optim_trust.hip: LAMB and LARS over the flat arena (layout: optim_trust.h).
+// The device tables and scratch of one optimizer: `chunks` int32 [nchunks][3]
+// (tensor, start element, element count), `tens` int32 [ntens][3] (first chunk,
+// chunk count, adapt flag), `partials` fp32 [2 * nchunks], `trust` fp32
+// [4 * ntens] (scalar, ||p||, ||u|| or ||g'||, 0).  Rows are checked against n on
+// the device as well; a bad row is skipped.
+struct TrustTables {
+  const int* chunks;
+  int nchunks;
+  const int* tens;
+  int ntens;
+  float* partials;
+  float* trust;
+};
+int trust_chunk();
+// One step = stage 1, reduce, stage 2 on `s`, after launch_optim_hyper; n % 64 ==
+// 0.  `grid_cap` > 0 lowers the workgroup count of the stage launches (the
+// results do not depend on it).  acc / w16 / ema may be null.
+void launch_lamb_step(const float* g, float* p, float* acc, float* m, float* v, uint16_t* w16,
+                      const TrustTables& t, long long n, const float* hyper, float wd, float eps,
+                      int grid_cap, hipStream_t s, float* ema = nullptr);
+void launch_lars_step(const float* g, float* p, float* acc, float* mom, uint16_t* w16,
+                      const TrustTables& t, long long n, const float* hyper, float wd,
+                      float momentum, float trust_coef, float lars_eps, int grid_cap,
+                      hipStream_t s, float* ema = nullptr);
+
 // xent.hip
 void launch_softmax_xent_bf16(const uint16_t* logits, const int64_t* labels, uint16_t* dlogits,
                               float* row_loss, int* row_hit, float* loss_out, int* hits_out,

@@ -28,7 +28,7 @@ from torch.optim.optimizer import Optimizer, required
 from .arena import attach_arena, get_arena
 from .clients import GlooPSClient, LocalPSClient, PSClient, check_push_wire
 from .ema import ModelEma
-from .fused_optim import FusedOptimCore, check_ema_options, sync_base_lr
+from .fused_optim import KINDS, FusedOptimCore, check_ema_options, sync_base_lr
 
 
 def default_client(**kw) -> PSClient:
@@ -46,8 +46,13 @@ class Asynchronous(Optimizer):
                  shadow_dtype: torch.dtype | None | str = "auto", optimizer: str = "sgd",
                  betas=(0.9, 0.999), eps: float = 1e-8, max_grad_norm: float = 0.0,
                  schedule=None, push_wire: str = "same", push_topk: int = 8,
-                 ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False):
-        """``ema_decay > 0``: an exponential moving average of the parameters and the
+                 ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False,
+                 trust_coef: float = 0.001, lars_eps: float = 0.0):
+        """``optimizer``: ``"sgd"``, ``"adamw"``, ``"lamb"`` or ``"lars"`` (the
+        layer-wise adaptive kinds of :mod:`.fused_optim`; ``momentum`` serves LARS,
+        which takes neither ``nesterov`` nor ``dampening``).
+
+        ``ema_decay > 0``: an exponential moving average of the parameters and the
         floating-point buffers is kept by the update pass (:mod:`.fused_optim`,
         :mod:`.ema`; ``self.ema.applied()`` evaluates with it).  A pull landing is no
         EMA event: the average sees the landed values at its next update.
@@ -65,8 +70,10 @@ class Asynchronous(Optimizer):
             raise ValueError(f"Invalid learning rate: {lr}")
         if int(n_push) < 1 or int(n_pull) < 1:
             raise ValueError("n_push and n_pull must be >= 1")
-        if optimizer not in ("sgd", "adamw"):
-            raise ValueError(f"unknown optimizer {optimizer!r}; 'sgd' or 'adamw'")
+        if optimizer not in KINDS:
+            raise ValueError(f"unknown optimizer {optimizer!r}; one of {KINDS}")
+        if optimizer == "lars" and (nesterov or dampening):
+            raise ValueError("optimizer 'lars' takes neither nesterov nor dampening")
         check_ema_options(ema_decay, ema_every, ema_warmup)
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
                         weight_decay=weight_decay)
@@ -88,17 +95,19 @@ class Asynchronous(Optimizer):
         dev = arena.device
         self.acc = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
         self._mom_steps = 0
-        self.mom = torch.zeros_like(self.acc) if momentum and optimizer == "sgd" else None
+        self.mom = torch.zeros_like(self.acc) if (momentum and optimizer == "sgd") or \
+            optimizer == "lars" else None
         # AdamW, clipping, a per-step schedule or a model EMA: the update reads lr
         # and the gradient scale from a device-resident hyper block
         # (fused_optim.py); plain constant-lr SGD keeps the by-value kernel
         self.core = None
-        if optimizer == "adamw" or max_grad_norm > 0 or schedule is not None or ema_decay > 0:
+        if optimizer != "sgd" or max_grad_norm > 0 or schedule is not None or ema_decay > 0:
+            trust = dict(trust_coef=trust_coef, lars_eps=lars_eps) if optimizer == "lars" else {}
             self.core = FusedOptimCore(arena, optimizer, lr, betas=betas, eps=eps,
                                        weight_decay=weight_decay, momentum=momentum,
                                        nesterov=nesterov, max_grad_norm=max_grad_norm,
                                        schedule=schedule, model=model, ema_decay=ema_decay,
-                                       ema_every=ema_every, ema_warmup=ema_warmup)
+                                       ema_every=ema_every, ema_warmup=ema_warmup, **trust)
         self.idx = 0
         self.timer = _NO_TIMER      # a utils.metrics.StepTimer when the trainer wires one
         if client is None:

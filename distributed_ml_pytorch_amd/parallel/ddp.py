@@ -259,6 +259,7 @@ class FusedAdamW(Optimizer):
     (:class:`~.fused_optim.Schedule`) act on the device: no gradient is
     rescaled by a separate pass and a captured step is captured once.
     """
+    KIND = "adamw"
 
     def __init__(self, params, arena: FlatArena, lr: float = 1e-3, betas=(0.9, 0.999),
                  eps: float = 1e-8, weight_decay: float = 0.01, grad_scale: float = 1.0,
@@ -266,7 +267,7 @@ class FusedAdamW(Optimizer):
                  ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False):
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.arena = arena
-        self.core = FusedOptimCore(arena, "adamw", lr, betas=betas, eps=eps,
+        self.core = FusedOptimCore(arena, self.KIND, lr, betas=betas, eps=eps,
                                    weight_decay=weight_decay, grad_scale=grad_scale,
                                    max_grad_norm=max_grad_norm, schedule=schedule, model=model,
                                    ema_decay=ema_decay, ema_every=ema_every,
@@ -294,5 +295,64 @@ class FusedAdamW(Optimizer):
         self.arena.bump()
         sync_base_lr(self.core, self.param_groups[0]["lr"])
         self.core.step(self.arena, None)
+        if self.ema is not None:
+            self.ema.update_buffers()
+
+
+class FusedLAMB(FusedAdamW):
+    """LAMB over a flat arena (``sync`` / ``single``): AdamW's moments and
+    arguments, the update of every tensor with ``dim() > 1`` that is not named in
+    ``no_weight_decay()`` scaled by its trust ratio ``||p|| / ||u||``
+    (:mod:`.fused_optim`; three native launches per step, captured once).
+    ``core.trust_ratios()`` reads the ratios of the last step back."""
+    KIND = "lamb"
+
+
+class FusedLARS(Optimizer):
+    """LARS with momentum over a flat arena (``sync`` / ``single``): SGD whose
+    gradient and weight decay are scaled per tensor by the local learning rate
+    ``trust_coef ||p|| / (||g|| + wd ||p|| + lars_eps)`` for every tensor with
+    ``dim() > 1`` that is not named in ``no_weight_decay()`` (:mod:`.fused_optim`).
+    No nesterov and no dampening."""
+
+    def __init__(self, params, arena: FlatArena, lr: float, momentum: float = 0.9,
+                 weight_decay: float = 0.0, trust_coef: float = 0.001, lars_eps: float = 0.0,
+                 grad_scale: float = 1.0, max_grad_norm: float = 0.0, schedule=None, model=None,
+                 ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False):
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
+                                      trust_coef=trust_coef, lars_eps=lars_eps))
+        self.arena = arena
+        self.mom = torch.zeros_like(arena.p32)      # checkpointed where FusedSGD's is
+        self._mom_steps = 0
+        self.core = FusedOptimCore(arena, "lars", lr, weight_decay=weight_decay,
+                                   momentum=momentum, grad_scale=grad_scale,
+                                   max_grad_norm=max_grad_norm, schedule=schedule, model=model,
+                                   ema_decay=ema_decay, ema_every=ema_every,
+                                   ema_warmup=ema_warmup, trust_coef=trust_coef,
+                                   lars_eps=lars_eps)
+        self.ema = ModelEma(model, self.core) if ema_decay > 0 else None
+
+    def zero_grad(self, set_to_none: bool = False):
+        self.arena.ensure_grads_attached()
+        self.arena.zero_grad()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.local_step()
+        return loss
+
+    def comm_step(self):
+        pass
+
+    @torch.no_grad()
+    def local_step(self):
+        self.arena.bump()
+        self._mom_steps += 1
+        sync_base_lr(self.core, self.param_groups[0]["lr"])
+        self.core.step(self.arena, None, self.mom)
         if self.ema is not None:
             self.ema.update_buffers()

@@ -29,6 +29,36 @@ shifts) and for the names a model lists in ``no_weight_decay()``; AdamW's
 decoupled weight decay skips them.  It is held as one ``uint8`` per 64-element
 arena block (every parameter starts on such a boundary, ``arena.ALIGN``).
 
+Layer-wise adaptive kinds, ``"lamb"`` and ``"lars"`` (GPU: ``optim_hyper`` +
+``lamb_fused_step`` / ``lars_fused_step`` of ``csrc/optim_trust.hip``).  Both keep
+everything above -- ``gscale``, ``lr_t``, ``acc``, the shadow, the EMA -- and add
+one scalar per tensor.  The *adapt set* is the tensors whose decay-mask bit is 1
+(``dim() > 1`` and not in ``no_weight_decay()``; timm's and apex's default); every
+other tensor has scalar 1 and no weight decay.  ``||x_i||`` runs over the tensor's
+own ``numel`` elements: pad elements of the arena never enter a norm and are never
+changed, whatever they hold.  With ``fl`` = one fp32 rounding::
+
+    LAMB (You et al. 2020; apex FusedLAMB adam_w_mode, timm Lamb):
+      m, v     as AdamW above (its expressions, its hyper words)
+      u        = fl(fl(fl(m / bc1) / fl(fl(sqrt(v) / sqrt(bc2)) + eps)) + fl(wd decay p))
+      trust_i  = fl32(||p_i|| / ||u_i||)  in the adapt set with both norms > 0, else 1
+      p        = fl(p - fl(fl(lr_t trust_i) u))
+    LARS (You et al. 2017, with momentum; the NVIDIA / torchvision form):
+      g'       = fl(gscale g)
+      local_i  = fl32(trust_coef ||p_i|| / (||g'_i|| + wd ||p_i|| + lars_eps))
+                 in the adapt set with both norms > 0, else 1
+      mom      = fl(fl(momentum mom) + fl(local_i fl(g' + fl(wd decay p))))
+      p        = fl(p - fl(lr_t mom))
+
+No multiply-add is contracted in these lines (the kernels pin that), and LAMB's
+``u`` is formed twice on the GPU from the same ``m``, ``v``, ``p`` by the same
+expression: the bits that were summed are the bits that are applied.  A norm is
+the square root of a sum of fp32 squares: on the GPU per-lane fp32 sums over a
+chunk of at most ``trust_chunk()`` elements in a fixed order, then the chunks of
+a tensor in fp64 in a fixed order (:func:`trust_tables`; bitwise reproducible,
+independent of the grid); on the CPU one fp64 sum.  The ratio is formed in fp64
+and rounded once.  ``nesterov`` and ``dampening`` do not exist for ``lars``.
+
 Model EMA (``ema_decay > 0``; evaluation through :mod:`.ema`): a flat fp32
 buffer ``e`` of the arena's length, a copy of ``p32`` when the optimizer is
 built, averaged in the same pass after the parameter update of step ``t``::
@@ -160,6 +190,33 @@ def decay_mask(arena: FlatArena, model: torch.nn.Module | None = None) -> torch.
     return mask
 
 
+TRUST_CHUNK = 8192          # csrc/optim_trust.h kTrustChunk (asserted against the extension)
+KINDS = ("sgd", "adamw", "lamb", "lars")
+
+
+def trust_tables(arena: FlatArena, mask: torch.Tensor, chunk: int = TRUST_CHUNK):
+    """``(chunks, tens)`` of LAMB / LARS, int32 on the host, a function of the arena
+    layout alone.  ``chunks [C, 3]``: (tensor, start element, element count), the
+    tensors cut into runs of at most ``chunk`` elements; a run never crosses a
+    tensor and starts on a 64-element boundary.  ``tens [T, 3]``: (first chunk,
+    chunk count, adapt flag = the tensor's decay-mask bit)."""
+    if chunk < ALIGN or chunk % ALIGN:
+        raise ValueError(f"chunk length must be a positive multiple of {ALIGN}, got {chunk}")
+    if not arena.slots:
+        raise ValueError("LAMB / LARS need the arena's tensor layout (arena.slots is empty)")
+    chunks, tens = [], []
+    for i, s in enumerate(arena.slots):
+        first = len(chunks)
+        chunks += [(i, s.offset + o, min(chunk, s.numel - o)) for o in range(0, s.numel, chunk)]
+        tens.append((first, len(chunks) - first, int(mask[s.offset // ALIGN]) if s.numel else 0))
+    return (torch.tensor(chunks, dtype=torch.int32).reshape(-1, 3),
+            torch.tensor(tens, dtype=torch.int32).reshape(-1, 3))
+
+
+def _norm64(x: torch.Tensor) -> float:
+    return float(x.double().square().sum().sqrt())
+
+
 def sync_base_lr(core: "FusedOptimCore", lr: float):
     """Adopt a ``param_groups`` lr the host changed (``inv_epoch``, user code).
     A captured step never gets here with a new value: the base lr of a device
@@ -180,9 +237,14 @@ class FusedOptimCore:
                  momentum: float = 0.0, nesterov: bool = False, grad_scale: float = 1.0,
                  max_grad_norm: float = 0.0, schedule=None,
                  model: torch.nn.Module | None = None, ema_decay: float = 0.0,
-                 ema_every: int = 1, ema_warmup: bool = False):
-        if kind not in ("sgd", "adamw"):
-            raise ValueError(f"unknown optimizer {kind!r}; 'sgd' or 'adamw'")
+                 ema_every: int = 1, ema_warmup: bool = False, trust_coef: float = 0.001,
+                 lars_eps: float = 0.0):
+        if kind not in KINDS:
+            raise ValueError(f"unknown optimizer {kind!r}; one of {KINDS}")
+        if kind == "lars" and nesterov:
+            raise ValueError("LARS has no nesterov form here")
+        if kind == "lars" and not (trust_coef > 0.0 and lars_eps >= 0.0):
+            raise ValueError("LARS needs trust_coef > 0 and lars_eps >= 0")
         if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"betas must be in [0, 1): {betas}")
         if eps < 0.0 or max_grad_norm < 0.0 or lr < 0.0:
@@ -210,11 +272,29 @@ class FusedOptimCore:
 
             self.native = native()
             assert self.native.optim_hyper_words() == HYPER_WORDS
+        self.trust_coef = float(trust_coef)
+        self.lars_eps = float(lars_eps)
         self.m = self.v = self.mask = None
-        if kind == "adamw":
+        if kind in ("adamw", "lamb"):
             self.m = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
             self.v = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
+        if kind != "sgd":
             self.mask = decay_mask(arena, model).to(dev)
+        # LAMB / LARS: the chunk and tensor tables of this arena, one float2 of
+        # partial sums per chunk and four words of results per tensor.  Nothing
+        # here is ever zeroed: a step writes every word it reads.
+        self.chunks = self.tens = self.trust_partials = self.trust = None
+        self.trust_grid_cap = 0             # > 0: fewer workgroups (same results)
+        if kind in ("lamb", "lars"):
+            self.chunks, self.tens = trust_tables(arena, self.mask.cpu())
+            self.trust = torch.ones(self.tens.shape[0], 4, dtype=torch.float32)
+            if self.native is not None:
+                assert self.native.trust_chunk() == TRUST_CHUNK
+                self.native.trust_check_tables(self.chunks, self.tens, arena.numel)
+                self.chunks, self.tens = self.chunks.to(dev), self.tens.to(dev)
+                self.trust = self.trust.to(dev)
+                self.trust_partials = torch.empty(2 * self.chunks.shape[0], dtype=torch.float32,
+                                                  device=dev)
         self.partials = None
         if self.native is not None and self.max_grad_norm > 0:
             self.partials = torch.zeros(_PARTIALS, dtype=torch.float32, device=dev)
@@ -260,7 +340,7 @@ class FusedOptimCore:
         checkpoint load, a new base lr / schedule length): one small H2D copy."""
         h = torch.zeros(HYPER_WORDS, dtype=torch.float32)
         hi = h.view(torch.int32)
-        b1, b2 = self.betas if self.kind == "adamw" else (0.0, 0.0)
+        b1, b2 = self.betas if self.kind in ("adamw", "lamb") else (0.0, 0.0)
         t = self._t
         hi[H_STEP] = t
         h[H_LR] = self._lr_t
@@ -336,10 +416,22 @@ class FusedOptimCore:
         """One update of ``arena.p32`` from ``arena.g32`` (+ bf16 shadow, + ``acc``).
         ``mom`` / ``dampening``: the SGD momentum buffer and this step's dampening."""
         a = arena if arena is not None else self.arena
+        if self.kind == "lars" and (mom is None or dampening):
+            raise ValueError("LARS needs a momentum buffer and takes no dampening")
         if self.native is not None:
             clip = self.partials is not None
             self.native.optim_hyper(self.hyper, a.g32 if clip else None, self.partials)
-            if self.kind == "adamw":
+            if self.kind == "lamb":
+                self.native.lamb_fused_step(a.g32, a.p32, acc, self.m, self.v, a.w16, self.chunks,
+                                            self.tens, self.trust_partials, self.trust,
+                                            self.hyper, self.weight_decay, self.eps, self.ema,
+                                            self.trust_grid_cap)
+            elif self.kind == "lars":
+                self.native.lars_fused_step(a.g32, a.p32, acc, mom, a.w16, self.chunks, self.tens,
+                                            self.trust_partials, self.trust, self.hyper,
+                                            self.weight_decay, self.momentum, self.trust_coef,
+                                            self.lars_eps, self.ema, self.trust_grid_cap)
+            elif self.kind == "adamw":
                 self.native.adamw_fused_step(a.g32, a.p32, acc, self.m, self.v, a.w16, self.mask,
                                              self.hyper, self.weight_decay, self.eps, self.ema)
             else:
@@ -359,13 +451,37 @@ class FusedOptimCore:
         lr = self._lr_t = self.schedule.lr_at(self.base_lr, t)
         gs = g * gscale if gscale != 1.0 else g
         p = a.p32
-        if self.kind == "adamw":
+        if self.kind in ("adamw", "lamb"):
             b1, b2 = self.betas
             self.m.mul_(b1).add_(gs, alpha=1.0 - b1)
             self.v.mul_(b2).addcmul_(gs, gs, value=1.0 - b2)
             denom = self.v.sqrt().div_(math.sqrt(1.0 - b2 ** t)).add_(self.eps)
+        if self.kind == "adamw":
             keep = 1.0 - lr * self.weight_decay * self._decay_elems()
             new = p * keep - (lr / (1.0 - b1 ** t)) * (self.m / denom)
+        elif self.kind == "lamb":
+            # one torch operation per rounding of the docstring's u
+            u = (self.m / (1.0 - b1 ** t)) / denom + (self.weight_decay * self._decay_elems()) * p
+            new = p.clone()                 # pad elements keep what they hold
+            for i, s, adapt in self._tensors():
+                sl = slice(s.offset, s.offset + s.numel)
+                pn, un = _norm64(p[sl]), _norm64(u[sl])
+                r = _f32(pn / un) if adapt and pn > 0.0 and un > 0.0 else 1.0
+                self.trust[i] = torch.tensor([r, pn, un, 0.0])
+                new[sl] = p[sl] - _f32(_f32(lr) * r) * u[sl]
+        elif self.kind == "lars":
+            wd = self.weight_decay
+            new = p.clone()
+            for i, s, adapt in self._tensors():
+                sl = slice(s.offset, s.offset + s.numel)
+                pn, gn = _norm64(p[sl]), _norm64(gs[sl])
+                r = 1.0
+                if adapt and pn > 0.0 and gn > 0.0:
+                    r = _f32(self.trust_coef * pn / (gn + wd * pn + self.lars_eps))
+                self.trust[i] = torch.tensor([r, pn, gn, 0.0])
+                d = r * (gs[sl] + (wd if adapt else 0.0) * p[sl])
+                mom[sl] = self.momentum * mom[sl] + d
+                new[sl] = p[sl] - lr * mom[sl]
         else:
             d = gs
             if self.weight_decay:
@@ -384,6 +500,19 @@ class FusedOptimCore:
             self._ema_last = (D, O)
             if O != 0.0:
                 self.ema.copy_(self.ema.mul(D).add(p.mul(O)))
+
+    def _tensors(self):
+        """(index, slot, adapt flag) of every tensor of the arena (LAMB / LARS)."""
+        return [(i, s, bool(self.tens[i, 2])) for i, s in enumerate(self.arena.slots)]
+
+    def trust_ratios(self) -> torch.Tensor:
+        """LAMB / LARS: fp32 ``[tensors, 3]`` on the host, per tensor of the arena the
+        scalar of the last step (LAMB's trust ratio, LARS's local learning rate; 1
+        outside the adapt set), ``||p||`` before that step and ``||u||`` (LAMB) or
+        ``||g'||`` (LARS).  A device read-back on the GPU: for logging and tests."""
+        if self.trust is None:
+            raise ValueError(f"{self.kind!r} forms no per-tensor trust ratios")
+        return self.trust.detach().cpu()[:, :3].clone()
 
     def _decay_elems(self) -> torch.Tensor:
         if getattr(self, "_decay_f", None) is None:

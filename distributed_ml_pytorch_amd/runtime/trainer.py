@@ -37,8 +37,8 @@ from ..parallel.asgd import Asynchronous
 from ..parallel.async_sharded import AsyncShardedPSClient
 from ..parallel.clients import (MX8_FLAVOURS, GlooPSClient, LocalPSClient, RcclPSClient,
                                 ShardedPSClient, SharedPSClient, check_push_wire)
-from ..parallel.ddp import BucketedAllReduce, FusedAdamW, FusedSGD
-from ..parallel.fused_optim import Schedule, check_ema_options
+from ..parallel.ddp import BucketedAllReduce, FusedAdamW, FusedLAMB, FusedLARS, FusedSGD
+from ..parallel.fused_optim import KINDS, Schedule, check_ema_options
 from ..parallel.server import ParameterServer, make_ps_groups
 from ..parallel.staleness import check_policy
 from ..utils import checkpoint as ckpt
@@ -74,10 +74,12 @@ class TrainConfig:
     weight_decay: float = 0.0
     lr_schedule: str = "constant"     # "inv_epoch": the reference's LambdaLR(1/(epoch+1)), per
                                       # epoch on the host; "warmup_cosine": per step on the device
-    optimizer: str = "sgd"            # sgd | adamw (parallel/fused_optim.py)
-    beta1: float = 0.9
+    optimizer: str = "sgd"            # sgd | adamw | lamb | lars (parallel/fused_optim.py)
+    beta1: float = 0.9                # AdamW and LAMB
     beta2: float = 0.999
     adam_eps: float = 1e-8
+    trust_coef: float = 0.001         # LARS: local lr = trust_coef ||p|| / (||g|| + wd ||p|| + eps)
+    lars_eps: float = 0.0
     clip_grad_norm: float = 0.0       # global-norm gradient clipping; 0 = off
     warmup_steps: int = 0             # warmup_cosine: linear warm-up updates
     lr_min: float = 0.0               # warmup_cosine: floor reached at schedule_steps
@@ -192,8 +194,8 @@ class Worker:
         params = list(self.model.parameters())
         if cfg.lr_schedule not in ("constant", "inv_epoch", "warmup_cosine"):
             raise ValueError(f"unknown lr_schedule {cfg.lr_schedule!r}")
-        if cfg.optimizer not in ("sgd", "adamw"):
-            raise ValueError(f"unknown optimizer {cfg.optimizer!r}; 'sgd' or 'adamw'")
+        if cfg.optimizer not in KINDS:
+            raise ValueError(f"unknown optimizer {cfg.optimizer!r}; one of {KINDS}")
         # extra optimizer arguments: empty with the defaults, so the plain SGD
         # constructors (and their by-value kernel) are reached exactly as before
         okw = {}
@@ -209,10 +211,14 @@ class Worker:
                        ema_warmup=cfg.model_ema_warmup)
             sgd_kw["model"] = self.model       # FusedSGD: the buffers that are averaged
         adam = dict(betas=(cfg.beta1, cfg.beta2), eps=cfg.adam_eps)
+        lars = dict(trust_coef=cfg.trust_coef, lars_eps=cfg.lars_eps)
+        adam_cls = FusedLAMB if cfg.optimizer == "lamb" else FusedAdamW
         if cfg.mode == "asgd":
             client = client if client is not None else self._make_client(ps_groups)
-            if cfg.optimizer == "adamw":
-                okw.update(optimizer="adamw", **adam)
+            if cfg.optimizer in ("adamw", "lamb"):
+                okw.update(optimizer=cfg.optimizer, **adam)
+            elif cfg.optimizer == "lars":
+                okw.update(optimizer="lars", **lars)
             if cfg.push_wire != "same":      # an explicit client takes the configured wire too
                 okw["push_wire"] = cfg.push_wire
                 okw["push_topk"] = cfg.push_topk
@@ -225,17 +231,25 @@ class Worker:
                 dist.broadcast(self.arena.p32, 0)
                 self.arena.refresh_shadow()
             self.ddp = BucketedAllReduce(self.arena, bucket_mb=cfg.bucket_mb)
-            if cfg.optimizer == "adamw":
-                self.opt = FusedAdamW(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
-                                      grad_scale=1.0 / world, model=self.model, **adam, **okw)
+            if cfg.optimizer in ("adamw", "lamb"):
+                self.opt = adam_cls(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
+                                    grad_scale=1.0 / world, model=self.model, **adam, **okw)
+            elif cfg.optimizer == "lars":
+                self.opt = FusedLARS(params, self.arena, cfg.lr, cfg.momentum,
+                                     weight_decay=cfg.weight_decay, grad_scale=1.0 / world,
+                                     model=self.model, **lars, **okw)
             else:
                 self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
                                     weight_decay=cfg.weight_decay, grad_scale=1.0 / world, **okw,
                                     **sgd_kw)
         elif cfg.mode == "single":
-            if cfg.optimizer == "adamw":
-                self.opt = FusedAdamW(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
-                                      model=self.model, **adam, **okw)
+            if cfg.optimizer in ("adamw", "lamb"):
+                self.opt = adam_cls(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
+                                    model=self.model, **adam, **okw)
+            elif cfg.optimizer == "lars":
+                self.opt = FusedLARS(params, self.arena, cfg.lr, cfg.momentum,
+                                     weight_decay=cfg.weight_decay, model=self.model, **lars,
+                                     **okw)
             else:
                 self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
                                     weight_decay=cfg.weight_decay, **okw, **sgd_kw)
@@ -661,7 +675,7 @@ def check_delay_comp_config(cfg: TrainConfig, info: DistInfo, client=None):
     """Delay compensation corrects a stale push at a PS that hands every worker
     its own snapshot: the central PS, and the shared PS of the virtual workers
     (``client``).  Anywhere else, and with an update that is not proportional to
-    the gradient (AdamW), asking for it is an error at start-up.  SGD with
+    the gradient (AdamW, LAMB, LARS), asking for it is an error at start-up.  SGD with
     momentum passes: its delta is a running mean of gradients, for which
     ``lambda * g*g`` is an approximation."""
     lam = cfg.delay_comp
@@ -672,8 +686,8 @@ def check_delay_comp_config(cfg: TrainConfig, info: DistInfo, client=None):
     what = None
     if cfg.mode != "asgd":
         what = (f"--mode {cfg.mode}", "there is no parameter server and no stale push")
-    elif cfg.optimizer == "adamw":
-        what = ("--optimizer adamw", "its update is not proportional to the gradient, so "
+    elif cfg.optimizer in ("adamw", "lamb", "lars"):
+        what = (f"--optimizer {cfg.optimizer}", "its update is not proportional to the gradient, so "
                 "lambda * g*g is no stand-in for the curvature seen by the pushed delta")
     elif client is not None and not isinstance(client, SharedPSClient):
         what = (type(client).__name__, "this client's server keeps no per-worker backup")
