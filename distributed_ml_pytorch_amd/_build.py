@@ -34,8 +34,9 @@ EXT_NAME = "_native"
 # dwconv so that the two files of this family share one flag set.  optim_trust:
 # memory-bound as well, and stage 1 and stage 2 of LAMB must form the same u bit
 # for bit, which is simplest to keep true with one scalar instruction per
-# operation.
-NO_PACKED_FP32 = {"dwconv", "layer_scale", "optim_trust"}
+# operation.  attention_window: bound by memory and by the softmax's
+# v_exp_f32, where pairing buys nothing; built like the rest of the newer files.
+NO_PACKED_FP32 = {"dwconv", "layer_scale", "optim_trust", "attention_window"}
 _NO_PACKED_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 
 

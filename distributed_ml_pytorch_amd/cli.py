@@ -151,7 +151,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--mix-switch-prob", type=float, default=0.5,
                    help="with --mixup and --cutmix both on: probability of CutMix for a batch")
     p.add_argument("--drop-path", type=float, default=0.0, metavar="RATE",
-                   help="ViT models: stochastic depth (drop path), per sample; RATE in [0, 1) is "
+                   help="ViT, ConvNeXt and Swin models: stochastic depth (drop path), per sample; RATE in [0, 1) is "
                         "the last block's, the blocks ramp up to it linearly (0 = off)")
     p.add_argument("--model-ema", type=float, default=0.0, metavar="DECAY",
                    help="keep an exponential moving average of the weights and BatchNorm "

@@ -3,6 +3,7 @@
 #include "util.h"
 
 #include "attn_plan.h"
+#include "attn_window_plan.h"
 
 namespace dmp::bind {
 namespace {
@@ -137,6 +138,66 @@ Tensor attention_bwd(Tensor qkv, Tensor out, Tensor dout, Tensor lse, int64_t he
   dmp::launch_attention_bwd(bf16(qkv), bf16(out), bf16(dout), lse.data_ptr<float>(), bf16(dqkv),
                             ptr_or_null<float>(ws), (int)B, (int)N, (int)heads, attn_scale(),
                             (int)route, cur_stream());
+  return dqkv;
+}
+
+// ------------------------------------------------ shifted-window attention
+// qkv: [B, Hm, Wm, 3*heads*32] bf16 rows of the qkv projection in map order
+// ([B, Hm, Wm, 3, heads, 32]); table: the fp32 bias parameter [(2 ws - 1)^2, heads].
+void check_win_attn(const Tensor& qkv, const Tensor& table, int64_t heads, int64_t ws, int64_t sh,
+                    int64_t& B, int64_t& Hm, int64_t& Wm, int64_t& C) {
+  check_rows_bf16(qkv, "qkv");
+  TORCH_CHECK(qkv.dim() == 4, "window_attention: qkv must be a [B, Hm, Wm, 3*C] tensor");
+  B = qkv.size(0), Hm = qkv.size(1), Wm = qkv.size(2);
+  TORCH_CHECK(qkv.size(3) % 3 == 0, "window_attention: last dim must be 3*C");
+  C = qkv.size(3) / 3;
+  TORCH_CHECK(heads > 0 && C % heads == 0 && C / heads == dmp::kWinHeadDim,
+              "window_attention: head dim must be ", dmp::kWinHeadDim);
+  TORCH_CHECK(ws >= 1 && ws * ws <= dmp::kWinMaxTokens, "window_attention: window ", ws, " has ",
+              ws * ws, " tokens, the kernels take <= ", dmp::kWinMaxTokens);
+  TORCH_CHECK(sh >= 0 && sh < ws, "window_attention: shift must be in [0, window), got ", sh);
+  TORCH_CHECK(Hm % ws == 0 && Wm % ws == 0, "window_attention: window ", ws,
+              " does not divide the ", Hm, " x ", Wm, " map");
+  TORCH_CHECK(B >= 1 && Hm <= INT32_MAX && Wm <= INT32_MAX &&
+                  dmp::plan_window_attention(B, (int)Hm, (int)Wm, (int)heads, (int)ws, (int)sh).ok,
+              "window_attention: no kernel plan for B ", B, ", map ", Hm, " x ", Wm, ", heads ",
+              heads);
+  check_vec(table, at::kFloat, (2 * ws - 1) * (2 * ws - 1) * heads,
+            "window_attention: table [(2 ws - 1)^2, heads]");
+  TORCH_CHECK(table.device() == qkv.device(), "window_attention: table must be on ", qkv.device());
+}
+
+Tensor window_attention_fwd(Tensor qkv, Tensor table, int64_t heads, int64_t ws, int64_t sh) {
+  int64_t B, Hm, Wm, C;
+  check_win_attn(qkv, table, heads, ws, sh, B, Hm, Wm, C);
+  auto out = at::empty({B, Hm, Wm, C}, qkv.options());
+  dmp::launch_window_attention_fwd(bf16(qkv), table.data_ptr<float>(), bf16(out), B, (int)Hm,
+                                   (int)Wm, (int)heads, (int)ws, (int)sh, cur_stream());
+  return out;
+}
+
+// returns dqkv (qkv layout, every element written once); dtable (fp32, the
+// table's shape) is accumulated into when given
+Tensor window_attention_bwd(Tensor qkv, Tensor dout, Tensor table, optional<Tensor> dtable,
+                            int64_t heads, int64_t ws, int64_t sh) {
+  int64_t B, Hm, Wm, C;
+  check_win_attn(qkv, table, heads, ws, sh, B, Hm, Wm, C);
+  dout = dout.contiguous();
+  check_vec(dout, at::kBFloat16, B * Hm * Wm * C, "window_attention_bwd: dout [B, Hm, Wm, C]");
+  TORCH_CHECK(aligned(dout), "window_attention_bwd: dout must be 16-byte aligned");
+  auto dqkv = at::empty_like(qkv);
+  Tensor slab;
+  if (has(dtable)) {
+    check_vec(*dtable, at::kFloat, table.numel(), "window_attention_bwd: dtable");
+    TORCH_CHECK(dtable->device() == qkv.device(), "window_attention_bwd: dtable must be on ",
+                qkv.device());
+    slab = at::empty({dmp::window_attention_slab_floats(B, (int)Hm, (int)Wm, (int)heads, (int)ws,
+                                                        (int)sh)},
+                     qkv.options().dtype(at::kFloat));
+  }
+  dmp::launch_window_attention_bwd(bf16(qkv), bf16(dout), table.data_ptr<float>(), bf16(dqkv),
+                                   ptr_or_null<float>(dtable), ptr_or_null<float>(slab), B,
+                                   (int)Hm, (int)Wm, (int)heads, (int)ws, (int)sh, cur_stream());
   return dqkv;
 }
 
@@ -463,6 +524,13 @@ void bind_transformer(pybind11::module_& m) {
   m.def("attention_bwd", &attention_bwd, "fused MHSA backward -> dqkv (qkv layout)",
         py::arg("qkv"), py::arg("out"), py::arg("dout"), py::arg("lse"), py::arg("heads"),
         py::arg("route") = -1);
+  m.def("window_attention_fwd", &window_attention_fwd,
+        "shifted-window MHSA forward on map-order qkv rows -> out [B, Hm, Wm, C]", py::arg("qkv"),
+        py::arg("table"), py::arg("heads"), py::arg("window"), py::arg("shift"));
+  m.def("window_attention_bwd", &window_attention_bwd,
+        "shifted-window MHSA backward -> dqkv; the bias-table gradient is added into dtable",
+        py::arg("qkv"), py::arg("dout"), py::arg("table"), py::arg("dtable"), py::arg("heads"),
+        py::arg("window"), py::arg("shift"));
   m.def("gelu_fwd", &gelu_fwd, "tanh-GELU forward");
   m.def("gelu_bwd", &gelu_bwd, "tanh-GELU backward");
   m.def("softmax_fwd", &softmax_fwd, "scaled row softmax forward");

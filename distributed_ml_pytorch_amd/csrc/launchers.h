@@ -384,6 +384,19 @@ void launch_attention_bwd(const uint16_t* qkv, const uint16_t* out, const uint16
                           const float* lse2, uint16_t* dqkv, float* ws, int B, int N, int H,
                           float scale, int route, hipStream_t s);
 
+// attention_window.hip: shifted-window MHSA on [B, Hm, Wm, 3, heads, 32] qkv rows
+// (Swin), fp32 bias table [(2 ws - 1)^2, heads]; the caller has checked
+// plan_window_attention (attn_window_plan.h).  Backward: dtable (accumulated
+// into) and slab (window_attention_slab_floats fp32 elements, uninitialised) are
+// both null when the table needs no gradient.
+long long window_attention_slab_floats(long long B, int Hm, int Wm, int heads, int ws, int sh);
+void launch_window_attention_fwd(const uint16_t* qkv, const float* table, uint16_t* out,
+                                 long long B, int Hm, int Wm, int heads, int ws, int sh,
+                                 hipStream_t s);
+void launch_window_attention_bwd(const uint16_t* qkv, const uint16_t* dout, const float* table,
+                                 uint16_t* dqkv, float* dtable, float* slab, long long B, int Hm,
+                                 int Wm, int heads, int ws, int sh, hipStream_t s);
+
 // linear.hip: bias gradient out[n] += sum_m dy[m][n] (bf16 dy, fp32 out)
 int colsum_num_slots();
 void launch_colsum_acc(const uint16_t* dy, float* out, float* slots, long long M, int N,

@@ -4,6 +4,7 @@ from __future__ import annotations
 from .cnn import MLP, AlexNet, LeNet
 from .convnext import ConvNeXt, convnext_mini, convnext_tiny
 from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101
+from .swin import SwinTransformer, swin_mini, swin_tiny
 from .vit import VisionTransformer, vit_b16, vit_mini_long, vit_tiny
 
 # name -> (constructor, input shape (C,H,W), num_classes)
@@ -22,6 +23,8 @@ REGISTRY = {
     "vit_mini_long": (lambda nc=10, **kw: vit_mini_long(nc, **kw), (3, 80, 80), 10),
     "convnext_tiny": (lambda nc=1000, **kw: convnext_tiny(nc, **kw), (3, 224, 224), 1000),
     "convnext_mini": (lambda nc=10, **kw: convnext_mini(nc, **kw), (3, 32, 32), 10),
+    "swin_tiny": (lambda nc=1000, **kw: swin_tiny(nc, **kw), (3, 224, 224), 1000),
+    "swin_mini": (lambda nc=10, **kw: swin_mini(nc, **kw), (3, 32, 32), 10),
 }
 
 
@@ -30,8 +33,8 @@ def is_vit(name: str) -> bool:
 
 
 def has_drop_path(name: str) -> bool:
-    """Models whose residual adds carry stochastic depth: the ViTs and ConvNeXts."""
-    return _key(name).startswith(("vit_", "convnext_"))
+    """Models whose residual adds carry stochastic depth: the ViTs, ConvNeXts and Swins."""
+    return _key(name).startswith(("vit_", "convnext_", "swin_"))
 
 
 def _key(name: str) -> str:
@@ -41,7 +44,7 @@ def _key(name: str) -> str:
 
 def build_model(name: str, num_classes: int | None = None, drop_path: float = 0.0):
     """Return ``(model, input_shape, num_classes)`` for a registry name.
-    ``drop_path``: stochastic depth rate, for the ViTs and ConvNeXts only."""
+    ``drop_path``: stochastic depth rate, for the ViTs, ConvNeXts and Swins only."""
     key = _key(name)
     if key not in REGISTRY:
         raise KeyError(f"unknown model {name!r}; choose from {sorted(REGISTRY)}")
@@ -52,11 +55,12 @@ def build_model(name: str, num_classes: int | None = None, drop_path: float = 0.
     if drop_path > 0:
         if not has_drop_path(key):
             raise ValueError(f"drop_path {drop_path} with model {name!r}: stochastic depth exists "
-                             "for the ViT and ConvNeXt models only (their residual adds carry it)")
+                             "for the ViT, ConvNeXt and Swin models only (their residual adds carry it)")
         return ctor(nc, drop_path=drop_path), shape, nc
     return ctor(nc), shape, nc
 
 
 __all__ = ["MLP", "AlexNet", "LeNet", "ConvNeXt", "convnext_mini", "convnext_tiny", "ResNet", "resnet18", "resnet34", "resnet50", "resnet101",
+           "SwinTransformer", "swin_mini", "swin_tiny",
            "VisionTransformer", "vit_b16", "vit_mini_long", "vit_tiny", "REGISTRY", "build_model",
            "has_drop_path", "is_vit"]

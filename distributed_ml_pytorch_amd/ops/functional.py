@@ -1198,3 +1198,153 @@ def attention(q, k, v):
         p = _ScaledSoftmax.apply(s, scale)
         return torch.matmul(p, v)
     return F.scaled_dot_product_attention(q, k, v)
+
+
+# --------------------------------------------------- shifted-window attention
+WINDOW_HEAD_DIM = 32          # csrc/attn_window_plan.h kWinHeadDim
+WINDOW_MAX_TOKENS = 64        # kWinMaxTokens: window * window
+WINDOW_MASK_VALUE = -100.0    # kWinMaskValue
+
+
+def window_bias_index(window: int, device=None):
+    """``[N, N]`` rows of the relative-position bias table: pair (i, j) of a
+    ``window`` x ``window`` window reads row ``(yi - yj + ws - 1) * (2 ws - 1) +
+    (xi - xj + ws - 1)``."""
+    c = torch.arange(window, device=device)
+    y, x = (t.reshape(-1) for t in torch.meshgrid(c, c, indexing="ij"))
+    return ((y[:, None] - y[None] + window - 1) * (2 * window - 1)
+            + (x[:, None] - x[None] + window - 1))
+
+
+def window_region_labels(Hm: int, Wm: int, window: int, shift: int, device=None):
+    """``[Hm, Wm]`` region labels of the rolled frame: per axis ``[0, L - ws)``,
+    ``[L - ws, L - sh)``, ``[L - sh, L)``; pairs with different labels are masked."""
+    def axis(L):
+        r = torch.arange(L, device=device)
+        return (r >= L - window).long() + (r >= L - shift).long()
+    return 3 * axis(Hm)[:, None] + axis(Wm)[None]
+
+
+def _windows(t, ws):
+    """``[B, Hm, Wm, ...] -> [B * nW, ws * ws, ...]`` (the window partition)."""
+    B, Hm, Wm = t.shape[:3]
+    rest = t.shape[3:]
+    t = t.reshape(B, Hm // ws, ws, Wm // ws, ws, *rest)
+    perm = (0, 1, 3, 2, 4) + tuple(range(5, 5 + len(rest)))
+    return t.permute(perm).reshape(-1, ws * ws, *rest)
+
+
+def _window_attention_torch(qkv, heads, ws, sh, table):
+    """The op with torch tensor ops, as the paper's code reads: roll, partition,
+    bias gather, ``-100`` mask, softmax, reverse."""
+    B, Hm, Wm, C3 = qkv.shape
+    C, N = C3 // 3, ws * ws
+    x = torch.roll(qkv, (-sh, -sh), (1, 2)) if sh else qkv
+    q, k, v = _windows(x, ws).view(-1, N, 3, heads, C // heads).permute(2, 0, 3, 1, 4)
+    s = (q @ k.transpose(-1, -2)).float() * (C // heads) ** -0.5
+    idx = window_bias_index(ws, qkv.device)
+    s = s + table.float()[idx.reshape(-1)].view(N, N, heads).permute(2, 0, 1)
+    if sh:
+        lab = _windows(window_region_labels(Hm, Wm, ws, sh, qkv.device)[None], ws)
+        mask = (lab[:, :, None] != lab[:, None, :]).float() * WINDOW_MASK_VALUE
+        s = (s.view(B, -1, heads, N, N) + mask[None, :, None]).view(-1, heads, N, N)
+    o = (torch.softmax(s, dim=-1).to(v.dtype) @ v).transpose(1, 2).reshape(-1, N, C)
+    o = o.view(B, Hm // ws, Wm // ws, ws, ws, C).permute(0, 1, 3, 2, 4, 5).reshape(B, Hm, Wm, C)
+    return torch.roll(o, (sh, sh), (1, 2)) if sh else o
+
+
+class _WindowAttention(Function):
+    """``csrc/attention_window.hip``: one wave per (window, head); the backward
+    writes ``dqkv`` in the qkv layout and adds the bias-table gradient into the
+    parameter-gradient sink through a slab reduced in fixed order."""
+
+    @staticmethod
+    def forward(ctx, qkv, table, heads, ws, sh):
+        qkv = qkv.contiguous()
+        ctx.save_for_backward(qkv)
+        ctx.table, ctx.geom = table, (int(heads), int(ws), int(sh))
+        return native().window_attention_fwd(qkv, table.detach(), *ctx.geom)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (qkv,) = ctx.saved_tensors
+        table = ctx.table
+        st = GradSink(table, ctx.needs_input_grad[1])
+        dqkv = native().window_attention_bwd(qkv, dout, table.detach(), st.buf, *ctx.geom)
+        return dqkv, st.done(), None, None, None
+
+
+def window_attention_supported(qkv, heads: int, window: int, shift: int, table) -> bool:
+    """Mirror of the binding's argument check (csrc/attn_window_plan.h)."""
+    if not (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 4):
+        return False
+    _, Hm, Wm, C3 = qkv.shape
+    T = (2 * window - 1) ** 2
+    return (qkv.numel() > 0 and heads > 0 and C3 == 3 * heads * WINDOW_HEAD_DIM
+            and 1 <= window * window <= WINDOW_MAX_TOKENS and 0 <= shift < window
+            and Hm % window == 0 and Wm % window == 0 and table.dtype == torch.float32
+            and tuple(table.shape) == (T, heads) and table.device == qkv.device)
+
+
+def window_attention(qkv, heads: int, window: int, shift: int, table):
+    """Shifted-window multi-head self-attention (Swin) straight from the qkv
+    projection rows in map order.
+
+    ``qkv``: ``[B, Hm, Wm, 3 * C]`` (= ``[B, Hm, Wm, 3, heads, C / heads]``); returns
+    ``[B, Hm, Wm, C]`` at the same pixels.  Each ``window`` x ``window`` window of
+    the map rolled by ``-shift`` attends within itself, with the learned
+    relative-position bias ``table`` (fp32 ``[(2 window - 1)^2, heads]``) added to
+    the scaled scores and ``-100`` added between regions the roll brought together.
+    On the GPU (bf16, head dim 32, ``window^2 <= 64``, the window dividing the map)
+    the roll, the partition and their inverses are address arithmetic inside the
+    kernels of ``csrc/attention_window.hip``.  On the CPU, and on the GPU in the
+    stock oracle mode only, the same op in torch tensor ops."""
+    if window < 1 or not 0 <= shift < window or qkv.dim() != 4 \
+            or qkv.shape[1] % window or qkv.shape[2] % window:
+        raise ValueError(f"window_attention: window {window} / shift {shift} do not fit a "
+                         f"{tuple(qkv.shape[1:3])} map (the window must divide it, 0 <= shift < "
+                         "window)")
+    if window_attention_supported(qkv, heads, window, shift, table):
+        if torch.is_grad_enabled() and (qkv.requires_grad or table.requires_grad):
+            return _WindowAttention.apply(qkv, table, heads, window, shift)
+        return native().window_attention_fwd(qkv.contiguous(), table.detach(), int(heads),
+                                             int(window), int(shift))
+    stock_gpu("window_attention (roll + partition + torch.matmul)", qkv,
+              reason=f"{qkv.dtype}, head dim {qkv.shape[-1] // 3 // max(heads, 1)}, window "
+                     f"{window}: the window kernels take bf16, head dim {WINDOW_HEAD_DIM}, "
+                     f"window^2 <= {WINDOW_MAX_TOKENS}")
+    return _window_attention_torch(qkv, heads, window, shift, table)
+
+
+# ------------------------------------------------------- 2x2 patch gather
+class _PatchGather(Function):
+    """``[B, H, W, C] -> [B, H/p, W/p, p*p*C]`` rows, k = (r, s, c): the patch
+    matrix kernel of ``csrc/im2col.hip`` at stride = window, and its gather-form
+    inverse for the gradient (every input pixel lies in exactly one patch)."""
+
+    @staticmethod
+    def forward(ctx, h, p):
+        B, H, W, C = h.shape
+        ctx.geom = (B, C, H, W, int(p))
+        cols = native().im2col(h.contiguous().permute(0, 3, 1, 2), p, p, p, 0, p * p * C)
+        return cols.view(B, H // p, W // p, p * p * C)
+
+    @staticmethod
+    def backward(ctx, dcols):
+        B, C, H, W, p = ctx.geom
+        dx = native().col2im(dcols.contiguous().view(-1, p * p * C), B, C, H, W, p, p, p, 0)
+        return dx.permute(0, 2, 3, 1), None
+
+
+def patch_gather(h, p: int = 2):
+    """Channels-last ``p`` x ``p`` / stride ``p`` patches of a ``[B, H, W, C]`` map as
+    rows ``[B, H/p, W/p, p*p*C]`` with k = (r, s, c): Swin's patch merging gather.
+    Native for bf16 GPU maps with ``C % 8 == 0``; reshape + permute elsewhere."""
+    B, H, W, C = h.shape
+    if H % p or W % p:
+        raise ValueError(f"patch_gather: {p} does not divide the {H} x {W} map")
+    if h.is_cuda and h.dtype == torch.bfloat16 and C % 8 == 0:
+        return _PatchGather.apply(h, p)
+    stock_gpu("patch_gather", h)
+    return (h.reshape(B, H // p, p, W // p, p, C).permute(0, 1, 3, 2, 4, 5)
+            .reshape(B, H // p, W // p, p * p * C))

@@ -617,7 +617,7 @@ def check_drop_path_config(cfg: TrainConfig):
         raise ValueError(f"--drop-path must be in [0, 1), got {cfg.drop_path}")
     if cfg.drop_path > 0 and not has_drop_path(cfg.model):
         raise ValueError(f"--drop-path {cfg.drop_path} with --model {cfg.model}: stochastic depth "
-                         "exists for the ViT and ConvNeXt models only (the ResNets' residual "
+                         "exists for the ViT, ConvNeXt and Swin models only (the ResNets' residual "
                          "add lives in the BatchNorm kernels)")
 
 
