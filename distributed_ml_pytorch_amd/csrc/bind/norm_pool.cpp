@@ -1,5 +1,5 @@
-// bn.hip, pool.hip, head.hip: BatchNorm, pooling, the GAP + Linear head and the
-// ReLU backward (im2col.hip).
+// bn.hip, group_norm.hip, pool.hip, head.hip: BatchNorm, GroupNorm, pooling, the
+// GAP + Linear head and the ReLU backward (im2col.hip).
 #include "util.h"
 
 namespace dmp::bind {
@@ -264,6 +264,115 @@ std::vector<Tensor> bn_fold_weights(Tensor w, optional<Tensor> gamma, optional<T
   return {w16, b32, b16};
 }
 
+// ---------------------------------------------------------------- groupnorm
+// group_norm.hip under group_norm_plan.h.  route: -1 automatic, 0 resident, 1
+// streaming; a forced route the planner cannot honour is an error.
+dmp::GnPlan gn_plan_of(int64_t N, int64_t C, int64_t HW, int64_t G, int64_t route, bool backward,
+                       const char* fn) {
+  TORCH_CHECK(C >= 8 && C % 8 == 0 && C <= dmp::kGnMaxC && G >= 1 && C % G == 0 &&
+                  dmp::gn_cpg_ok((int)(C / G)),
+              fn, ": C = ", C, ", G = ", G, " outside coverage (C % 8 == 0, C <= ", dmp::kGnMaxC,
+              ", C / G in {1, 2, 4} or a multiple of 8)");
+  TORCH_CHECK(route >= -1 && route <= 1, fn, ": route must be -1, 0 or 1");
+  const dmp::GnPlan p = dmp::plan_group_norm(N, (int)C, HW, (int)G, (int)route, backward);
+  TORCH_CHECK(p.ok, fn, ": no plan for N = ", N, ", C = ", C, ", HW = ", HW, ", G = ", G,
+              route == 0 ? " on the resident route (the slice does not fit LDS)"
+                         : " (over 32-bit offsets, the LDS or the part / batch caps)");
+  return p;
+}
+
+struct GnGeom {
+  int N, C, HW;
+};
+
+GnGeom gn_geom(const Tensor& x, const char* fn) {
+  check_nhwc_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 4 && x.numel() > 0, fn, ": non-empty 4-D channels_last input expected");
+  return {(int)x.size(0), (int)x.size(1), (int)(x.size(2) * x.size(3))};
+}
+
+// -> (y, stats fp32 [2, N, G]: mean, rstd)
+std::vector<Tensor> gn_fwd(Tensor x, optional<Tensor> res, Tensor gamma, Tensor beta, int64_t G,
+                           double eps, bool relu, int64_t route) {
+  const GnGeom g = gn_geom(x, "gn_fwd");
+  const dmp::GnPlan p = gn_plan_of(g.N, g.C, g.HW, G, route, false, "gn_fwd");
+  if (has(res)) {
+    check_nhwc_bf16(*res, "res");
+    same_shape(*res, x, "res");
+  }
+  check_vec(gamma, at::kFloat, g.C, "gn gamma");
+  check_vec(beta, at::kFloat, g.C, "gn beta");
+  auto fopt = x.options().dtype(at::kFloat);
+  auto y = at::empty_like(x);
+  auto stats = at::empty({2, g.N, G}, fopt);
+  Tensor part;
+  if (p.route == 1) part = at::empty({g.N, p.parts, G, 3}, fopt.dtype(at::kDouble));
+  dmp::launch_gn_fwd(p, bf16(x), bf16_or_null(res), gamma.data_ptr<float>(),
+                     beta.data_ptr<float>(), bf16(y), stats.data_ptr<float>(),
+                     stats.data_ptr<float>() + (int64_t)g.N * G, ptr_or_null<double>(part), g.N,
+                     g.C, g.HW, (int)G, (float)eps, relu, cur_stream());
+  return {y, stats};
+}
+
+// -> (dx, dres: dy * [y > 0], undefined unless want_dres); dgamma / dbeta += through
+// `slab` (the layer's persistent one, or a fresh one)
+std::vector<Tensor> gn_bwd(Tensor x, Tensor dy, optional<Tensor> y, Tensor gamma, Tensor stats,
+                           int64_t G, bool relu, bool want_dres, optional<Tensor> dgamma,
+                           optional<Tensor> dbeta, optional<Tensor> slab, int64_t route) {
+  const GnGeom g = gn_geom(x, "gn_bwd");
+  const dmp::GnPlan p = gn_plan_of(g.N, g.C, g.HW, G, route, true, "gn_bwd");
+  if (!dy.is_contiguous(kCL)) dy = dy.contiguous(kCL);
+  check_nhwc_bf16(dy, "dy");
+  same_shape(dy, x, "dy");
+  if (relu) {
+    TORCH_CHECK(has(y), "gn_bwd: the fused ReLU needs the forward's y");
+    check_nhwc_bf16(*y, "y");
+    same_shape(*y, x, "y");
+  }
+  check_vec(gamma, at::kFloat, g.C, "gn gamma");
+  check_vec(stats, at::kFloat, 2 * (int64_t)g.N * G, "gn stats [2, N, G]");
+  check_vecs({&dgamma, &dbeta}, at::kFloat, g.C, "gn dgamma / dbeta");
+  auto fopt = x.options().dtype(at::kFloat);
+  Tensor sl, part;
+  if (has(dgamma) || has(dbeta)) {
+    const int64_t n = dmp::gn_slab_floats(g.C);
+    if (has(slab)) {
+      check_vec(*slab, at::kFloat, n, "gn slab");
+      sl = *slab;
+    } else {
+      sl = at::empty({n}, fopt);
+    }
+  }
+  if (p.route == 1) part = at::empty({g.N, p.parts, G, 2}, fopt.dtype(at::kDouble));
+  auto dx = at::empty_like(x);
+  Tensor dres;
+  if (want_dres) dres = at::empty_like(x);
+  dmp::launch_gn_bwd(p, bf16(x), bf16(dy), bf16_or_null(y), gamma.data_ptr<float>(),
+                     stats.data_ptr<float>(), stats.data_ptr<float>() + (int64_t)g.N * G, bf16(dx),
+                     bf16_or_null(dres), ptr_or_null<float>(dgamma), ptr_or_null<float>(dbeta),
+                     ptr_or_null<float>(sl), ptr_or_null<double>(part), g.N, g.C, g.HW, (int)G,
+                     relu, cur_stream());
+  return {dx, dres};
+}
+
+py::dict gn_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t G, int64_t route,
+                 bool backward) {
+  const dmp::GnPlan p = gn_plan_of(N, C, H * W, G, route, backward, "gn_plan");
+  py::dict d;
+  d["route"] = p.route == 0 ? "resident" : "stream";
+  d["slice_channels"] = p.SV * dmp::kGnVec;
+  d["slices"] = p.slices;
+  d["groups_per_slice"] = p.GS;
+  d["pixel_rows"] = p.PR;
+  d["threads"] = dmp::kGnThreads;
+  d["parts"] = p.parts;
+  d["part_pixels"] = p.PP;
+  d["lds_bytes"] = p.lds_bytes;
+  d["grid"] = py::make_tuple(p.grid[0], p.grid[1], p.grid[2]);
+  d["slab_rows"] = p.slab_rows;
+  return d;
+}
+
 // ------------------------------------------------------------------ pooling
 // fused GAP + Linear head: [y [B, N] bf16, f [B, C] bf16 (pooled features, kept
 // for the weight gradient)]
@@ -447,6 +556,20 @@ void bind_norm_pool(pybind11::module_& m) {
         py::arg("dy"), py::arg("y"), py::arg("gamma"), py::arg("stats"), py::arg("dgamma"),
         py::arg("dbeta"), py::arg("relu"), py::arg("want_dres"), py::arg("slots") = py::none(),
         py::arg("mask") = py::none(), py::arg("batch_stats") = true);
+  m.def("gn_fwd", &gn_fwd, "NHWC groupnorm(+residual)(+relu) forward -> (y, stats [2, N, G])",
+        py::arg("x"), py::arg("res"), py::arg("gamma"), py::arg("beta"), py::arg("G"),
+        py::arg("eps"), py::arg("relu"), py::arg("route") = -1);
+  m.def("gn_bwd", &gn_bwd, "NHWC groupnorm(+residual)(+relu) backward -> (dx, dres)",
+        py::arg("x"), py::arg("dy"), py::arg("y"), py::arg("gamma"), py::arg("stats"),
+        py::arg("G"), py::arg("relu"), py::arg("want_dres"), py::arg("dgamma") = py::none(),
+        py::arg("dbeta") = py::none(), py::arg("slab") = py::none(), py::arg("route") = -1);
+  m.def("gn_plan", &gn_plan, "what the GroupNorm planner chose for a geometry", py::arg("N"),
+        py::arg("C"), py::arg("H"), py::arg("W"), py::arg("G"), py::arg("route") = -1,
+        py::arg("backward") = false);
+  m.def("gn_slab_numel", [](int64_t C) {
+          TORCH_CHECK(C >= 8 && C <= dmp::kGnMaxC, "gn_slab_numel: C = ", C);
+          return (int64_t)dmp::gn_slab_floats((int)C);
+        }, "fp32 words of a GroupNorm layer's dgamma / dbeta slab");
   m.def("relu_bwd", &relu_bwd, "ReLU backward from the saved output", py::arg("dy"), py::arg("y"),
         py::arg("out") = py::none());
   m.def("gap_fwd", &gap_fwd, "NHWC global average pool forward");

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "bn_slots.h"
+#include "group_norm_plan.h"
 #include <stdint.h>
 
 namespace dmp {
@@ -474,5 +475,19 @@ void launch_layer_scale_fwd(const uint16_t* x, const uint16_t* r, const float* g
 void launch_layer_scale_bwd(const uint16_t* dh, const uint16_t* r, const float* gamma,
                             const float* rscale, uint16_t* dr, float* dgamma, float* slots,
                             long long rows, int C, int tokens, hipStream_t s);
+
+// group_norm.hip: GroupNorm (+ residual) (+ ReLU) over [N][HW][C] bf16 under a plan
+// that plan_group_norm (group_norm_plan.h) accepted for (N, C, HW, G).  mean / rstd:
+// fp32 [N][G]; part: streaming partials, fp64 [N][parts][G][3] (null when resident)
+void launch_gn_fwd(const GnPlan& p, const uint16_t* x, const uint16_t* res, const float* gamma,
+                   const float* beta, uint16_t* y, float* mean, float* rstd, double* part, int N,
+                   int C, int HW, int G, float eps, bool relu, hipStream_t s);
+// dx, dres = dy * [y > 0] (null: skipped); dgamma / dbeta [C] += their gradients
+// (null: skipped) by a fixed-order reduce of `slab` (gn_slab_floats(C) words,
+// overwritten); part: fp64 [N][parts][G][2] (null when resident); y: with relu only
+void launch_gn_bwd(const GnPlan& p, const uint16_t* x, const uint16_t* dy, const uint16_t* y,
+                   const float* gamma, const float* mean, const float* rstd, uint16_t* dx,
+                   uint16_t* dres, float* dgamma, float* dbeta, float* slab, double* part, int N,
+                   int C, int HW, int G, bool relu, hipStream_t s);
 
 }  // namespace dmp

@@ -3,7 +3,8 @@ from __future__ import annotations
 
 from .cnn import MLP, AlexNet, LeNet
 from .convnext import ConvNeXt, convnext_mini, convnext_tiny
-from .resnet import ResNet, resnet18, resnet34, resnet50, resnet101
+from .resnet import (ResNet, resnet18, resnet18_gn, resnet34, resnet34_gn, resnet50, resnet50_gn,
+                     resnet101)
 from .swin import SwinTransformer, swin_mini, swin_tiny
 from .vit import VisionTransformer, vit_b16, vit_mini_long, vit_tiny
 
@@ -17,6 +18,10 @@ REGISTRY = {
     "resnet50": (lambda nc=1000: resnet50(nc, stem="imagenet"), (3, 224, 224), 1000),
     "resnet50_cifar": (lambda nc=10: resnet50(nc, stem="cifar"), (3, 32, 32), 10),
     "resnet101": (lambda nc=1000: resnet101(nc, stem="imagenet"), (3, 224, 224), 1000),
+    "resnet18_gn": (lambda nc=10: resnet18_gn(nc, stem="cifar"), (3, 32, 32), 10),
+    "resnet34_gn": (lambda nc=10: resnet34_gn(nc, stem="cifar"), (3, 32, 32), 10),
+    "resnet50_gn": (lambda nc=1000: resnet50_gn(nc, stem="imagenet"), (3, 224, 224), 1000),
+    "resnet50_gn_cifar": (lambda nc=10: resnet50_gn(nc, stem="cifar"), (3, 32, 32), 10),
     "vit_b16": (lambda nc=1000, **kw: vit_b16(nc, **kw), (3, 224, 224), 1000),
     "vit_b16_384": (lambda nc=1000, **kw: vit_b16(nc, image_size=384, **kw), (3, 384, 384), 1000),
     "vit_tiny": (lambda nc=10, **kw: vit_tiny(nc, **kw), (3, 32, 32), 10),
@@ -61,6 +66,7 @@ def build_model(name: str, num_classes: int | None = None, drop_path: float = 0.
 
 
 __all__ = ["MLP", "AlexNet", "LeNet", "ConvNeXt", "convnext_mini", "convnext_tiny", "ResNet", "resnet18", "resnet34", "resnet50", "resnet101",
+           "resnet18_gn", "resnet34_gn", "resnet50_gn",
            "SwinTransformer", "swin_mini", "swin_tiny",
            "VisionTransformer", "vit_b16", "vit_mini_long", "vit_tiny", "REGISTRY", "build_model",
            "has_drop_path", "is_vit"]

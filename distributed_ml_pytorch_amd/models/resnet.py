@@ -13,6 +13,14 @@ block output ``relu(bn2(conv2(h)) + shortcut)`` is ONE kernel on GPU.  In eval
 mode under ``no_grad`` (the reference's evaluation loop) every BatchNorm is
 folded into its conv instead (ops/eval_fold.py): one launch per conv, none
 per BatchNorm.
+
+``norm="gn"`` (the ``*_gn`` registry names) puts ``L.GroupNorm(min(gn_groups, C),
+C)`` wherever a BatchNorm stands, on the fused GN(+residual)(+ReLU) kernels of
+``csrc/group_norm.hip``.  Such a model has no buffers: everything an
+asynchronous worker evaluates with travels in the parameter arena, where a
+BatchNorm model evaluates pulled weights against running statistics of its own
+shard.  GroupNorm is the same function in train and eval mode, so there is no
+eval fold, and the ImageNet stem runs GN + ReLU and then the max pool.
 """
 from __future__ import annotations
 
@@ -32,25 +40,48 @@ from ..ops.linear import gap_linear, gap_linear_ok
 _SC_SUB = os.environ.get("DMP_SC_SUB", "1") != "0"
 
 
+def _norm(norm: str, channels: int, gn_groups: int, relu: bool = False):
+    """The normalisation after a conv: BatchNorm, or GroupNorm of
+    ``min(gn_groups, channels)`` groups (``norm="gn"``)."""
+    if norm == "bn":
+        return L.BatchNorm2d(channels, relu=relu)
+    if norm == "gn":
+        return L.GroupNorm(min(gn_groups, channels), channels, relu=relu)
+    raise ValueError(f"unknown norm {norm!r} (bn | gn)")
+
+
 def _sc_sub(shortcut) -> bool:
     """A 1x1 / stride-2 / unpadded shortcut conv that can run on x[:, :, ::2, ::2]."""
     return (shortcut is not None and _SC_SUB and shortcut[0].kernel_size == (1, 1)
             and shortcut[0].stride == (2, 2) and shortcut[0].padding == (0, 0))
 
 
+def _shortcut(shortcut, xa, x, sub: bool):
+    """The shortcut branch on conv1's alias ``xa`` (GroupNorm blocks; the BatchNorm
+    blocks spell the same three cases out next to their deferred-mask notes)."""
+    if shortcut is None:
+        return xa
+    if sub and xa.shape[-1] != x.shape[-1]:
+        return shortcut[1](shortcut[0](xa, stride=1))
+    return shortcut(xa)
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, cin: int, planes: int, stride: int = 1):
+    def __init__(self, cin: int, planes: int, stride: int = 1, norm: str = "bn",
+                 gn_groups: int = 32):
         super().__init__()
+        self.norm = norm
         self.conv1 = L.Conv2d(cin, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn1 = L.BatchNorm2d(planes, relu=True)
+        self.bn1 = _norm(norm, planes, gn_groups, relu=True)
         self.conv2 = L.Conv2d(planes, planes, 3, stride=1, padding=1, bias=False)
-        self.bn2 = L.BatchNorm2d(planes, relu=True)
+        self.bn2 = _norm(norm, planes, gn_groups, relu=True)
         self.shortcut = None
         if stride != 1 or cin != planes:
             self.shortcut = nn.Sequential(
-                L.Conv2d(cin, planes, 1, stride=stride, bias=False), L.BatchNorm2d(planes))
+                L.Conv2d(cin, planes, 1, stride=stride, bias=False),
+                _norm(norm, planes, gn_groups))
 
     def _forward_folded(self, x):
         h = conv_bn(x, self.conv1, self.bn1)
@@ -61,7 +92,18 @@ class BasicBlock(nn.Module):
             return None
         return conv_bn(h, self.conv2, self.bn2, residual=sc)
 
+    def _forward_gn(self, x):
+        # GroupNorm has no mode and nothing to fold; its residual gradient is
+        # always fully masked, so the shortcut carries no deferred-mask mark
+        sub = self.conv1.stride == (2, 2) and _sc_sub(self.shortcut)
+        h, xa = self.conv1(x, alias="sub" if sub else True)
+        h = self.bn1(h)
+        sc = _shortcut(self.shortcut, xa, x, sub)
+        return self.bn2(self.conv2(h), residual=sc)
+
     def forward(self, x):
+        if self.norm == "gn":
+            return self._forward_gn(x)
         if fold_enabled(x, self):
             y = self._forward_folded(x)
             if y is not None:
@@ -91,19 +133,21 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, cin: int, planes: int, stride: int = 1):
+    def __init__(self, cin: int, planes: int, stride: int = 1, norm: str = "bn",
+                 gn_groups: int = 32):
         super().__init__()
+        self.norm = norm
         out = planes * self.expansion
         self.conv1 = L.Conv2d(cin, planes, 1, bias=False)
-        self.bn1 = L.BatchNorm2d(planes, relu=True)
+        self.bn1 = _norm(norm, planes, gn_groups, relu=True)
         self.conv2 = L.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
-        self.bn2 = L.BatchNorm2d(planes, relu=True)
+        self.bn2 = _norm(norm, planes, gn_groups, relu=True)
         self.conv3 = L.Conv2d(planes, out, 1, bias=False)
-        self.bn3 = L.BatchNorm2d(out, relu=True)
+        self.bn3 = _norm(norm, out, gn_groups, relu=True)
         self.shortcut = None
         if stride != 1 or cin != out:
             self.shortcut = nn.Sequential(
-                L.Conv2d(cin, out, 1, stride=stride, bias=False), L.BatchNorm2d(out))
+                L.Conv2d(cin, out, 1, stride=stride, bias=False), _norm(norm, out, gn_groups))
 
     def _forward_folded(self, x):
         h = conv_bn(x, self.conv1, self.bn1)
@@ -115,7 +159,16 @@ class Bottleneck(nn.Module):
             return None
         return conv_bn(h, self.conv3, self.bn3, residual=sc)
 
+    def _forward_gn(self, x):
+        sub = _sc_sub(self.shortcut)
+        h, xa = self.conv1(x, alias="sub" if sub else True)
+        h = self.bn2(self.conv2(self.bn1(h)))
+        sc = _shortcut(self.shortcut, xa, x, sub)
+        return self.bn3(self.conv3(h), residual=sc)
+
     def forward(self, x):
+        if self.norm == "gn":
+            return self._forward_gn(x)
         if fold_enabled(x, self):
             y = self._forward_folded(x)
             if y is not None:
@@ -139,9 +192,10 @@ class Bottleneck(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, block, layers, num_classes: int = 10, stem: str = "cifar",
-                 zero_init_residual: bool = False):
+                 zero_init_residual: bool = False, norm: str = "bn", gn_groups: int = 32):
         super().__init__()
         self.stem_kind = stem
+        self.norm = norm
         if stem == "cifar":
             self.conv1 = L.Conv2d(3, 64, 3, stride=1, padding=1, bias=False)
             self.pool = None
@@ -150,14 +204,15 @@ class ResNet(nn.Module):
             self.pool = L.MaxPool2d(3, stride=2, padding=1)
         else:
             raise ValueError(f"unknown stem {stem!r}")
-        self.bn1 = L.BatchNorm2d(64, relu=True)
+        self.bn1 = _norm(norm, 64, gn_groups, relu=True)
         cin = 64
         stages = []
         for i, (planes, n) in enumerate(zip((64, 128, 256, 512), layers)):
             blocks = []
             for j in range(n):
                 stride = 2 if (i > 0 and j == 0) else 1
-                blocks.append(block(cin, planes, stride))
+                blocks.append(block(cin, planes, stride) if norm == "bn"
+                              else block(cin, planes, stride, norm, gn_groups))
                 cin = planes * block.expansion
             stages.append(nn.Sequential(*blocks))
         self.layer1, self.layer2, self.layer3, self.layer4 = stages
@@ -166,7 +221,7 @@ class ResNet(nn.Module):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
-            if isinstance(m, L.Conv2d):
+            if isinstance(m, L.Conv2d) and norm == "bn":
                 m.emit_bn_stats = True      # every conv here feeds a BatchNorm
         if zero_init_residual:
             for m in self.modules():
@@ -176,7 +231,9 @@ class ResNet(nn.Module):
                     nn.init.zeros_(m.bn2.weight)
 
     def forward(self, x):
-        h = conv_bn(x, self.conv1, self.bn1) if fold_enabled(x, self) else None
+        gn = self.norm == "gn"     # no eval fold, no fused stem pool: GN + ReLU, then the pool
+        h = self.bn1(self.conv1(x)) if gn else (
+            conv_bn(x, self.conv1, self.bn1) if fold_enabled(x, self) else None)
         pooled = False
         if h is None:
             h = self.conv1(x)
@@ -208,3 +265,15 @@ def resnet50(num_classes: int = 1000, stem: str = "imagenet", **kw) -> ResNet:
 
 def resnet101(num_classes: int = 1000, stem: str = "imagenet", **kw) -> ResNet:
     return ResNet(Bottleneck, (3, 4, 23, 3), num_classes, stem, **kw)
+
+
+def resnet18_gn(num_classes: int = 10, stem: str = "cifar", **kw) -> ResNet:
+    return resnet18(num_classes, stem, norm="gn", **kw)
+
+
+def resnet34_gn(num_classes: int = 10, stem: str = "cifar", **kw) -> ResNet:
+    return resnet34(num_classes, stem, norm="gn", **kw)
+
+
+def resnet50_gn(num_classes: int = 1000, stem: str = "imagenet", **kw) -> ResNet:
+    return resnet50(num_classes, stem, norm="gn", **kw)

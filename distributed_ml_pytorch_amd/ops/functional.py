@@ -606,6 +606,111 @@ def bn_relu_maxpool(x, bn, k: int, s: int, p: int):
     return set_nonneg(y)
 
 
+# ------------------------------------------------------------------ GroupNorm
+def group_norm_route() -> int:
+    """Route request of the GroupNorm bindings, read per call: -1 automatic (the
+    planner of ``csrc/group_norm_plan.h``); ``DMP_GN_ROUTE=resident`` / ``stream``
+    forces one (A/Bs and tests; a forced route that does not fit is an error)."""
+    r = os.environ.get("DMP_GN_ROUTE", "")
+    if r not in ("", "resident", "stream"):
+        raise ValueError(f"DMP_GN_ROUTE must be 'resident' or 'stream', got {r!r}")
+    return {"": -1, "resident": 0, "stream": 1}[r]
+
+
+def group_norm_slab(owner, x):
+    """Persistent ``dgamma`` / ``dbeta`` slab of a GroupNorm layer on ``owner``
+    (overwritten by every backward: never zeroed).  Its size depends on the
+    channel count alone, so an evaluation at another batch size keeps what a
+    captured step holds."""
+    n = native().gn_slab_numel(x.shape[1])
+    buf = owner.__dict__.get("_dmp_gn_slab")
+    if buf is None or buf.device != x.device or buf.numel() != n:
+        buf = torch.empty(n, dtype=torch.float32, device=x.device)
+        owner.__dict__["_dmp_gn_slab"] = buf
+    return buf
+
+
+class _GroupNormAct(Function):
+    """GroupNorm (+ residual) (+ ReLU) on ``csrc/group_norm.hip``.  The residual's
+    gradient is always the fully masked ``dy * [y > 0]`` (or ``dy`` itself without
+    a ReLU): no deferred-mask hand-off."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, groups, eps, relu, slab, route):
+        x = x.contiguous(memory_format=CL)
+        if residual is not None:
+            residual = residual.contiguous(memory_format=CL)
+        y, stats = native().gn_fwd(x, residual, gamma.detach(), beta.detach(), int(groups),
+                                   float(eps), bool(relu), int(route))
+        ctx.save_for_backward(x, stats, *((y,) if relu else ()))
+        ctx.gamma, ctx.beta, ctx.slab = gamma, beta, slab
+        ctx.meta = (int(groups), bool(relu), int(route), residual is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, stats = ctx.saved_tensors[:2]
+        groups, relu, route, has_res = ctx.meta
+        y = ctx.saved_tensors[2] if relu else None
+        gamma, beta = ctx.gamma, ctx.beta
+        sg = GradSink(gamma, ctx.needs_input_grad[2])
+        sb = GradSink(beta, ctx.needs_input_grad[3])
+        need_res = has_res and ctx.needs_input_grad[1]
+        dx, dres = native().gn_bwd(x, dy.to(x.dtype), y, gamma.detach(), stats, groups, relu,
+                                   need_res and relu, sg.buf, sb.buf, ctx.slab, route)
+        if need_res and not relu:
+            dres = dy
+        return (dx if ctx.needs_input_grad[0] else None, dres if need_res else None, sg.done(),
+                sb.done(), None, None, None, None, None)
+
+
+def group_norm_supported(x, groups: int, weight, bias) -> bool:
+    """Coverage of the native GroupNorm: bf16 GPU 4-D input, fp32 affine, ``C % 8 ==
+    0``, ``C <= 2048`` and ``C / groups`` in {1, 2, 4} or a multiple of 8."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and x.numel() > 0):
+        return False
+    C = x.shape[1]
+    cpg = C // groups if groups > 0 and C % groups == 0 else 0
+    return (C % 8 == 0 and C <= 2048 and (cpg in (1, 2, 4) or (cpg > 0 and cpg % 8 == 0))
+            and weight is not None and bias is not None and weight.dtype == torch.float32
+            and bias.dtype == torch.float32)
+
+
+def group_norm_act(x, groups: int, weight, bias, eps: float, relu: bool = False, residual=None,
+                   slab=None):
+    """``relu?(group_norm(x) * weight + bias [+ residual])`` over ``[N, C, H, W]``.
+
+    The specification, and the CPU path, is the torch expression below: fp32,
+    mean and *centred* biased variance over the ``H*W*C/groups`` elements of each
+    (sample, group), ``((x - mean) * rstd) * weight + bias``, then the residual and
+    the ReLU, one rounding to ``x``'s dtype.  bf16 GPU input inside
+    :func:`group_norm_supported` runs ``csrc/group_norm.hip`` (route:
+    :func:`group_norm_route`); any other GPU input is refused by ``stock_gpu``
+    outside the oracle mode.  ``slab``: the layer's :func:`group_norm_slab`."""
+    if group_norm_supported(x, groups, weight, bias) and (
+            residual is None or (residual.dtype == x.dtype and residual.shape == x.shape)):
+        y = _GroupNormAct.apply(x, residual, weight, bias, groups, eps, relu, slab,
+                                group_norm_route())
+        return set_nonneg(y, relu)
+    stock_gpu("group_norm", x, reason=f"dtype {x.dtype}, shape {tuple(x.shape)}, {groups} groups")
+    N, C = x.shape[:2]
+    xf = x.float().reshape(N, groups, -1)
+    mean = xf.mean(-1, keepdim=True)
+    d = xf - mean
+    rstd = torch.rsqrt((d * d).mean(-1, keepdim=True) + eps)
+    t = (d * rstd).reshape(x.shape)
+    shape = (1, C) + (1,) * (x.dim() - 2)
+    if weight is not None:
+        t = t * weight.float().view(shape)
+    if bias is not None:
+        t = t + bias.float().view(shape)
+    if residual is not None:
+        t = t + residual.float()
+    if relu:
+        t = torch.relu(t)
+    return t.to(x.dtype)
+
+
 # ----------------------------------------------------------------------- ReLU
 class _ReLU(Function):
     """Standalone ReLU (where no producing GEMM / conv epilogue can take it):

@@ -120,6 +120,24 @@ class BatchNorm1d(nn.BatchNorm1d):
             relu=self.relu, residual=residual, slots=self._slots(x))
 
 
+class GroupNorm(nn.GroupNorm):
+    """GroupNorm with optional fused residual-add and ReLU epilogue
+    (``csrc/group_norm.hip``).  No buffers and no mode: train and eval run the
+    same kernels, and the whole state is the two arena parameters."""
+
+    def __init__(self, num_groups, num_channels, eps=1e-5, affine=True, relu: bool = False, **kw):
+        super().__init__(num_groups, num_channels, eps=eps, affine=affine, **kw)
+        self.relu = relu
+
+    def forward(self, x, residual=None):
+        # the slab only where a backward can follow (not in a no_grad evaluation)
+        slab = DF.group_norm_slab(self, x) if (
+            torch.is_grad_enabled() and self.affine and self.weight.requires_grad
+            and DF.group_norm_supported(x, self.num_groups, self.weight, self.bias)) else None
+        return DF.group_norm_act(x, self.num_groups, self.weight, self.bias, self.eps,
+                                 relu=self.relu, residual=residual, slab=slab)
+
+
 class MaxPool2d(nn.MaxPool2d):
     def native_params(self):
         """(k, s, p) as ints when the native floor-mode square pool applies, else
