@@ -23,12 +23,13 @@ from __future__ import annotations
 
 import torch
 import torch.distributed as dist
-from torch.optim.optimizer import Optimizer, required
+from torch.optim.optimizer import required
 
 from .arena import attach_arena, get_arena
 from .clients import GlooPSClient, LocalPSClient, PSClient, check_push_wire
 from .ema import ModelEma
-from .fused_optim import KINDS, FusedOptimCore, check_ema_options, sync_base_lr
+from .fused_optim import (KINDS, ArenaOptimizer, FusedOptimCore, check_ema_options,
+                          sgd_by_value)
 
 
 def default_client(**kw) -> PSClient:
@@ -38,7 +39,9 @@ def default_client(**kw) -> PSClient:
     return LocalPSClient(**kw)
 
 
-class Asynchronous(Optimizer):
+class Asynchronous(ArenaOptimizer):
+    has_client = True
+
     def __init__(self, params, lr=required, n_push=required, n_pull=required, model=required, *,
                  client: PSClient | None = None, staleness: int = 1, momentum: float = 0.0,
                  dampening: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0,
@@ -75,32 +78,27 @@ class Asynchronous(Optimizer):
         if optimizer == "lars" and (nesterov or dampening):
             raise ValueError("optimizer 'lars' takes neither nesterov nor dampening")
         check_ema_options(ema_decay, ema_every, ema_warmup)
-        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
-                        weight_decay=weight_decay)
-        super().__init__(params, defaults)
-        self.model = model
-        self.n_push = int(n_push)
-        self.n_pull = int(n_pull)
         arena = get_arena(model)
         if arena is None:
             dev = next(model.parameters()).device
             if shadow_dtype == "auto":
                 shadow_dtype = torch.bfloat16 if dev.type == "cuda" else None
             arena = attach_arena(model, shadow_dtype=shadow_dtype)
-        self.arena = arena
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, nesterov=nesterov,
+                        weight_decay=weight_decay)
+        super().__init__(params, defaults, arena,
+                         mom=bool(momentum and optimizer == "sgd") or optimizer == "lars")
+        self.model = model
+        self.n_push = int(n_push)
+        self.n_pull = int(n_pull)
         mine = {id(p) for g in self.param_groups for p in g["params"]}
         if mine != {id(p) for p in arena.params}:
             raise ValueError("Asynchronous must be given exactly model.parameters() "
                              "(the push/pull vector is the whole model, as in the reference)")
-        dev = arena.device
-        self.acc = torch.zeros(arena.numel, dtype=torch.float32, device=dev)
-        self._mom_steps = 0
-        self.mom = torch.zeros_like(self.acc) if (momentum and optimizer == "sgd") or \
-            optimizer == "lars" else None
+        self.acc = torch.zeros(arena.numel, dtype=torch.float32, device=arena.device)
         # AdamW, clipping, a per-step schedule or a model EMA: the update reads lr
         # and the gradient scale from a device-resident hyper block
         # (fused_optim.py); plain constant-lr SGD keeps the by-value kernel
-        self.core = None
         if optimizer != "sgd" or max_grad_norm > 0 or schedule is not None or ema_decay > 0:
             trust = dict(trust_coef=trust_coef, lars_eps=lars_eps) if optimizer == "lars" else {}
             self.core = FusedOptimCore(arena, optimizer, lr, betas=betas, eps=eps,
@@ -121,74 +119,22 @@ class Asynchronous(Optimizer):
         self.client.attach(self)
         self.client.init()
         # the average starts from the parameters as the PS client left them
-        self.ema = None
         if ema_decay > 0:
             self.core.reset_ema()
             self.ema = ModelEma(model, self.core, self.client)
-        self._nat = None
-        if dev.type == "cuda":
-            from ..ops._ext import native
-
-            self._nat = native()
 
     # reference-visible attributes -----------------------------------------
     @property
     def accumulated_gradients(self) -> torch.Tensor:
         return self.acc
 
-    def zero_grad(self, set_to_none: bool = False):
-        """Zero the flat grad arena (views stay attached; ``set_to_none`` ignored).
-        Opens the compute half of a step (closed by ``local_step``)."""
-        self.client.in_compute = True
-        self.arena.ensure_grads_attached()
-        self.arena.zero_grad()
-
-    def _local_update(self, lr: float):
-        g = self.param_groups[0]
-        a = self.arena
-        # torch.optim.SGD seeds the momentum buffer with the first gradient
-        # (no dampening); the buffer starts at zero, so dampening 0 on the
-        # first update gives exactly that
-        damp = g["dampening"] if self._mom_steps > 0 else 0.0
-        self._mom_steps += 1
+    def _update(self, g):
+        """Fused accumulate + SGD (or the core's kind), the push accumulator included."""
+        damp = self._first_step_dampening(g)
         if self.core is not None:
-            sync_base_lr(self.core, lr)
-            self.core.step(a, self.acc, self.mom, damp)
-            return
-        if self._nat is not None:
-            self._nat.asgd_fused_step(a.g32, a.p32, self.acc, self.mom, a.w16, lr,
-                                      g["weight_decay"], g["momentum"], damp, g["nesterov"])
-            return
-        with torch.no_grad():
-            d = a.g32
-            if g["weight_decay"]:
-                d = d + g["weight_decay"] * a.p32
-            if self.mom is not None:
-                self.mom.mul_(g["momentum"]).add_(d, alpha=1 - damp)
-                d = d + g["momentum"] * self.mom if g["nesterov"] else self.mom
-            self.acc.add_(d, alpha=-lr)
-            a.p32.add_(d, alpha=-lr)
-            if a.w16 is not None:
-                a.w16.copy_(a.p32)
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self.local_step()
-        self.comm_step()
-        return loss
-
-    @torch.no_grad()
-    def local_step(self):
-        """Device-only half of a step (graph-capturable): fused accumulate + SGD."""
-        self._local_update(self.param_groups[0]["lr"])
-        if self.ema is not None:
-            self.ema.update_buffers()
-        self.arena.bump()
-        self.client.in_compute = False
+            return self._core_step(self.acc, self.mom, damp)
+        sgd_by_value(self.arena, self.acc, self.mom, g["lr"], g["weight_decay"], g["momentum"],
+                     damp, g["nesterov"])
 
     @torch.no_grad()
     def comm_step(self):

@@ -27,11 +27,10 @@ import time
 
 import torch
 import torch.distributed as dist
-from torch.optim.optimizer import Optimizer
 
 from .arena import FlatArena
 from .ema import ModelEma
-from .fused_optim import FusedOptimCore, check_ema_options, sync_base_lr
+from .fused_optim import ArenaOptimizer, FusedOptimCore, check_ema_options, sgd_by_value
 
 
 _CAL_MB = (2.0, 4.0, 8.0, 16.0, 32.0, 64.0)
@@ -155,7 +154,7 @@ class BucketedAllReduce:
         return len(self.buckets)
 
 
-class FusedSGD(Optimizer):
+class FusedSGD(ArenaOptimizer):
     """Plain/momentum SGD over a flat arena in one fused HIP kernel.
 
     Used by sync-DP (with ``grad_scale = 1/world``) and by the reference's
@@ -171,14 +170,11 @@ class FusedSGD(Optimizer):
         that are averaged with the parameters (None: parameters only)."""
         check_ema_options(ema_decay, ema_every, ema_warmup)
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening,
-                                      nesterov=nesterov, weight_decay=weight_decay))
-        self.arena = arena
+                                      nesterov=nesterov, weight_decay=weight_decay),
+                         arena, mom=bool(momentum))
         self.grad_scale = grad_scale
-        self.mom = torch.zeros_like(arena.p32) if momentum else None
-        self._mom_steps = 0
         # clipping, a per-step schedule or a model EMA: lr and the gradient scale
         # (1/W included) come from the device-resident hyper block (fused_optim.py)
-        self.core = None
         if max_grad_norm > 0 or schedule is not None or ema_decay > 0:
             self.core = FusedOptimCore(arena, "sgd", lr, weight_decay=weight_decay,
                                        momentum=momentum, nesterov=nesterov,
@@ -186,71 +182,23 @@ class FusedSGD(Optimizer):
                                        schedule=schedule, ema_decay=ema_decay,
                                        ema_every=ema_every, ema_warmup=ema_warmup)
         self.ema = ModelEma(model, self.core) if ema_decay > 0 else None
-        self._nat = None
-        if arena.device.type == "cuda":
-            from ..ops._ext import native
 
-            self._nat = native()
-
-    def zero_grad(self, set_to_none: bool = False):
-        self.arena.ensure_grads_attached()
-        self.arena.zero_grad()
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self.local_step()
-        return loss
-
-    def comm_step(self):
-        pass
-
-    @torch.no_grad()
-    def local_step(self):
-        g = self.param_groups[0]
-        a = self.arena
-        lr = g["lr"]
-        a.bump()
+    def _update(self, g):
+        damp = self._first_step_dampening(g)
         if self.core is not None:
-            damp = g["dampening"] if self._mom_steps > 0 else 0.0
-            self._mom_steps += 1
-            sync_base_lr(self.core, lr)
-            self.core.step(a, None, self.mom, damp)
-            if self.ema is not None:
-                self.ema.update_buffers()
-            return
+            return self._core_step(None, self.mom, damp)
+        lr, wd = g["lr"], g["weight_decay"]
         if self.grad_scale != 1.0:
-            # fold the 1/W average into lr (and rescale weight decay so wd*p is not scaled)
-            lr_eff = lr * self.grad_scale
-            wd_eff = g["weight_decay"] / self.grad_scale
-        else:
-            lr_eff, wd_eff = lr, g["weight_decay"]
-        if self.mom is not None and self.grad_scale != 1.0:
-            # momentum must see the averaged gradient: scale grads explicitly
-            a.g32.mul_(self.grad_scale)
-            lr_eff, wd_eff = lr, g["weight_decay"]
-        # first update: momentum buffer = gradient, as torch.optim.SGD (no dampening)
-        damp = g["dampening"] if self._mom_steps > 0 else 0.0
-        self._mom_steps += 1
-        if self._nat is not None:
-            self._nat.asgd_fused_step(a.g32, a.p32, None, self.mom, a.w16, lr_eff, wd_eff,
-                                      g["momentum"], damp, g["nesterov"])
-        else:
-            d = a.g32
-            if wd_eff:
-                d = d + wd_eff * a.p32
-            if self.mom is not None:
-                self.mom.mul_(g["momentum"]).add_(d, alpha=1 - damp)
-                d = d + g["momentum"] * self.mom if g["nesterov"] else self.mom
-            a.p32.add_(d, alpha=-lr_eff)
-            if a.w16 is not None:
-                a.w16.copy_(a.p32)
+            if self.mom is None:
+                # fold the 1/W average into lr (and rescale weight decay so wd*p is not scaled)
+                lr, wd = lr * self.grad_scale, wd / self.grad_scale
+            else:
+                # momentum must see the averaged gradient: scale grads explicitly
+                self.arena.g32.mul_(self.grad_scale)
+        sgd_by_value(self.arena, None, self.mom, lr, wd, g["momentum"], damp, g["nesterov"])
 
 
-class FusedAdamW(Optimizer):
+class FusedAdamW(ArenaOptimizer):
     """AdamW over a flat arena in one fused HIP kernel (``sync`` / ``single``).
 
     Decoupled weight decay skips 1-D parameters and the names ``model``
@@ -265,8 +213,8 @@ class FusedAdamW(Optimizer):
                  eps: float = 1e-8, weight_decay: float = 0.01, grad_scale: float = 1.0,
                  max_grad_norm: float = 0.0, schedule=None, model=None,
                  ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False):
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        self.arena = arena
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay),
+                         arena)
         self.core = FusedOptimCore(arena, self.KIND, lr, betas=betas, eps=eps,
                                    weight_decay=weight_decay, grad_scale=grad_scale,
                                    max_grad_norm=max_grad_norm, schedule=schedule, model=model,
@@ -274,29 +222,8 @@ class FusedAdamW(Optimizer):
                                    ema_warmup=ema_warmup)
         self.ema = ModelEma(model, self.core) if ema_decay > 0 else None
 
-    def zero_grad(self, set_to_none: bool = False):
-        self.arena.ensure_grads_attached()
-        self.arena.zero_grad()
-
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self.local_step()
-        return loss
-
-    def comm_step(self):
-        pass
-
-    @torch.no_grad()
-    def local_step(self):
-        self.arena.bump()
-        sync_base_lr(self.core, self.param_groups[0]["lr"])
-        self.core.step(self.arena, None)
-        if self.ema is not None:
-            self.ema.update_buffers()
+    def _update(self, g):
+        self._core_step()
 
 
 class FusedLAMB(FusedAdamW):
@@ -308,7 +235,7 @@ class FusedLAMB(FusedAdamW):
     KIND = "lamb"
 
 
-class FusedLARS(Optimizer):
+class FusedLARS(ArenaOptimizer):
     """LARS with momentum over a flat arena (``sync`` / ``single``): SGD whose
     gradient and weight decay are scaled per tensor by the local learning rate
     ``trust_coef ||p|| / (||g|| + wd ||p|| + lars_eps)`` for every tensor with
@@ -319,11 +246,10 @@ class FusedLARS(Optimizer):
                  weight_decay: float = 0.0, trust_coef: float = 0.001, lars_eps: float = 0.0,
                  grad_scale: float = 1.0, max_grad_norm: float = 0.0, schedule=None, model=None,
                  ema_decay: float = 0.0, ema_every: int = 1, ema_warmup: bool = False):
+        # the momentum buffer always exists: checkpointed where FusedSGD's is
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay,
-                                      trust_coef=trust_coef, lars_eps=lars_eps))
-        self.arena = arena
-        self.mom = torch.zeros_like(arena.p32)      # checkpointed where FusedSGD's is
-        self._mom_steps = 0
+                                      trust_coef=trust_coef, lars_eps=lars_eps),
+                         arena, mom=True)
         self.core = FusedOptimCore(arena, "lars", lr, weight_decay=weight_decay,
                                    momentum=momentum, grad_scale=grad_scale,
                                    max_grad_norm=max_grad_norm, schedule=schedule, model=model,
@@ -332,27 +258,7 @@ class FusedLARS(Optimizer):
                                    lars_eps=lars_eps)
         self.ema = ModelEma(model, self.core) if ema_decay > 0 else None
 
-    def zero_grad(self, set_to_none: bool = False):
-        self.arena.ensure_grads_attached()
-        self.arena.zero_grad()
+    def _update(self, g):
+        self._mom_steps += 1        # counted as FusedSGD's; LARS takes no dampening
+        self._core_step(None, self.mom)
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
-        self.local_step()
-        return loss
-
-    def comm_step(self):
-        pass
-
-    @torch.no_grad()
-    def local_step(self):
-        self.arena.bump()
-        self._mom_steps += 1
-        sync_base_lr(self.core, self.param_groups[0]["lr"])
-        self.core.step(self.arena, None, self.mom)
-        if self.ema is not None:
-            self.ema.update_buffers()

@@ -81,6 +81,7 @@ import math
 from dataclasses import asdict, dataclass
 
 import torch
+from torch.optim.optimizer import Optimizer
 
 from .arena import ALIGN, FlatArena
 
@@ -558,3 +559,103 @@ class FusedOptimCore:
                 _LOG.warning("model EMA: the checkpoint holds no EMA of this arena; starting "
                              "the average from the loaded parameters")
                 self.reset_ema()
+
+
+def sgd_by_value(arena: FlatArena, acc: torch.Tensor | None, mom: torch.Tensor | None,
+                 lr: float, wd: float, momentum: float, dampening: float, nesterov: bool):
+    """torch.optim.SGD on ``arena.g32`` with lr and wd passed by value (plain
+    constant-lr SGD, no hyper block): one ``asgd_fused_step`` launch on the GPU.
+    ``acc`` (the Downpour push accumulator) receives the applied ``-lr * d``."""
+    a = arena
+    if a.device.type == "cuda":
+        from ..ops._ext import native
+
+        native().asgd_fused_step(a.g32, a.p32, acc, mom, a.w16, lr, wd, momentum, dampening,
+                                 nesterov)
+        return
+    d = a.g32
+    if wd:
+        d = d + wd * a.p32
+    if mom is not None:
+        mom.mul_(momentum).add_(d, alpha=1 - dampening)
+        d = d + momentum * mom if nesterov else mom
+    if acc is not None:
+        acc.add_(d, alpha=-lr)
+    a.p32.add_(d, alpha=-lr)
+    if a.w16 is not None:
+        a.w16.copy_(a.p32)
+
+
+class ArenaOptimizer(Optimizer):
+    """Host side shared by every optimizer over one flat arena (``ddp.Fused*``,
+    ``asgd.Asynchronous``): the step protocol ``zero_grad`` / ``local_step`` (device
+    only, graph-capturable) / ``comm_step`` (host-scheduled) / ``finish``, and the
+    state a checkpoint reads: ``arena``, ``core`` (None: the by-value SGD kernel),
+    ``mom``, ``acc``, ``ema``.  A subclass builds its core and writes ``_update``."""
+    acc = None              # push accumulator (Asynchronous)
+    timer = None            # a utils.metrics.StepTimer when the trainer wires one
+    # Asynchronous: ``self.client`` is a PS client; zero_grad opens its compute half,
+    # local_step closes it and bumps the arena after the update, not before
+    has_client = False
+
+    def __init__(self, params, defaults: dict, arena: FlatArena, mom: bool = False):
+        super().__init__(params, defaults)
+        self.arena = arena
+        self.core = None
+        self.ema = None
+        self.mom = torch.zeros_like(arena.p32) if mom else None
+        self._mom_steps = 0
+        if arena.device.type == "cuda":
+            from ..ops._ext import native
+
+            native()        # a missing extension fails here, not at the first step
+
+    def zero_grad(self, set_to_none: bool = False):
+        """Zero the flat grad arena (views stay attached; ``set_to_none`` ignored)."""
+        if self.has_client:
+            self.client.in_compute = True
+        self.arena.ensure_grads_attached()
+        self.arena.zero_grad()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self.local_step()
+        self.comm_step()
+        return loss
+
+    @torch.no_grad()
+    def local_step(self):
+        """Device-only half of a step (graph-capturable)."""
+        if not self.has_client:
+            self.arena.bump()
+        self._update(self.param_groups[0])
+        if self.ema is not None:
+            self.ema.update_buffers()
+        if self.has_client:
+            self.arena.bump()
+            self.client.in_compute = False
+
+    def comm_step(self):
+        """Host-scheduled half of a step: nothing without a parameter server."""
+
+    def finish(self):
+        pass
+
+    def _update(self, g: dict):
+        raise NotImplementedError
+
+    def _first_step_dampening(self, g: dict) -> float:
+        """torch.optim.SGD seeds the momentum buffer with the first gradient (no
+        dampening); the buffer starts at zero, so dampening 0 on the first update
+        gives exactly that.  Counts the update."""
+        damp = g["dampening"] if self._mom_steps > 0 else 0.0
+        self._mom_steps += 1
+        return damp
+
+    def _core_step(self, acc=None, mom=None, dampening: float = 0.0):
+        sync_base_lr(self.core, self.param_groups[0]["lr"])
+        self.core.step(self.arena, acc, mom, dampening)

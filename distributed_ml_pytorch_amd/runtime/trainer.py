@@ -52,6 +52,9 @@ from .dist import DistInfo, preflight
 
 _LOG = logging.getLogger(__name__)
 
+# ``sync`` / ``single``: the optimizer class of a kind (``asgd``: Asynchronous takes the kind)
+_ARENA_OPTIMIZERS = {"sgd": FusedSGD, "adamw": FusedAdamW, "lamb": FusedLAMB, "lars": FusedLARS}
+
 
 class DivergenceError(RuntimeError):
     """Training produced non-finite parameters (the log-interval watchdog)."""
@@ -196,8 +199,8 @@ class Worker:
             raise ValueError(f"unknown lr_schedule {cfg.lr_schedule!r}")
         if cfg.optimizer not in KINDS:
             raise ValueError(f"unknown optimizer {cfg.optimizer!r}; one of {KINDS}")
-        # extra optimizer arguments: empty with the defaults, so the plain SGD
-        # constructors (and their by-value kernel) are reached exactly as before
+        # optional optimizer arguments: none of clipping, schedule and EMA with the
+        # defaults, so plain SGD keeps its by-value kernel (``opt.core is None``)
         okw = {}
         if cfg.clip_grad_norm > 0:
             okw["max_grad_norm"] = cfg.clip_grad_norm
@@ -205,58 +208,38 @@ class Worker:
             total = cfg.schedule_steps or cfg.max_steps or \
                 cfg.epochs * max(1, cfg.n_train // cfg.batch_size)
             okw["schedule"] = Schedule("warmup_cosine", cfg.warmup_steps, total, cfg.lr_min)
-        sgd_kw = {}
         if cfg.model_ema > 0:
             okw.update(ema_decay=cfg.model_ema, ema_every=cfg.model_ema_every,
                        ema_warmup=cfg.model_ema_warmup)
-            sgd_kw["model"] = self.model       # FusedSGD: the buffers that are averaged
-        adam = dict(betas=(cfg.beta1, cfg.beta2), eps=cfg.adam_eps)
-        lars = dict(trust_coef=cfg.trust_coef, lars_eps=cfg.lars_eps)
-        adam_cls = FusedLAMB if cfg.optimizer == "lamb" else FusedAdamW
+        # what the kind takes beyond lr and weight decay
+        okw.update({"sgd": dict(momentum=cfg.momentum),
+                    "adamw": dict(betas=(cfg.beta1, cfg.beta2), eps=cfg.adam_eps),
+                    "lamb": dict(betas=(cfg.beta1, cfg.beta2), eps=cfg.adam_eps),
+                    "lars": dict(momentum=cfg.momentum, trust_coef=cfg.trust_coef,
+                                 lars_eps=cfg.lars_eps)}[cfg.optimizer])
         if cfg.mode == "asgd":
             client = client if client is not None else self._make_client(ps_groups)
-            if cfg.optimizer in ("adamw", "lamb"):
-                okw.update(optimizer=cfg.optimizer, **adam)
-            elif cfg.optimizer == "lars":
-                okw.update(optimizer="lars", **lars)
+            okw.setdefault("momentum", cfg.momentum)
             if cfg.push_wire != "same":      # an explicit client takes the configured wire too
                 okw["push_wire"] = cfg.push_wire
                 okw["push_topk"] = cfg.push_topk
             self.opt = Asynchronous(params, lr=cfg.lr, n_push=cfg.n_push, n_pull=cfg.n_pull,
-                                    model=self.model, client=client, momentum=cfg.momentum,
+                                    model=self.model, client=client, optimizer=cfg.optimizer,
                                     weight_decay=cfg.weight_decay, **okw)
-        elif cfg.mode == "sync":
-            world = dist.get_world_size() if info.is_distributed else 1
-            if info.is_distributed:
-                dist.broadcast(self.arena.p32, 0)
-                self.arena.refresh_shadow()
-            self.ddp = BucketedAllReduce(self.arena, bucket_mb=cfg.bucket_mb)
-            if cfg.optimizer in ("adamw", "lamb"):
-                self.opt = adam_cls(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
-                                    grad_scale=1.0 / world, model=self.model, **adam, **okw)
-            elif cfg.optimizer == "lars":
-                self.opt = FusedLARS(params, self.arena, cfg.lr, cfg.momentum,
-                                     weight_decay=cfg.weight_decay, grad_scale=1.0 / world,
-                                     model=self.model, **lars, **okw)
-            else:
-                self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
-                                    weight_decay=cfg.weight_decay, grad_scale=1.0 / world, **okw,
-                                    **sgd_kw)
-        elif cfg.mode == "single":
-            if cfg.optimizer in ("adamw", "lamb"):
-                self.opt = adam_cls(params, self.arena, cfg.lr, weight_decay=cfg.weight_decay,
-                                    model=self.model, **adam, **okw)
-            elif cfg.optimizer == "lars":
-                self.opt = FusedLARS(params, self.arena, cfg.lr, cfg.momentum,
-                                     weight_decay=cfg.weight_decay, model=self.model, **lars,
-                                     **okw)
-            else:
-                self.opt = FusedSGD(params, self.arena, cfg.lr, cfg.momentum,
-                                    weight_decay=cfg.weight_decay, **okw, **sgd_kw)
+        elif cfg.mode in ("sync", "single"):
+            grad_scale = 1.0        # sync: the 1/world average, folded into the update
+            if cfg.mode == "sync":
+                grad_scale = 1.0 / (dist.get_world_size() if info.is_distributed else 1)
+                if info.is_distributed:
+                    dist.broadcast(self.arena.p32, 0)
+                    self.arena.refresh_shadow()
+                self.ddp = BucketedAllReduce(self.arena, bucket_mb=cfg.bucket_mb)
+            self.opt = _ARENA_OPTIMIZERS[cfg.optimizer](
+                params, self.arena, cfg.lr, weight_decay=cfg.weight_decay, grad_scale=grad_scale,
+                model=self.model, **okw)
         else:
             raise ValueError(f"unknown mode {cfg.mode!r}")
-        if isinstance(self.opt, Asynchronous):
-            self.opt.timer = self.timer
+        self.opt.timer = self.timer
         if resume:
             ckpt.load_worker_optimizer(resume, self.opt)
 
@@ -389,8 +372,7 @@ class Worker:
         """A by-value lr is baked into the captured update kernel, so it keys the
         graph; with the device-resident hyper block (``opt.core``) the kernels
         read lr from memory and the graph survives any learning rate."""
-        lr = None if getattr(self.opt, "core", None) is not None else \
-            self.opt.param_groups[0]["lr"]
+        lr = None if self.opt.core is not None else self.opt.param_groups[0]["lr"]
         return (tuple(x.shape), x.dtype, lr)
 
     def _capture_agreed(self, ok: bool) -> bool:
@@ -499,7 +481,7 @@ class Worker:
         reference's verbose per-class precision/recall/F1 table (main.py:127-131).
         """
         if ema:
-            avg = getattr(self.opt, "ema", None)
+            avg = self.opt.ema
             if avg is None:
                 raise ValueError("evaluate(ema=True) needs a run with model_ema > 0")
             with avg.applied():
@@ -541,13 +523,11 @@ class Worker:
     def set_lr(self, lr: float):
         for g in self.opt.param_groups:
             g["lr"] = lr
-        core = getattr(self.opt, "core", None)
-        if core is not None:          # between steps, never inside a capture
-            core.set_base_lr(lr)
+        if self.opt.core is not None:          # between steps, never inside a capture
+            self.opt.core.set_base_lr(lr)
 
     def finish(self):
-        if isinstance(self.opt, Asynchronous):
-            self.opt.finish()
+        self.opt.finish()
 
 
 def check_stale_config(cfg: TrainConfig, info: DistInfo):
@@ -789,7 +769,7 @@ def run_training(cfg: TrainConfig, info: DistInfo):
             tr = torch.utils.data.Subset(tr, idx)
         train_loader, test_loader = make_loaders(tr, te, cfg.batch_size, cfg.test_batch_size,
                                                  shuffle_seed=cfg.seed + info.rank)
-    core = getattr(w.opt, "core", None)
+    core = w.opt.core
     if core is not None and cfg.lr_schedule == "warmup_cosine" and \
             not (cfg.schedule_steps or cfg.max_steps) and core.t == 0:
         core.set_total_steps(max(cfg.epochs * len(train_loader), cfg.warmup_steps + 1))

@@ -45,27 +45,23 @@ def save_worker_checkpoint(path: str, model: torch.nn.Module, optimizer=None, st
     sd = {"kind": "worker", "step": int(step),
           "model": {k: v.detach().cpu() for k, v in model.state_dict().items()}}
     if optimizer is not None:
-        acc = getattr(optimizer, "acc", None)
-        mom = getattr(optimizer, "mom", None)
+        acc, mom = optimizer.acc, optimizer.mom
         sd["opt"] = {
-            "idx": int(getattr(optimizer, "idx", step)),
+            "idx": int(optimizer.idx if optimizer.has_client else step),
             "lr": float(optimizer.param_groups[0]["lr"]),
             "acc": acc.detach().cpu() if acc is not None else None,
             "mom": mom.detach().cpu() if mom is not None else None,
         }
-        core = getattr(optimizer, "core", None)
-        if core is not None:
+        if optimizer.core is not None:
             # AdamW moments, step count and schedule (parallel/fused_optim.py)
-            sd["opt"].update(core.state_dict())
-        ema = getattr(optimizer, "ema", None)
-        if ema is not None:
+            sd["opt"].update(optimizer.core.state_dict())
+        if optimizer.ema is not None:
             # averaged model buffers (parallel/ema.py); the averaged parameters are
             # part of the core's state above
-            sd["ema"] = ema.state_dict()
-        client = getattr(optimizer, "client", None)
-        if client is not None:
+            sd["ema"] = optimizer.ema.state_dict()
+        if optimizer.has_client:
             # PS state held on this worker (in-process master / its sharded-PS shard)
-            sd["client"] = client.state_dict()
+            sd["client"] = optimizer.client.state_dict()
     if extra:
         sd["extra"] = extra
     _atomic_save(sd, path)
@@ -104,29 +100,27 @@ def load_worker_optimizer(path: str, optimizer) -> None:
     sd = _load_worker_sd(path)
     if "opt" in sd:
         o = sd["opt"]
-        if hasattr(optimizer, "idx"):
+        if optimizer.has_client:
             optimizer.idx = o["idx"]
         for g in optimizer.param_groups:
             g["lr"] = o["lr"]
         with torch.no_grad():
-            if o.get("acc") is not None and getattr(optimizer, "acc", None) is not None:
+            if o.get("acc") is not None and optimizer.acc is not None:
                 optimizer.acc.copy_(o["acc"])
-            if o.get("mom") is not None and getattr(optimizer, "mom", None) is not None:
+            if o.get("mom") is not None and optimizer.mom is not None:
                 optimizer.mom.copy_(o["mom"])
                 optimizer._mom_steps = max(1, int(o.get("idx", 1)))   # buffer already seeded
-        core = getattr(optimizer, "core", None)
+        core = optimizer.core
         if core is not None and "t" in o:     # absent in checkpoints of plain SGD runs
             core.load_state_dict(o)
         elif core is not None and core.ema is not None:
             _LOG.warning("model EMA: the checkpoint holds no EMA; starting the average from "
                          "the loaded parameters")
             core.reset_ema()
-    ema = getattr(optimizer, "ema", None)
-    if ema is not None:       # EMA state in a checkpoint is ignored when EMA is off
-        ema.load_state_dict(sd.get("ema"))
-    client = getattr(optimizer, "client", None)
-    if client is not None and sd.get("client"):
-        client.load_state_dict(sd["client"])
+    if optimizer.ema is not None:       # EMA state in a checkpoint is ignored when EMA is off
+        optimizer.ema.load_state_dict(sd.get("ema"))
+    if optimizer.has_client and sd.get("client"):
+        optimizer.client.load_state_dict(sd["client"])
 
 
 def load_worker_checkpoint(path: str, model: torch.nn.Module, optimizer=None) -> int:

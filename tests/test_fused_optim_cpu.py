@@ -261,6 +261,79 @@ def test_default_options_take_the_existing_path():
         Asynchronous(m.parameters(), lr=0.1, n_push=1, n_pull=1, model=m, optimizer="adam")
 
 
+def _two_linear(seed=0):
+    torch.manual_seed(seed)
+    return torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.ReLU(), torch.nn.Linear(5, 3))
+
+
+def _by_value_cases():
+    for scale in (1.0, 0.5):
+        yield scale, 0.0, False
+        for nesterov in (False, True):
+            yield scale, 0.9, nesterov
+
+
+@pytest.mark.parametrize("grad_scale,momentum,nesterov", list(_by_value_cases()))
+def test_by_value_sgd_written_out(grad_scale, momentum, nesterov):
+    """The by-value path (``core is None``) of FusedSGD, grad_scale != 1 included,
+    and of Asynchronous against the update written out with the same fp32 torch
+    operations in the same order: bit for bit, no tolerance."""
+    lr, wd, dampening, steps = 0.05, 1e-3, 0.3, 4
+    model = _two_linear()
+    arena = attach_arena(model, shadow_dtype=None)
+    opt = FusedSGD(model.parameters(), arena, lr, momentum, dampening, nesterov, wd,
+                   grad_scale=grad_scale)
+    amodel = _two_linear()
+    aopt = Asynchronous(amodel.parameters(), lr=lr, n_push=10 ** 6, n_pull=10 ** 6, model=amodel,
+                        client=LocalPSClient(staleness=0), momentum=momentum,
+                        dampening=dampening, nesterov=nesterov, weight_decay=wd,
+                        shadow_dtype=None)
+    assert opt.core is None and aopt.core is None
+    assert (opt.mom is not None) == bool(momentum) == (aopt.mom is not None)
+    grads = _grads(arena, steps=steps)
+    p, mom = arena.p32.clone(), torch.zeros_like(arena.p32) if momentum else None
+    ap, amom, aacc = p.clone(), None if mom is None else mom.clone(), torch.zeros_like(p)
+    assert torch.equal(aopt.arena.p32, ap)
+    for t, g in enumerate(grads):
+        damp = dampening if t > 0 else 0.0
+        # FusedSGD: the three grad_scale cases, then the update
+        g32 = g.clone()
+        if grad_scale != 1.0:
+            lr_eff, wd_eff = lr * grad_scale, wd / grad_scale
+        else:
+            lr_eff, wd_eff = lr, wd
+        if mom is not None and grad_scale != 1.0:
+            g32.mul_(grad_scale)
+            lr_eff, wd_eff = lr, wd
+        d = g32
+        if wd_eff:
+            d = d + wd_eff * p
+        if mom is not None:
+            mom.mul_(momentum).add_(d, alpha=1 - damp)
+            d = d + momentum * mom if nesterov else mom
+        p.add_(d, alpha=-lr_eff)
+        arena.g32.copy_(g)
+        opt.local_step()
+        assert torch.equal(arena.p32, p), t
+        if mom is not None:
+            assert torch.equal(opt.mom, mom), t
+        # Asynchronous: the same update on the unscaled gradient, accumulated for the push
+        d = g
+        if wd:
+            d = d + wd * ap
+        if amom is not None:
+            amom.mul_(momentum).add_(d, alpha=1 - damp)
+            d = d + momentum * amom if nesterov else amom
+        aacc.add_(d, alpha=-lr)
+        ap.add_(d, alpha=-lr)
+        aopt.arena.g32.copy_(g)
+        aopt.local_step()
+        assert torch.equal(aopt.arena.p32, ap) and torch.equal(aopt.acc, aacc), t
+        if amom is not None:
+            assert torch.equal(aopt.mom, amom), t
+    assert opt.core is None and aopt.core is None
+
+
 def test_cli_flags():
     from distributed_ml_pytorch_amd.cli import build_parser, config_from_args
     from distributed_ml_pytorch_amd.runtime.trainer import TrainConfig
